@@ -21,7 +21,16 @@ timed region; `hbm_resident_fps` is the compute lane alone.
 
 Prints ONE JSON line (rank 0).
 
-`metric` / `value` = BASELINE.json's metric: ENCODED fps of the whole encoder with the HIP path bound in (integration/_build/
+A plain run (`--gpus 1 --steps K --warmup W`) measures the front half alone, in this process, through the HIP library: it sets the loop up, runs W
+warm-up steps, times K steps and prints `value` = pictures per second through the loop above and `ms_per_step` = milliseconds per step (2 lanes x
+64 pictures at 4K).  `--dump-outputs DIR` writes what the last timed step handed back to the host: a fixed, seeded sample of 1024 of its LCUs'
+compact motion-estimation and open-loop intra records (DIR/front_half_me_records.npy, DIR/front_half_ois_records.npy: their bytes as float32,
+one row per LCU; DIR/front_half_sample_index.npy: which LCUs).  Its inputs come from the committed fixtures and a seeded clip, so two builds of
+the library compare output for output.  Everything else below - the whole-encoder figure, which needs the reference encoder built from the
+reference's sources (oracle/_ref/hooked), its md5 gate, the CPU baselines, the HBM-resident loop, the rooflines and their counter passes, the
+encode pass, the exchange legs of N > 1 - runs with `--full`, which adds those measurements to the same line.
+
+`encoded_fps` (--full) = BASELINE.json's metric: ENCODED fps of the whole encoder with the HIP path bound in (oracle/_ref/hooked/
 SvtHevcEncApp_hip = the drop-in libSvtHevcEnc.so.1 + the reference's sample application) on BASELINE configs[2]'s command line, WITH THE CLOSED
 LOOP ON THE DEVICE (CLOSED_LOOP_ENV below: SVT_HOOK_MD=pb - motion estimation and open-loop intra search of every picture, mode decision, merge / skip
 decisions and encode pass of every open-loop P / B picture, one call per picture; `encoder_fps.coverage` says how many pictures that was), the
@@ -98,7 +107,7 @@ def cpu_baseline_reference(cfg, unique=8, frames=48):
         S.write_clip(yuv, "motion", w, h, unique, 7)
         t0 = time.perf_counter()
         E.run_app(S.REF_APP, yuv, w, h, frames, args + ["-asm", "1"], os.path.join(td, "o.265"), env={"SVT_REF_FRONT_TIME": rep},
-                  nb=unique)
+                  nb=min(unique, frames))
         wall = time.perf_counter() - t0
         r = json.load(open(rep))
     nl = S.lcu_count(w, h)
@@ -247,7 +256,7 @@ def encoded_fps_leg(enc_cfg, steps, rank, local_rank, world, sync):
         ref_md5 = ""
         if rank == 0:
             try:
-                ref = E.run_app(S.REF_APP, yuv, w, h, frames, args, os.path.join(td, "ref.265"), nb=unique)
+                ref = E.run_app(S.REF_APP, yuv, w, h, frames, args, os.path.join(td, "ref.265"), nb=min(unique, frames))
                 out["reference"], ref_md5 = ref, ref["md5"]
             except Exception as e:
                 out["reference"] = {"error": str(e)[-300:]}
@@ -274,7 +283,7 @@ def encoded_fps_leg(enc_cfg, steps, rank, local_rank, world, sync):
         with GpuBusy(local_rank) as gb:
             for k in range(RUNS if world == 1 else 1):
                 try:
-                    hips.append(E.run_app(E.HIP_APP, yuv, w, h, frames, hargs, os.path.join(td, "hip.265"), env=dict(env, **({"SVT_HOOK_REPORT": rp} if k == 0 else {})), nb=unique,
+                    hips.append(E.run_app(E.HIP_APP, yuv, w, h, frames, hargs, os.path.join(td, "hip.265"), env=dict(env, **({"SVT_HOOK_REPORT": rp} if k == 0 else {})), nb=min(unique, frames),
                                           timeout=240))
                 except Exception as e:
                     aborted.append(str(e)[-1200:])
@@ -288,7 +297,7 @@ def encoded_fps_leg(enc_cfg, steps, rank, local_rank, world, sync):
         if rank == 0 and world == 1:
             try:
                 if lp < ncpu:
-                    r2 = _median_run([E.run_app(S.REF_APP, yuv, w, h, frames, hargs, os.path.join(td, "ref_lp.265"), nb=unique) for _ in range(RUNS)])
+                    r2 = _median_run([E.run_app(S.REF_APP, yuv, w, h, frames, hargs, os.path.join(td, "ref_lp.265"), nb=min(unique, frames)) for _ in range(RUNS)])
                     out["reference_same_threads"] = dict(r2, args="-lp %d" % lp, same_bitstream_as_default_threading=r2["md5"] == ref_md5)
                 # the other configurations of the same encode, one run each
                 side = {}
@@ -297,7 +306,7 @@ def encoded_fps_leg(enc_cfg, steps, rank, local_rank, world, sync):
                                     ("closed_loop_i_pictures_on_device", dict(env, SVT_HOOK_MD="1"), hargs),
                                     ("closed_loop_default_threads", env, list(args))):
                     try:
-                        r = E.run_app(E.HIP_APP, yuv, w, h, frames, a2, os.path.join(td, "side.265"), env=e2, nb=unique)
+                        r = E.run_app(E.HIP_APP, yuv, w, h, frames, a2, os.path.join(td, "side.265"), env=e2, nb=min(unique, frames))
                         side[tag] = {"fps": r["fps"], "bitstream_identical": r["md5"] == ref_md5}
                     except Exception as e:
                         side[tag] = {"error": str(e)[-300:]}
@@ -545,6 +554,23 @@ def recon_exchange_leg(lib, root, rank, world, dev, reps=10, limit_s=120.0):
     return out
 
 
+def dump_front_half(out_dir, sets, records, per_set, me_b, ois_b, sample=1024, seed=0):
+    """--dump-outputs: what the last timed step handed back to the host (the compact records in the pinned arrays of every buffer set, NL batches),
+    as a fixed, seeded sample of `sample` LCUs out of `records`: their ME and OIS record bytes as float32 rows, and which LCUs they are"""
+    idx = np.sort(np.random.default_rng(seed).choice(records, size=min(sample, records), replace=False))
+    me, ois = np.empty((len(idx), me_b), np.float32), np.empty((len(idx), ois_b), np.float32)
+    for k, L in enumerate(sets):
+        h_me = np.frombuffer((C.c_uint8 * (per_set * me_b)).from_address(L["h_me"].value), np.uint8).reshape(per_set, me_b)
+        h_ois = np.frombuffer((C.c_uint8 * (per_set * ois_b)).from_address(L["h_ois"].value), np.uint8).reshape(per_set, ois_b)
+        sel = (idx >= k * per_set) & (idx < (k + 1) * per_set)
+        me[sel] = h_me[idx[sel] - k * per_set]
+        ois[sel] = h_ois[idx[sel] - k * per_set]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "front_half_me_records.npy"), me)
+    np.save(os.path.join(out_dir, "front_half_ois_records.npy"), ois)
+    np.save(os.path.join(out_dir, "front_half_sample_index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -558,18 +584,21 @@ def main():
     ap.add_argument("--no-encode-pass", action="store_true")
     ap.add_argument("--no-pmc", action="store_true")
     ap.add_argument("--inner", action="store_true", help="(internal) counter pass: GPU loop only, prints the batch count")
+    ap.add_argument("--full", action="store_true", help="everything beside the front-half loop: the whole-encoder figure and its md5 gate, CPU baselines, "
+                                                        "HBM-resident loop, rooflines and counter passes, encode pass, exchange legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write a seeded sample of the last timed step's records as DIR/<name>.npy")
     a = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     assert world == a.gpus, "launch with torch.distributed.run --nproc-per-node %d" % a.gpus
-    # ---- the headline first: md5-gated encoded fps of the whole encoder with the HIP path bound in.  The encoder is a child process with two dozen streams of its
+    # ---- --full: md5-gated encoded fps of the whole encoder with the HIP path bound in.  The encoder is a child process with two dozen streams of its
     # own; measured BEFORE this process opens the device, so that the two do not share the part's hardware queues (the same leg after the loops below: 87-97 fps where the
     # stand-alone sweeps of the same binary read 103-117, profiles/r05_ah_bench_encoder_leg_last.json).  N > 1: the ranks meet through files (FileSync), not through the process
     # group - the nccl backend opens the device.
     enc = None
-    if not a.inner and not a.no_encoder_fps:
+    if a.full and not a.inner and not a.no_encoder_fps:
         sync = FileSync(rank, world) if world > 1 else None
         enc = encoded_fps_leg(CONFIGS[a.config]["enc"], a.steps, rank, local_rank, world, sync)
         if sync:
@@ -705,10 +734,12 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(nsteps, copies):
+    def timed(nsteps, copies, stamps=True):
+        """stamps: arm the library's per-kernel event stamps (what the rooflines read) for the pass"""
         barrier()
-        for L in lanes:
-            lib.svt_amd_timer_begin(L["ctx"])
+        if stamps:
+            for L in lanes:
+                lib.svt_amd_timer_begin(L["ctx"])
         t0 = time.perf_counter()
         for s in range(nsteps):
             for k in range(NL):  # NL batches per step, one per buffer set
@@ -722,6 +753,8 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         kt = {}
+        if not stamps:
+            return dt, kt
         for cls in (b"me_search", b"prep", b"ois"):
             tot, n = 0.0, 0
             for L in lanes:
@@ -739,7 +772,12 @@ def main():
         for k in range(NL):
             step(k)
     sync_all()
-    dt, kt = timed(a.steps, True)
+    dt, kt = timed(a.steps, True, stamps=a.inner)
+    if a.dump_outputs and rank == 0 and not a.inner:
+        dump_front_half(a.dump_outputs, sets, NL * B * nlcu, B * nlcu, me_b, ois_b)
+    if a.full:
+        # the per-kernel stamps the rooflines read: a pass of their own, so that `value` is timed exactly as in a plain run
+        dt_stamped, kt = timed(a.steps, True)
 
     if trace and rank == 0:
         print("host seconds per library call over %d batches: %s" % (counts["batches"], {k: round(v, 4) for k, v in sorted(acc.items(), key=lambda kv: -kv[1])}),
@@ -747,14 +785,23 @@ def main():
     if a.inner:
         if rank == 0:
             print(json.dumps({"me_batches": counts["batches"], "pictures_per_batch": B}), flush=True)
-    else:
+    elif a.full:
         dt_res, kt_res = timed(max(2, a.steps // 2), False)
         res_steps = max(2, a.steps // 2)
 
-    xchg = recon_exchange_leg(lib, root, rank, world, dev) if (world > 1 and not a.inner) else None
+    xchg = recon_exchange_leg(lib, root, rank, world, dev) if (world > 1 and a.full and not a.inner) else None
 
-    if rank == 0 and not a.inner:
-        fps = world * NL * B * a.steps / dt
+    fps = world * NL * B * a.steps / dt
+    what = ("upload + picture preparation + open-loop motion estimation of %d LCUs against %d list(s) (HME L0 %dx%d + L1, full-pel %dx%d 85-PU search, sub-pel, "
+            "bi-prediction) + open-loop intra search + result download, through the host boundary (PCIe inside the timed region), %d pictures per launch, %d lanes" %
+            (nlcu, nlists, params.hme_l0_total_w, params.hme_l0_total_h, params.search_area_width, params.search_area_height, B, NL))
+    line = {"metric": "front-half fps, %s: pictures per second through %s" % (cfg["name"], what),
+            "value": round(fps, 2), "unit": "fps", "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": "weak", "dtype": "u8", "data": "synthetic", "pictures_per_step_per_gpu": NL * B}
+    if rank == 0 and not a.inner and not a.full:
+        print(json.dumps(line), flush=True)
+
+    if rank == 0 and not a.inner and a.full:
         me_ms, me_n = kt["me_search"]
         # algorithmic HBM bytes of one ME batch: per picture the source + `nlists` references, each
         # full + 1/4 + 1/16 planes (1.3125 bytes/pel), plus the per-LCU result records
@@ -770,12 +817,12 @@ def main():
         prep_bytes = B * (W * H + 4 * (W + 136) * (H + 136) + (W // 2 + 64) * (H // 2 + 64) + (W // 4 + 32) * (H // 4 + 32))
         ois_bytes = B * (W * H + nlcu * 6208)
         value = enc["value"] if enc and "value" in enc else None
-        res = {
+        res = dict(line)
+        res["encoded_fps"] = {
             "metric": "encoded fps, %s, bitstream md5-identical to the unmodified reference (BASELINE.json metric; whole encoder with the "
                       "HIP path bound in, application's Average Speed)" % cfg["name"],
-            "value": value if value is not None else 0.0, "unit": "fps", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(8e3 / value, 4) if value else None, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "vs_cpu_baseline": None,
-            "dtype": "u8", "data": "synthetic",
+            "value": value if value is not None else 0.0, "unit": "fps", "steps": a.steps,
+            "ms_per_step": round(8e3 / value, 4) if value else None, "higher_is_better": True, "vs_baseline": None, "vs_cpu_baseline": None,
             "unstable": bool(enc.get("unstable")) if enc else None,   # an encode of the measured configuration aborted (watchdog) or timed out: `value` is 0 then, never a retry's
             "fps_runs": (enc.get("hip") or {}).get("fps_runs") if enc else None,
             "peak_rss_mb_of_this_process": round(__import__("resource").getrusage(__import__("resource").RUSAGE_SELF).ru_maxrss / 1024.0, 1),
@@ -793,13 +840,16 @@ def main():
                        "on_host_in_this_run": ("EncDec of the I pictures and of the base-layer P / B pictures (closed-loop intra + branch-and-depth-pillar LCUs: the reference's "
                                                "code, DESIGN 7) with their deblocking + SAO, entropy coding, picture management") if enc else None,
                        "parallelism": "one encoder per rank on its own GPU, no data-path collective" if world > 1 else "1 GPU"},
+        }
+        res.update({
             "encoder_fps": enc,
             "front_half": {"what": "upload + picture preparation + open-loop motion estimation of %d LCUs against %d list(s) (HME L0 %dx%d + L1, "
                                    "full-pel %dx%d 85-PU search, sub-pel, bi-prediction) + open-loop intra search + result download, through the "
                                    "host boundary (PCIe inside the timed region), %d pictures per launch, %d lanes" %
                                    (nlcu, nlists, params.hme_l0_total_w, params.hme_l0_total_h, params.search_area_width,
                                     params.search_area_height, B, NL),
-                           "fps": round(fps, 2), "steps": a.steps, "ms_per_step": round(dt / a.steps * 1e3, 4), "timed_region_s": round(dt, 3),
+                           "fps": round(fps, 2), "steps": a.steps, "ms_per_step": round(dt / a.steps * 1e3, 4),
+                           "ms_per_step_with_kernel_stamps": round(dt_stamped / a.steps * 1e3, 4), "timed_region_s": round(dt, 3),
                            "pictures_per_step_per_gpu": NL * B, "hbm_resident_fps": round(world * NL * B * res_steps / dt_res, 2),
                            "h2d_bytes_per_picture": W * H, "d2h_bytes_per_picture": nlcu * (me_b + ois_b)},
             "roofline": {"bound": "hbm", "kernel": "k_me<0> (hme) + k_me<1> (search): one ME batch = %d dispatches (2 per list)" % (2 * nlists),
@@ -815,7 +865,7 @@ def main():
                              "k_ois_picture": {"avg_ms": round(kt["ois"][0], 4), "launches": kt["ois"][1], "algorithmic_bytes": int(ois_bytes),
                                                "GBps": round(ois_bytes / (kt["ois"][0] * 1e-3) / 1e9, 1) if kt["ois"][0] > 0 else None}},
                          "avg_launch_ms_hbm_resident_loop": round(kt_res["me_search"][0], 4)},
-        }
+        })
         if xchg is not None:
             res["recon_exchange"] = xchg
         if world == 1 and not a.no_pmc:
@@ -833,7 +883,7 @@ def main():
             except Exception as e:  # the reference build is absent: say so, do not substitute
                 res["cpu_baseline"] = {"error": str(e)[-300:]}
         if res.get("cpu_baseline", {}).get("value") and value:
-            res["vs_cpu_baseline"] = round(value / res["cpu_baseline"]["value"], 3)
+            res["encoded_fps"]["vs_cpu_baseline"] = round(value / res["cpu_baseline"]["value"], 3)
         if world == 1 and not a.no_encode_pass and os.path.exists(S.REF_APP):
             try:
                 res["roofline_md"] = md_kernel_leg(W, H)

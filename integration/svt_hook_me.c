@@ -4,7 +4,7 @@
  *
  * This is the code a maintainer adds to the reference: it is
  * compiled against the reference headers and linked, with the reference's own
- * objects and -Wl,--wrap=MotionEstimateLcu, into integration/_build/libsvthip.so /
+ * objects and -Wl,--wrap=MotionEstimateLcu, into oracle/_ref/hooked/libSvtHevcEnc.so.1 /
  * SvtHevcEncApp_hip.  Every call the reference's MotionEstimationKernel makes to
  * MotionEstimateLcu (Codec/EbMotionEstimationProcess.c:780) is answered from the
  * result of ONE svt_amd_me_picture() call per picture on the MI355X; the

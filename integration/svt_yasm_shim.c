@@ -3,7 +3,7 @@
  * /root/reference links on a machine without yasm / nasm (this image).  A maintainer with yasm
  * drops this file and assembles the reference's own .asm files instead.
  *
- * Compiled into integration/_build/ (the drop-in library) and, by oracle/Makefile, into
+ * Compiled into oracle/_ref/hooked/ (the drop-in library) and, by oracle/Makefile, into
  * oracle/_ref/ (the reference build used as parity checker and CPU baseline).  It contains no
  * reference source; every symbol forwards to the reference's own C_DEFAULT peer.
  *

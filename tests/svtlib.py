@@ -16,6 +16,10 @@ PRODUCT_SO = os.path.join(ROOT, "svt-hevc_amd", "libsvt_hevc_amd.so")
 ORACLE_SO = os.path.join(ROOT, "oracle", "liboracle.so")
 REF_SO = os.path.join(ROOT, "oracle", "_ref", "libsvtref.so")
 REF_APP = os.path.join(ROOT, "oracle", "_ref", "SvtHevcEncApp_ref")
+# the reference encoder with the HIP library bound in (integration/Makefile builds it next to the reference binaries)
+HOOKED_DIR = os.path.join(ROOT, "oracle", "_ref", "hooked")
+HIP_APP = os.path.join(HOOKED_DIR, "SvtHevcEncApp_hip")
+DROP_IN = os.path.join(HOOKED_DIR, "libSvtHevcEnc.so.1")
 GOLDEN_DIR = os.path.join(ROOT, "tests", "golden")
 
 ME_PU_COUNT = 85

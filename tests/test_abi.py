@@ -69,11 +69,11 @@ def test_no_gpu_means_loud_failure():
 EB_API = {"EbInitHandle", "EbH265EncSetParameter", "EbInitEncoder", "EbH265EncStreamHeader", "EbH265EncReleaseStreamHeader", "EbH265EncEosNal",
           "EbH265EncReleaseEosNal", "EbH265EncSendPicture", "EbH265GetPacket", "EbH265ReleaseOutBuffer", "EbH265GetRecon", "EbDeinitEncoder",
           "EbDeinitHandle"}
-DROP_IN = os.path.join(S.ROOT, "integration", "_build", "libSvtHevcEnc.so.1")
+DROP_IN = S.DROP_IN
 
 
 def test_drop_in_library_is_the_reference_outer_abi():
-    """integration/_build/libSvtHevcEnc.so.1 (reference objects + the bindings) is what ffmpeg / gstreamer / the sample application
+    """oracle/_ref/hooked/libSvtHevcEnc.so.1 (reference objects + the bindings) is what ffmpeg / gstreamer / the sample application
     load in place of the reference's library: SONAME libSvtHevcEnc.so.1, version node SVT_HEVC_1, exactly the 13 Eb* entry points
     (SURVEY 8b outer ABI).  The library is prebuilt by __graft_entry__.build() (needs /root/reference), so it is present wherever
     the tests run."""
@@ -110,7 +110,7 @@ print("OUTER_ABI_OK", any(cfg.raw))
     assert "OUTER_ABI_OK True" in r.stdout, r.stdout[-500:] + r.stderr[-1500:]
 
 
-HIP_APP = os.path.join(S.ROOT, "integration", "_build", "SvtHevcEncApp_hip")
+HIP_APP = S.HIP_APP
 
 
 def _run_hooked(tmp_path, env):

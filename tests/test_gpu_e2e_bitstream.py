@@ -13,7 +13,7 @@ import svtlib as S
 
 pytestmark = pytest.mark.gpu
 
-HIP_APP = os.path.join(S.ROOT, "integration", "_build", "SvtHevcEncApp_hip")
+HIP_APP = S.HIP_APP
 
 CASES = [
     ("motion", 640, 384, 8, ["-encMode", "9", "-pred-struct", "0"]),
@@ -64,7 +64,7 @@ def _encode(app, yuv, w, h, n, args, out):
 @pytest.mark.parametrize("kind,w,h,n,args", CASES)
 def test_bitstream_identical_with_gpu_me(tmp_path, kind, w, h, n, args):
     assert os.path.exists(HIP_APP) and os.path.exists(S.REF_APP), \
-        "integration/_build and oracle/_ref must be prebuilt (python __graft_entry__.py build, needs /root/reference)"
+        "oracle/_ref/hooked and oracle/_ref must be prebuilt (python __graft_entry__.py build, needs the reference sources)"
     yuv = str(tmp_path / "clip.yuv")
     if kind.endswith("10c"):
         S.write_clip10_compressed(yuv, kind[:-3], w, h, n, 7)

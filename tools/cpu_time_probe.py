@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import svtlib as S
 S.write_clip("/tmp/c.yuv", "motion", 3840, 2160, 16, 7)
 args = "-i /tmp/c.yuv -w 3840 -h 2160 -n 96 -nb 16 -encMode 7 -pred-struct 2 -hierarchical-levels 2 -sao 1 -fps 60 -q 32 -asm 1 -b /tmp/o.265".split()
-for app in ("oracle/_ref/SvtHevcEncApp_ref", "integration/_build/SvtHevcEncApp_hip"):
+for app in ("oracle/_ref/SvtHevcEncApp_ref", "oracle/_ref/hooked/SvtHevcEncApp_hip"):
     for extra in ({}, {"SVT_HOOK_ENCODEPASS": "1"}) if "hip" in app else ({},):
         t0 = time.time()
         p = subprocess.Popen([os.path.join(ROOT, app)] + args, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, env=dict(os.environ, **extra))

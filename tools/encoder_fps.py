@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Whole-encoder fps of the hooked encoder (integration/_build/SvtHevcEncApp_hip: reference host control + the HIP
+"""Whole-encoder fps of the hooked encoder (oracle/_ref/hooked/SvtHevcEncApp_hip: reference host control + the HIP
 hot path behind the bindings) next to the unmodified reference (oracle/_ref/SvtHevcEncApp_ref, -asm 1 = its AVX2 path)
 on the same synthetic clip, md5-gated: the BASELINE.json metric ("encoded fps ... bit-exact").
 
@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import svtlib as S  # noqa: E402
 
-HIP_APP = os.path.join(ROOT, "integration", "_build", "SvtHevcEncApp_hip")
+HIP_APP = S.HIP_APP
 
 CONFIGS = {
     # BASELINE.md section 2 command lines

@@ -17,7 +17,7 @@ import svtlib as S  # noqa: E402
 def main():
     kind, w, h, n = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
     args = sys.argv[5:]
-    app = os.path.join(ROOT, "integration", "_build", "SvtHevcEncApp_hip")
+    app = os.path.join(ROOT, "oracle", "_ref", "hooked", "SvtHevcEncApp_hip")
     with tempfile.TemporaryDirectory() as td:
         yuv = os.path.join(td, "clip.yuv")
         if kind.endswith("10c"):

@@ -1,6 +1,6 @@
 cd ${GRAFT_REPO_ROOT:-.}
 O=gpurun_out/r04_final; mkdir -p $O
-timeout 900 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json
 bash tools/profile_bench.sh r04_final_prof > $O/profile_bench.log 2>&1
 cp gpurun_out/r04_final_prof/kernel_stats.txt $O/kernel_stats.txt 2>/dev/null

@@ -2,7 +2,7 @@
 cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
 O=gpurun_out/r06_final; mkdir -p $O
-timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err
+timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err
 tail -c 300 $O/bench.err
 # rocprofv3 --kernel-trace --stats of the encoder in the measured configuration (the library's defaults), 160 pictures, -lp 32
 python - <<PY
@@ -11,7 +11,7 @@ sys.path.insert(0, "tests")
 import svtlib as S
 S.write_clip("/tmp/md_clip.yuv", "motion", 3840, 2160, 16, 7)
 PY
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tr -o t -- integration/_build/SvtHevcEncApp_hip -i /tmp/md_clip.yuv -w 3840 -h 2160 -n 160 -nb 16 -b /tmp/md.265 -encMode 7 -pred-struct 2 -hierarchical-levels 2 -sao 1 -fps 60 -q 32 -asm 1 -lp 32 > $O/app.txt 2> $O/prof.err < /dev/null
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/tr -o t -- oracle/_ref/hooked/SvtHevcEncApp_hip -i /tmp/md_clip.yuv -w 3840 -h 2160 -n 160 -nb 16 -b /tmp/md.265 -encMode 7 -pred-struct 2 -hierarchical-levels 2 -sao 1 -fps 60 -q 32 -asm 1 -lp 32 > $O/app.txt 2> $O/prof.err < /dev/null
 grep "Average Speed" $O/app.txt
 python - "$O" <<'PY'
 import csv, glob, sys, collections

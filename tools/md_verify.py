@@ -5,7 +5,7 @@ import hashlib, os, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import svtlib as S
-HIP_APP = os.path.join(ROOT, "integration", "_build", "SvtHevcEncApp_hip")
+HIP_APP = os.path.join(ROOT, "oracle", "_ref", "hooked", "SvtHevcEncApp_hip")
 kind, w, h, n, how = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
 args = sys.argv[6:]
 with tempfile.TemporaryDirectory() as td:

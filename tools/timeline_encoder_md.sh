@@ -13,7 +13,7 @@ import svtlib as S
 S.write_clip("/tmp/md_clip.yuv", "motion", 3840, 2160, 16, 7)
 PY
 if [ "$TL_MD" = "off" ]; then MDENV="SVT_HOOK_NOTHING=1"; else MDENV="SVT_HOOK_MD=${TL_MD:-1}"; fi   # TL_MD=off: front half only (the host's own EncDec on the time line)
-env $MDENV SVT_HOOK_REPORT=$O/report.txt SVT_HOOK_TIMELINE=$O/timeline.txt "$@" timeout 200 integration/_build/SvtHevcEncApp_hip -i /tmp/md_clip.yuv -w 3840 -h 2160 -n $N -nb 16 -b /tmp/md.265 -encMode 7 -pred-struct 2 -hierarchical-levels 2 -sao 1 -fps 60 -q 32 -asm 1 -lp $LP > $O/app.txt 2> $O/app.err < /dev/null
+env $MDENV SVT_HOOK_REPORT=$O/report.txt SVT_HOOK_TIMELINE=$O/timeline.txt "$@" timeout 200 oracle/_ref/hooked/SvtHevcEncApp_hip -i /tmp/md_clip.yuv -w 3840 -h 2160 -n $N -nb 16 -b /tmp/md.265 -encMode 7 -pred-struct 2 -hierarchical-levels 2 -sao 1 -fps 60 -q 32 -asm 1 -lp $LP > $O/app.txt 2> $O/app.err < /dev/null
 grep "Average Speed" $O/app.txt
 python - "$O" <<'PY'
 import sys
