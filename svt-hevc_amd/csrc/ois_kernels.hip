@@ -5,30 +5,41 @@
  *   UpdateNeighborSamplesArrayOpenLoop -> IntraPredictionOpenLoop -> NxMSadKernel -> candidate injection
  * (EbMotionEstimation.c:5053-5320, EbIntraPrediction.c:5222-5421) by:
  *   1. the source window rows/cols -1..95 of the LCU in LDS (covers the 2N left / 2N top neighbours of every CU),
- *   2. the reference-sample array of all 84 CUs at once (out-of-picture samples = 128, no smoothing),
- *   3. a task list (CU, mode): one wavefront per task, lanes over the CU's samples, prediction evaluated per
- *      sample in closed form (planar / DC+edge / V,H+edge / angular with on-the-fly projection), SAD by
- *      wave reduction,
- *   4. per-CU decision threads reproducing the injection tables; the one serial dependency of the reference
+ *      and a transposed copy of the LCU's 64x64 samples,
+ *   2. one wavefront per CU at a time (CU 1 + wave, 5 + wave, ...: every wave gets one 32x32 and four 16x16 CUs),
+ *      an instance of the search per CU size: the CU's reference-sample array (out-of-picture samples = 128, no
+ *      smoothing), its DC value and the main references of both angular classes, then a loop over the CU's modes
+ *      (P/B: DC SAD -> GetOisPoint -> stage-1 modes, all inside the wave, no barrier); each mode is predicted four
+ *      samples a lane: an angular mode is a row routine on packed bytes over the HEVC main reference (a negative
+ *      angle adds its projected side samples), horizontal-class modes run the same routine against the transposed
+ *      source; SAD by v_sad_u8 and wave reduction,
+ *   3. per-CU decision threads reproducing the injection tables; the one serial dependency of the reference
  *      (bestMode / stage1SadArray surviving from CU to CU when no mode beats 32*32*255) is detected and, only
  *      then, replayed serially by one thread.
  * Results use the SvtAmdOisLcuResult convention (include/svt_hevc_amd.h): written bitfields flagged.
  */
 #include "svt_amd_internal.h"
 
-#define WIN_W 100 /* row pitch in bytes: columns -4 .. 95 of the LCU (starts on a dword of the plane) */
-#define WIN_X0 4  /* window column of LCU column 0 */
+#define WIN_W 112 /* row pitch in bytes: columns -16 .. 95 of the LCU (seven 16-byte loads per row) */
+#define WIN_X0 16 /* window column of LCU column 0 */
 #define WIN_H 97
-#define MAXK 35
+#define EXT_OFF 36 /* ext[EXT_OFF + k] = main[k], k = -N .. 2N+4 (the dword reads of a row reach 3 below the lowest index used) */
+#define EXT_W 108
 
-struct OisShared {
-    uint8_t win[WIN_H * WIN_W];         /* win[(y+1)*WIN_W + x + WIN_X0] = source sample (x,y) relative to the LCU */
-    uint8_t refs[4 * 129 + 16 * 65 + 64 * 33 + 4]; /* per CU: left[0..2N-1] top-to-bottom, top-left, top[0..2N-1] */
-    uint32_t sad[85][MAXK];
-    uint32_t out_cand[85][SVT_AMD_OIS_MAX_CAND];
+/* K = SAD columns per CU: 10 (intra: 7 modes; P/B: 9 stage-1 modes + DC in slot 9), 35 with ois_kernel_level */
+template <int K> struct OisShared {
+    union {
+        struct {
+            alignas(16) uint8_t win[WIN_H * WIN_W]; /* win[(y+1)*WIN_W + x + WIN_X0] = source sample (x,y) relative to the LCU */
+            uint8_t wint[64 * 64];      /* wint[x*64 + y] = source sample (x,y), 0 <= x,y < 64 */
+        } src;
+        uint32_t out_cand[85][SVT_AMD_OIS_MAX_CAND]; /* decisions: written once the SADs are complete */
+    } u;
+    uint8_t refs[4][132];   /* per wave, its current CU: left[0..2N-1] top-to-bottom, top-left, top[0..2N-1] */
+    uint8_t ext[4][2][EXT_W]; /* per wave, its current CU: the extended main reference of the vertical / horizontal class */
+    uint32_t sad[85][K];
     uint8_t out_total[88];
-    uint8_t dc[88];
-    uint8_t nmodes[88];                 /* stage-1 modes to test per CU (P path) */
+    uint8_t nmodes[88];     /* stage-1 modes to test per CU (P path) */
     int stale;
 };
 
@@ -41,15 +52,12 @@ __device__ __forceinline__ void cu_geom(int cu, int &x, int &y, int &N, int &lg)
     else
         N = 8, lg = 3, x = ((cu - 21) & 7) * 8, y = ((cu - 21) >> 3) * 8;
 }
-__device__ __forceinline__ int ref_base(int cu)
-{
-    return cu < 5 ? (cu - 1) * 129 : cu < 21 ? 516 + (cu - 5) * 65 : 516 + 1040 + (cu - 21) * 33;
-}
 
 __device__ __constant__ int8_t c_ang[9] = {0, 2, 5, 9, 13, 17, 21, 26, 32};
 __device__ __constant__ int16_t c_inv[9] = {0, 4096, 1638, 910, 630, 482, 390, 315, 256};
 __device__ __constant__ uint8_t c_islice[7] = {0, 1, 10, 26, 2, 18, 34};
 __device__ __constant__ uint8_t c_stage1[9] = {10, 26, 2, 18, 34, 6, 14, 22, 30};
+__device__ __constant__ uint8_t c_all35[35] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34};
 __device__ __constant__ uint8_t c_inject[9][9] = {
     {10, 1, 0, 9, 11, 8, 12, 7, 13}, {26, 1, 0, 25, 27, 24, 28, 23, 29}, {2, 1, 0, 3, 4, 5, 7, 8, 9},
     {18, 1, 0, 17, 19, 16, 20, 15, 21}, {34, 1, 0, 33, 32, 29, 31, 27, 28}, {6, 1, 0, 7, 5, 4, 8, 3, 9},
@@ -60,63 +68,25 @@ __device__ __constant__ int16_t c_ois_th[3][6][4] = {
     {{-150, 0, 150, 200}, {-150, 0, 150, 200}, {-125, 0, 100, 150}, {-50, 50, 200, 300}, {-50, 50, 200, 300}, {-50, 50, 200, 300}},
     {{-400, -300, -200, 0}, {-400, -300, -200, 0}, {-400, -300, -200, 0}, {-400, -300, -200, 0}, {-400, -300, -200, 0}, {-400, -300, -200, 0}}};
 
-/* HEVC intra prediction of sample (x,y), unfiltered references, luma edge filters for N < 32.
- * r: left[0..2N-1], r[2N] = top-left, r[2N+1+j] = top[j]. */
-__device__ __forceinline__ int predict_sample(int mode, int N, int lg, const uint8_t *r, int x, int y, int dc)
+/* planar / DC (with its N < 32 edge filter) of sample (x,y); r: left[0..2N-1], r[2N] = top-left, r[2N+1+j] = top[j] */
+__device__ __forceinline__ int predict_planar_dc(int mode, int N, int lg, const uint8_t *r, int x, int y, int dc)
 {
     const uint8_t *left = r, *top = r + 2 * N + 1;
-    const int tl = r[2 * N];
     if (mode == 0)
         return ((N - 1 - x) * left[y] + (x + 1) * top[N] + (N - 1 - y) * top[x] + (y + 1) * left[N] + N) >> (lg + 1);
-    if (mode == 1) {
-        if (N < 32) {
-            if (x == 0 && y == 0)
-                return (left[0] + top[0] + 2 * dc + 2) >> 2;
-            if (y == 0)
-                return (top[x] + 3 * dc + 2) >> 2;
-            if (x == 0)
-                return (left[y] + 3 * dc + 2) >> 2;
-        }
-        return dc;
+    if (N < 32) {
+        if (x == 0 && y == 0)
+            return (left[0] + top[0] + 2 * dc + 2) >> 2;
+        if (y == 0)
+            return (top[x] + 3 * dc + 2) >> 2;
+        if (x == 0)
+            return (left[y] + 3 * dc + 2) >> 2;
     }
-    if (mode == 26) {
-        if (N < 32 && x == 0)
-            return min(255, max(0, top[0] + ((left[y] - tl) >> 1)));
-        return top[x];
-    }
-    if (mode == 10) {
-        if (N < 32 && y == 0)
-            return min(255, max(0, left[0] + ((top[x] - tl) >> 1)));
-        return left[y];
-    }
-    /* angular: main / side reference by direction */
-    const bool vert = mode >= 18;
-    const int d = vert ? mode - 26 : 10 - mode;      /* -8..8 */
-    const int a = d < 0 ? -c_ang[-d] : c_ang[d];
-    const int u = vert ? x : y, v = vert ? y : x;     /* u along the main reference, v across */
-    const uint8_t *mainr = vert ? top : left, *side = vert ? left : top;
-    const int pos = (v + 1) * a, i = pos >> 5, f = pos & 31;
-    int idx = u + i + 1;                               /* main[idx]; main[0] = top-left, main[k] = mainr[k-1] */
-    int s0, s1;
-    if (idx > 0)
-        s0 = mainr[idx - 1];
-    else if (idx == 0)
-        s0 = tl;
-    else
-        s0 = side[((-idx * c_inv[-d] + 128) >> 8) - 1];
-    idx++;
-    if (idx > 0)
-        s1 = mainr[idx - 1];
-    else if (idx == 0)
-        s1 = tl;
-    else
-        s1 = side[((-idx * c_inv[-d] + 128) >> 8) - 1];
-    return ((32 - f) * s0 + f * s1 + 16) >> 5;
+    return dc;
 }
 
 /* wave sum on the DPP path (quad_perm [1,0,3,2] / [2,3,0,1], row_half_mirror, row_mirror: after the quad steps a mirror step completes the next power of two) and
- * v_readlane across the four rows: __shfl_xor compiles to ds_bpermute_b32, an LDS-crossbar round trip per step, and every (coding unit, mode) task of this kernel - a whole
- * wave for as few as 64 samples - ends in one.  Wave-uniform result. */
+ * v_readlane across the four rows: __shfl_xor compiles to ds_bpermute_b32, an LDS-crossbar round trip per step.  Wave-uniform result. */
 #define OIS_DPP(v, ctrl) ((uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), ctrl, 0xF, 0xF, true))
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
@@ -128,46 +98,183 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
            (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
 }
 
-/* SAD of CU `cu` predicted with `mode`; executed by one whole wavefront */
-__device__ __forceinline__ uint32_t task_sad(const OisShared &S, int cu, int mode, int lane)
+/* LDS written by some lanes of a wave and read by others of the same wave */
+__device__ __forceinline__ void wave_lds_sync()
 {
-    int cx, cy, N, lg;
-    cu_geom(cu, cx, cy, N, lg);
-    const uint8_t *r = S.refs + ref_base(cu);
-    const int dc = S.dc[cu];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+/* one CU as seen by the wave that searches it */
+template <int LG> struct CuView {
+    int cx, cy;
+    const uint8_t *r; /* reference samples (OisShared::refs[wave]) */
+    uint8_t *ext;     /* OisShared::ext[wave]: the main reference of the vertical class, then of the horizontal class */
+    int dc;
+};
+
+/* SAD of planar (mode 0) or DC (mode 1): four samples a lane, per-sample prediction only where it is not a constant */
+template <int K, int LG>
+__device__ __forceinline__ uint32_t sad_planar_dc(const OisShared<K> &S, const CuView<LG> &c, int mode, int lane)
+{
+    constexpr int N = 1 << LG, NQ = (N * N) >> 2, QS = LG - 2; /* dwords of the CU, log2 dwords per row */
+    const uint32_t dc4 = (uint32_t)c.dc * 0x01010101u;
     uint32_t acc = 0;
-    for (int p = lane; p < N * N; p += 64) {
-        const int y = p >> lg, x = p & (N - 1);
-        const int pr = predict_sample(mode, N, lg, r, x, y, dc);
-        acc += (uint32_t)abs((int)S.win[(cy + y + 1) * WIN_W + cx + x + WIN_X0] - pr);
+#pragma unroll 1
+    for (int q0 = 0; q0 < NQ; q0 += 64) {
+        const int q = q0 + lane;
+        if (NQ >= 64 || q < NQ) {
+            const int y = q >> QS, x4 = (q & ((1 << QS) - 1)) << 2;
+            const uint32_t sv = *(const uint32_t *)&S.u.src.win[(c.cy + y + 1) * WIN_W + c.cx + x4 + WIN_X0];
+            uint32_t pv = dc4;
+            if (mode == 0 || (N < 32 && (y == 0 || x4 == 0))) {
+                pv = 0;
+#pragma unroll
+                for (int i = 0; i < 4; i++)
+                    pv |= (uint32_t)predict_planar_dc(mode, N, LG, c.r, x4 + i, y, c.dc) << (8 * i);
+            }
+            acc = __builtin_amdgcn_sad_u8(sv, pv, acc);
+        }
     }
     return wave_sum(acc);
 }
 
-/* DC prediction is a constant except for the filtered first row / column (N < 32): SAD four samples per lane-op
- * against the replicated DC value; the DC SAD of every CU is the one task every P/B picture always runs */
-__device__ __forceinline__ uint32_t task_sad_dc(const OisShared &S, int cu, int lane)
+/* SAD of an angular mode (2..34, 10 and 26 included), four samples a lane.
+ * Vertical class (18..34): row y of the CU is, for every x, ((32-f)*main[x+i+1] + f*main[x+i+2] + 16) >> 5 with pos = (y+1)*angle, i = pos >> 5,
+ * f = pos & 31 constant along the row; main[0] = top-left, main[k] = top[k-1], and for k < 0 the side (left) sample projected through the inverse
+ * angle.  Horizontal class (2..17) is the same with left and top swapped and rows and columns swapped: it runs against the transposed source.
+ * main[0 .. 2N] of both classes is built once per CU (search_cu); a negative angle adds its projected side samples below index 0.
+ * The N < 32 edge filter of 10 / 26 touches column 0 of the (transposed) rows only and is patched in there. */
+template <int K, int LG>
+__device__ __forceinline__ uint32_t sad_angular(const OisShared<K> &S, const CuView<LG> &c, int mode, int lane)
 {
-    int cx, cy, N, lg;
-    cu_geom(cu, cx, cy, N, lg);
-    const uint8_t *r = S.refs + ref_base(cu);
-    const int dc = S.dc[cu];
-    const uint32_t dc4 = (uint32_t)dc * 0x01010101u;
-    const int qshift = lg - 2; /* dwords per row = N / 4 */
+    constexpr int N = 1 << LG, NQ = (N * N) >> 2, QS = LG - 2;
+    const bool vert = mode >= 18;
+    const int d = vert ? mode - 26 : 10 - mode; /* -8..8 */
+    const int a = d < 0 ? -c_ang[-d] : c_ang[d];
+    const uint8_t *left = c.r, *top = c.r + 2 * N + 1;
+    const int tl = c.r[2 * N];
+    const uint8_t *mainr = vert ? top : left, *side = vert ? left : top;
+    uint8_t *ext = c.ext + (vert ? 0 : EXT_W);
+    if (a < 0) { /* main[k] for kmin <= k < 0; kmin = ((N*a) >> 5) + 1 is the lowest index any sample reads */
+        const int kmin = ((N * a) >> 5) + 1, k = -1 - lane;
+        wave_lds_sync(); /* the previous mode's rows have read ext */
+        if (k >= kmin)
+            ext[EXT_OFF + k] = side[((-k * c_inv[-d] + 128) >> 8) - 1];
+        wave_lds_sync();
+    }
+
+    const uint8_t *src = vert ? &S.u.src.win[(c.cy + 1) * WIN_W + c.cx + WIN_X0] : &S.u.src.wint[c.cx * 64 + c.cy];
+    const int pitch = vert ? WIN_W : 64;
+    const bool edge = N < 32 && d == 0;
+    const uint32_t M = 0x00FF00FFu;
     uint32_t acc = 0;
-    for (int q = lane; q < (N * N) >> 2; q += 64) {
-        const int y = q >> qshift, x4 = (q & ((1 << qshift) - 1)) << 2;
-        const uint32_t sv = *(const uint32_t *)&S.win[(cy + y + 1) * WIN_W + cx + x4 + WIN_X0];
-        uint32_t pv = dc4;
-        if (N < 32 && (y == 0 || x4 == 0)) {
-            pv = 0;
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-                pv |= (uint32_t)predict_sample(1, N, lg, r, x4 + i, y, dc) << (8 * i);
+#pragma unroll 1
+    for (int q0 = 0; q0 < NQ; q0 += 64) {
+        const int q = q0 + lane;
+        if (NQ >= 64 || q < NQ) {
+            const int v = q >> QS, u4 = (q & ((1 << QS) - 1)) << 2;
+            const int pos = (v + 1) * a, i = pos >> 5, f = pos & 31;
+            const int o = EXT_OFF + u4 + i + 1; /* main[u4 + i + 1] */
+            const uint32_t *e32 = (const uint32_t *)&ext[o & ~3];
+            const uint64_t w64 = (((uint64_t)e32[1] << 32) | e32[0]) >> ((o & 3) * 8); /* bytes B0..B4 = main[u4+i+1 .. u4+i+5] */
+            const uint32_t w = (uint32_t)w64;
+            const uint32_t p0 = w & M, p1 = (w >> 8) & M, p2 = (uint32_t)(w64 >> 16) & M; /* {B0,B2}, {B1,B3}, {B2,B4} */
+            const uint32_t lo = ((p0 * (uint32_t)(32 - f) + p1 * (uint32_t)f + 0x00100010u) >> 5) & M;
+            const uint32_t hi = ((p1 * (uint32_t)(32 - f) + p2 * (uint32_t)f + 0x00100010u) >> 5) & M;
+            uint32_t pv = lo | (hi << 8);
+            if (edge && u4 == 0)
+                pv = (pv & ~0xFFu) | (uint32_t)min(255, max(0, mainr[0] + ((side[v] - tl) >> 1)));
+            acc = __builtin_amdgcn_sad_u8(*(const uint32_t *)&src[v * pitch + u4], pv, acc);
         }
-        acc = __builtin_amdgcn_sad_u8(sv, pv, acc);
     }
     return wave_sum(acc);
+}
+
+template <int K, int LG>
+__device__ __forceinline__ uint32_t mode_sad(const OisShared<K> &S, const CuView<LG> &c, int mode, int lane)
+{
+    return mode < 2 ? sad_planar_dc(S, c, mode, lane) : sad_angular(S, c, mode, lane);
+}
+
+/* the search of CU `cu` (N = 1 << LG) by one wave: references, DC, then the CU's modes (P/B: DC SAD -> GetOisPoint -> stage-1 modes) */
+template <int K, int LG>
+__device__ __forceinline__ void search_cu(OisShared<K> &S, const SvtAmdOisParams &P, const SvtAmdMeLcuResult *__restrict__ me, int lcu, int cu, int lx,
+                                          int ly, bool wide, int wave, int lane)
+{
+    constexpr int N = 1 << LG;
+    const int W = P.luma_width, H = P.luma_height;
+    CuView<LG> c;
+    int n_, lg_;
+    cu_geom(cu, c.cx, c.cy, n_, lg_);
+    const int ox = lx + c.cx, oy = ly + c.cy;
+    if (ox + N > W || oy + N > H)
+        return;
+    uint8_t *R = S.refs[wave];
+    wave_lds_sync(); /* the previous CU's modes have read R and ext */
+    for (int e = lane; e < 4 * N + 1; e += 64) {
+        int v = 128;
+        if (e < 2 * N) {
+            if (ox != 0 && oy + e < H)
+                v = S.u.src.win[(c.cy + e + 1) * WIN_W + c.cx + WIN_X0 - 1];
+        } else if (e == 2 * N) {
+            if (ox != 0 && oy != 0)
+                v = S.u.src.win[c.cy * WIN_W + c.cx + WIN_X0 - 1];
+        } else {
+            const int j = e - 2 * N - 1;
+            if (oy != 0 && ox + j < W)
+                v = S.u.src.win[c.cy * WIN_W + c.cx + j + WIN_X0];
+        }
+        R[e] = (uint8_t)v;
+    }
+    wave_lds_sync();
+    /* main[0 .. 2N] of both classes (top-left, then top / left); main[2N+1 ..] is read with weight 0 only (angle 32) */
+    uint8_t *ext = S.ext[wave][0];
+    for (int e = lane; e < 2 * N + 5; e += 64) {
+        ext[EXT_OFF + e] = e <= 2 * N ? R[2 * N + e] : 0;
+        ext[EXT_W + EXT_OFF + e] = e == 0 ? R[2 * N] : e <= 2 * N ? R[e - 1] : 0;
+    }
+    wave_lds_sync();
+    c.r = R;
+    c.ext = ext;
+    c.dc = (int)((wave_sum(lane < N ? (uint32_t)R[lane] + R[2 * N + 1 + lane] : 0u) + N) >> (LG + 1));
+
+    const uint8_t *modes = c_islice; /* the modes to test, in SAD-slot order */
+    int nk;
+    if (P.slice_is_intra) {
+        nk = N == 32 ? 1 : 7; /* 32x32: planar only */
+    } else if (wide) {
+        modes = c_all35, nk = 35;
+    } else {
+        const uint32_t dcSad = sad_planar_dc(S, c, 1, lane); /* DC -> slot 9 */
+        if (lane == 0)
+            S.sad[cu][9] = dcSad;
+        if (P.limit_ois_to_dc_mode)
+            return;
+        /* GetInterIntraSadDistance / GetOisPoint (EbMotionEstimation.c:4782,4814) */
+        const uint32_t meSad = me[lcu].pu[cu].distortion[0];
+        const int32_t diff = (int32_t)((meSad - dcSad) * 100u);
+        const int32_t dist = dcSad ? diff / (int32_t)dcSad : 0;
+        int point = 4;
+        const int16_t *th = c_ois_th[P.ois_th_set][P.temporal_layer_index];
+        if (dcSad == 0 || meSad == 0 || dist <= th[0])
+            point = 0;
+        else if (dist <= th[1])
+            point = 1;
+        else if (dist <= th[2])
+            point = 2;
+        else if (dist <= th[3])
+            point = 3;
+        modes = c_stage1, nk = point == 0 ? 0 : 2 * point + 1;
+        if (lane == 0)
+            S.nmodes[cu] = (uint8_t)nk;
+    }
+    for (int k = 0; k < nk; k++) {
+        const uint32_t s = mode_sad(S, c, modes[k], lane);
+        if (lane == 0)
+            S.sad[cu][k] = s;
+    }
 }
 
 #define W_DIST (1u << 21)
@@ -180,10 +287,11 @@ __device__ __forceinline__ void set_mode(uint32_t &c, uint32_t m) { c = (c & 0x0
 /* Decision step of one CU given its SADs (S.sad[cu][k], k = position in the tested mode list).
  * bestMode / stage1 carry the reference's function-scope state; returns false when the search of this CU did not
  * update bestMode (the caller must then replay serially). */
-__device__ bool decide_cu(OisShared &S, const SvtAmdOisParams &P, int cu, bool valid, uint32_t meSad, uint32_t &bestMode,
+template <int K>
+__device__ bool decide_cu(OisShared<K> &S, const SvtAmdOisParams &P, int cu, bool valid, uint32_t meSad, uint32_t &bestMode,
                           uint32_t *stage1)
 {
-    uint32_t *cand = S.out_cand[cu];
+    uint32_t *cand = S.u.out_cand[cu];
     for (int k = 0; k < SVT_AMD_OIS_MAX_CAND; k++)
         cand[k] = 0;
     S.out_total[cu] = 0xFF;
@@ -223,7 +331,7 @@ __device__ bool decide_cu(OisShared &S, const SvtAmdOisParams &P, int cu, bool v
     }
     if (!valid)
         return true;
-    if (P.ois_kernel_level) {
+    if (K >= 35 && P.ois_kernel_level) {
         for (int k = 0; k < 18; k++)
             set_valid(cand[k], 0);
         for (uint32_t m = 0; m < 35; m++) {
@@ -291,9 +399,11 @@ __device__ bool decide_cu(OisShared &S, const SvtAmdOisParams &P, int cu, bool v
     return updated;
 }
 
-__global__ __launch_bounds__(256) void k_ois_picture(const OisJobDev *__restrict__ jobs)
+/* K = 10: intra slices and the P/B stage-1 search (19.9 KB LDS, at most 64 VGPRs: 8 workgroups per CU); K = 35: a batch with a P/B picture under
+ * ois_kernel_level (27.9 KB: 5 workgroups per CU) */
+template <int K> __global__ __launch_bounds__(256, K >= 35 ? 5 : 8) void k_ois_picture(const OisJobDev *__restrict__ jobs)
 {
-    __shared__ OisShared S;
+    __shared__ OisShared<K> S;
     const OisJobDev &J = jobs[blockIdx.y];
     const int lcu = blockIdx.x;
     if (lcu >= J.nlcu)
@@ -303,138 +413,54 @@ __global__ __launch_bounds__(256) void k_ois_picture(const OisJobDev *__restrict
     const int pitch = J.pitch, lcus_w = J.lcus_w;
     const SvtAmdMeLcuResult *__restrict__ me = J.me;
     SvtAmdOisLcuResult *__restrict__ out = J.out;
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
     const int lx = (lcu % lcus_w) * 64, ly = (lcu / lcus_w) * 64;
     const int W = P.luma_width, H = P.luma_height;
+    const bool wide = K >= 35 && !P.slice_is_intra && P.ois_kernel_level;
     const int last = P.slice_is_intra ? 84 : ((P.skip_ois_8x8 || P.cu8x8_mode == 1) ? 20 : 84);
 
-    /* 1. window (the padded plane makes every address valid; out-of-picture samples are never USED); rows start at
-     * LCU column -4, a dword boundary of the plane, so every load is one aligned dword */
-    for (int i = t; i < WIN_H * 25; i += 256) {
-        const int row = i / 25, c4 = i - row * 25;
-        *(uint32_t *)&S.win[row * WIN_W + c4 * 4] =
-            *(const uint32_t *)(full + (ptrdiff_t)(ly + row - 1) * pitch + lx - WIN_X0 + c4 * 4);
+    /* 1. window (the padded plane makes every address valid; out-of-picture samples are never USED): rows start at LCU column -16, a
+     * 16-byte boundary of the plane, seven 16-byte loads per row */
+    for (int i = t; i < WIN_H * 8; i += 256) {
+        const int row = i >> 3, c16 = i & 7;
+        if (c16 < 7)
+            *(uint4 *)&S.u.src.win[row * WIN_W + c16 * 16] = *(const uint4 *)(full + (ptrdiff_t)(ly + row - 1) * pitch + lx - WIN_X0 + c16 * 16);
     }
     if (t == 0)
         S.stale = 0;
     __syncthreads();
-
-    /* 2. reference arrays of every CU */
-    const int nref = last == 20 ? 516 + 1040 : 516 + 1040 + 2112; /* no 8x8 CUs when last == 20 */
-    for (int i = t; i < nref; i += 256) {
-        int cu, e;
-        if (i < 516)
-            cu = 1 + i / 129, e = i % 129;
-        else if (i < 1556)
-            cu = 5 + (i - 516) / 65, e = (i - 516) % 65;
-        else
-            cu = 21 + (i - 1556) / 33, e = (i - 1556) % 33;
-        int cx, cy, N, lg;
-        cu_geom(cu, cx, cy, N, lg);
-        const int ox = lx + cx, oy = ly + cy;
-        int v = 128;
-        if (e < 2 * N) {
-            if (ox != 0 && oy + e < H)
-                v = S.win[(cy + e + 1) * WIN_W + cx + WIN_X0 - 1];
-        } else if (e == 2 * N) {
-            if (ox != 0 && oy != 0)
-                v = S.win[cy * WIN_W + cx + WIN_X0 - 1];
-        } else {
-            const int j = e - 2 * N - 1;
-            if (oy != 0 && ox + j < W)
-                v = S.win[cy * WIN_W + cx + j + WIN_X0];
-        }
-        S.refs[i] = (uint8_t)v;
-    }
-    __syncthreads();
-    if (t >= 1 && t <= last) {
-        int cx, cy, N, lg;
-        cu_geom(t, cx, cy, N, lg);
-        const uint8_t *r = S.refs + ref_base(t);
-        uint32_t s = 0;
-        for (int k = 0; k < N; k++)
-            s += r[k] + r[2 * N + 1 + k];
-        S.dc[t] = (uint8_t)((s + N) >> (lg + 1));
-        S.nmodes[t] = 0;
+    /* ... and its 64x64 samples transposed: a 4x4 block per thread */
+    {
+        const int x0 = (t & 15) << 2, y0 = (t >> 4) << 2;
+        const uint8_t *w0 = &S.u.src.win[(y0 + 1) * WIN_W + x0 + WIN_X0];
+        const uint32_t r0 = *(const uint32_t *)w0, r1 = *(const uint32_t *)(w0 + WIN_W), r2 = *(const uint32_t *)(w0 + 2 * WIN_W),
+                       r3 = *(const uint32_t *)(w0 + 3 * WIN_W);
+        const uint32_t a = __builtin_amdgcn_perm(r1, r0, 0x05010400u), b = __builtin_amdgcn_perm(r1, r0, 0x07030602u); /* {r0[0],r1[0],r0[1],r1[1]}, {..[2], ..[3]} */
+        const uint32_t c = __builtin_amdgcn_perm(r3, r2, 0x05010400u), d = __builtin_amdgcn_perm(r3, r2, 0x07030602u);
+        uint8_t *o = &S.u.src.wint[x0 * 64 + y0];
+        *(uint32_t *)o = __builtin_amdgcn_perm(c, a, 0x05040100u);
+        *(uint32_t *)(o + 64) = __builtin_amdgcn_perm(c, a, 0x07060302u);
+        *(uint32_t *)(o + 128) = __builtin_amdgcn_perm(d, b, 0x05040100u);
+        *(uint32_t *)(o + 192) = __builtin_amdgcn_perm(d, b, 0x07060302u);
     }
     __syncthreads();
 
+    /* 2. a wave per CU: CU 1 + wave, then 5 + wave, 9 + wave, ... */
+    search_cu<K, 5>(S, P, me, lcu, 1 + wave, lx, ly, wide, wave, lane);
+    for (int cu = 5 + wave; cu < 21; cu += 4)
+        search_cu<K, 4>(S, P, me, lcu, cu, lx, ly, wide, wave, lane);
+    if (last == 84)
+        for (int cu = 21 + wave; cu < 85; cu += 4)
+            search_cu<K, 3>(S, P, me, lcu, cu, lx, ly, wide, wave, lane);
+    __syncthreads();
+
+    /* 3. decisions: one thread per CU, then the serial replay if the carried state mattered (out_cand overlays the window) */
 #define CU_VALID(cu_, v_)                                                          \
     do {                                                                           \
         int cx_, cy_, N_, lg_;                                                     \
         cu_geom(cu_, cx_, cy_, N_, lg_);                                           \
         v_ = !(lx + cx_ + N_ > W || ly + cy_ + N_ > H);                            \
     } while (0)
-
-    /* 3. SAD tasks */
-    if (P.slice_is_intra) {
-        for (int task = wave; task < 4 + 80 * 7; task += 4) {
-            const int cu = task < 4 ? 1 + task : 5 + (task - 4) / 7, k = task < 4 ? 0 : (task - 4) % 7;
-            bool valid;
-            CU_VALID(cu, valid);
-            if (!valid)
-                continue;
-            const uint32_t s = task_sad(S, cu, c_islice[k], lane);
-            if (lane == 0)
-                S.sad[cu][k] = s;
-        }
-    } else if (P.ois_kernel_level) {
-        for (int task = wave; task < last * 35; task += 4) {
-            const int cu = 1 + task / 35, m = task % 35;
-            bool valid;
-            CU_VALID(cu, valid);
-            if (!valid)
-                continue;
-            const uint32_t s = task_sad(S, cu, m, lane);
-            if (lane == 0)
-                S.sad[cu][m] = s;
-        }
-    } else {
-        for (int cu = 1 + wave; cu <= last; cu += 4) { /* DC of every CU -> slot 9 */
-            bool valid;
-            CU_VALID(cu, valid);
-            if (!valid)
-                continue;
-            const uint32_t s = task_sad_dc(S, cu, lane);
-            if (lane == 0)
-                S.sad[cu][9] = s;
-        }
-        __syncthreads();
-        if (!P.limit_ois_to_dc_mode) {
-            if (t >= 1 && t <= last) { /* GetInterIntraSadDistance / GetOisPoint (EbMotionEstimation.c:4782,4814) */
-                bool valid;
-                CU_VALID(t, valid);
-                if (valid) {
-                    const uint32_t meSad = me[lcu].pu[t].distortion[0], dcSad = S.sad[t][9];
-                    const int32_t diff = (int32_t)((meSad - dcSad) * 100u);
-                    const int32_t dist = dcSad ? diff / (int32_t)dcSad : 0;
-                    int point = 4;
-                    const int16_t *th = c_ois_th[P.ois_th_set][P.temporal_layer_index];
-                    if (dcSad == 0 || meSad == 0 || dist <= th[0])
-                        point = 0;
-                    else if (dist <= th[1])
-                        point = 1;
-                    else if (dist <= th[2])
-                        point = 2;
-                    else if (dist <= th[3])
-                        point = 3;
-                    S.nmodes[t] = (uint8_t)(point == 0 ? 0 : 2 * point + 1);
-                }
-            }
-            __syncthreads();
-            for (int task = wave; task < last * 9; task += 4) {
-                const int cu = 1 + task / 9, k = task % 9;
-                if (k >= S.nmodes[cu])
-                    continue;
-                const uint32_t s = task_sad(S, cu, c_stage1[k], lane);
-                if (lane == 0)
-                    S.sad[cu][k] = s;
-            }
-        }
-    }
-    __syncthreads();
-
-    /* 4. decisions: one thread per CU, then the serial replay if the carried state mattered */
     if (t >= 1 && t <= 84) {
         if (t <= last) {
             bool valid;
@@ -446,13 +472,13 @@ __global__ __launch_bounds__(256) void k_ois_picture(const OisJobDev *__restrict
                 S.stale = 1;
         } else {
             for (int k = 0; k < SVT_AMD_OIS_MAX_CAND; k++)
-                S.out_cand[t][k] = 0;
+                S.u.out_cand[t][k] = 0;
             S.out_total[t] = 0xFF;
         }
     }
     if (t == 0) {
         for (int k = 0; k < SVT_AMD_OIS_MAX_CAND; k++)
-            S.out_cand[0][k] = 0;
+            S.u.out_cand[0][k] = 0;
         S.out_total[0] = 0xFF;
     }
     __syncthreads();
@@ -468,11 +494,11 @@ __global__ __launch_bounds__(256) void k_ois_picture(const OisJobDev *__restrict
     }
     __syncthreads();
 
-    /* 5. write the record */
+    /* 4. write the record */
     uint32_t *o = (uint32_t *)&out[lcu];
-    const uint32_t *c = &S.out_cand[0][0];
+    const uint32_t *cs = &S.u.out_cand[0][0];
     for (int i = t; i < 85 * SVT_AMD_OIS_MAX_CAND; i += 256)
-        o[i] = c[i];
+        o[i] = cs[i];
     uint8_t *ot = out[lcu].total_intra_luma_mode;
     if (t < 88)
         ot[t] = t < 85 ? S.out_total[t] : 0;
@@ -485,7 +511,13 @@ int svt_amd_launch_ois_batch(SvtAmdContext *ctx, const OisJobDev *host_jobs, int
         if (rcd)
             return rcd;
     }
-    hipLaunchKernelGGL(k_ois_picture, dim3(max_lcus, njobs), dim3(256), 0, ctx->stream, (const OisJobDev *)ctx->d_ois_jobs);
+    bool wide = false; /* 35 SAD columns per CU only when some P/B picture of the batch ranks every mode */
+    for (int i = 0; i < njobs; i++)
+        wide |= !host_jobs[i].P.slice_is_intra && host_jobs[i].P.ois_kernel_level;
+    if (wide)
+        hipLaunchKernelGGL(k_ois_picture<35>, dim3(max_lcus, njobs), dim3(256), 0, ctx->stream, (const OisJobDev *)ctx->d_ois_jobs);
+    else
+        hipLaunchKernelGGL(k_ois_picture<10>, dim3(max_lcus, njobs), dim3(256), 0, ctx->stream, (const OisJobDev *)ctx->d_ois_jobs);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
 }

@@ -18,7 +18,7 @@ meta = {}
 for f in glob.glob(O + "/p*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
-        k = "k_ois_picture" if "k_ois" in k else "k_prep_fused" if "k_prep" in k else None
+        k = "k_ois_picture" if "k_ois_picture" in k else "k_prep_fused" if "k_prep" in k else None  # not k_pack_ois
         if not k:
             continue
         acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
