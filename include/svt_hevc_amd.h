@@ -133,9 +133,10 @@ SVT_AMD_API int svt_amd_context_create(int device_ordinal, uint16_t max_luma_wid
                                        SvtAmdContext **out_ctx);
 SVT_AMD_API void svt_amd_context_destroy(SvtAmdContext *ctx);
 SVT_AMD_API const char *svt_amd_version(void);
-/* OPT-IN process setting for hosts that keep several pictures in flight (lanes = HIP streams): asks the HIP runtime for 24 hardware queues
+/* OPT-IN process setting for hosts that keep MORE streams in flight than the runtime's hardware queues (four by default; lanes = HIP streams, and
+ * a context or lane holds a stream only from its first stream-ordered call on, see svt_amd_context_fork): asks the HIP runtime for 24 hardware queues
  * (GPU_MAX_HW_QUEUES, unless the user set it) so that every lane's stream has a queue of its own.  Only has an effect BEFORE the process's first
- * HIP call; the library never changes the environment on its own. */
+ * HIP call; the library never changes the environment on its own.  A host with up to three lanes beside the process's null stream does not need it. */
 SVT_AMD_API int svt_amd_runtime_env_defaults(void);
 /* OPT-IN device setting for hosts whose threads wait on the device while OTHER host threads have work to do (the encoder binding: up to a dozen EncDec threads
  * wait 60 - 100 ms each for their picture's mode-decision kernel while the base-layer pictures are decided on the same 32 logical processors): the threads sleep
@@ -278,6 +279,11 @@ SVT_AMD_API int svt_amd_zz_sad_picture(SvtAmdContext *ctx, int cur_slot, int pre
  * the one that owns the picture slots (svt_amd_context_fork): all lanes see the same slots, each has its own stream,
  * descriptors, timers and pinned result buffers.  The owning context is itself a lane.  Calls on one lane are serialised by
  * the caller; different lanes may be driven from different threads.
+ * A context - the owner or a lane - takes its stream at its first stream-ordered call (a launch, an asynchronous copy or upload, a
+ * lane event, a timer), not when it is made: an owner that only allocates (svt_amd_device_alloc, svt_amd_host_alloc), copies blocking
+ * (svt_amd_device_upload / _download / _copy) and forks holds none, and svt_amd_synchronize of it returns at once.  Streams beyond the
+ * runtime's hardware queues (four by default) share one and run in submission order with their neighbour, so what counts is the number
+ * of contexts that queue work: three lanes under such an owner run side by side at the default (svt_amd_runtime_env_defaults for more).
  *   svt_amd_picture_upload_async  copies `luma` into pinned staging before returning (caller may reuse it), queues the rest
  *   svt_amd_frontend_submit       queues ME (has_me) and/or OIS (has_ois) of cur_slot + the result copies; never blocks
  *   svt_amd_frontend_wait         blocks until the lane's job is complete; *me / *ois point at the lane's pinned buffers

@@ -338,26 +338,26 @@ extern "C" int svt_amd_coeff_scan_picture(SvtAmdContext *ctx, const void *works,
     const uint8_t *d_works = (const uint8_t *)works, *d_results = (const uint8_t *)results;
     if (!device_arrays) { /* only the heads travel: unit lists without the source samples, flags + coefficients without the reconstruction */
         uint8_t *dw = (uint8_t *)d_levels + b_lpool, *dr = dw + b_works;
-        HIP_TRY(hipMemcpy2DAsync(dw, work_head, works, work_stride, work_head, n, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpy2DAsync(dr, result_head, results, result_stride, result_head, n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpy2DAsync(dw, work_head, works, work_stride, work_head, n, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+        HIP_TRY(hipMemcpy2DAsync(dr, result_head, results, result_stride, result_head, n, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
         d_works = dw, d_results = dr, work_stride = work_head, result_stride = result_head;
     }
-    hipLaunchKernelGGL(k_coeff_scan, dim3((unsigned)n_lcus), dim3(256), 0, ctx->stream, d_works, work_stride, d_results, result_stride, d_lcus, d_gpool, d_lpool);
-    hipLaunchKernelGGL(k_coeff_scan_bases, dim3(1), dim3(1024), 0, ctx->stream, d_lcus, n_lcus, d_totals);
-    hipLaunchKernelGGL(k_coeff_scan_compact, dim3((unsigned)n_lcus), dim3(256), 0, ctx->stream, d_lcus, d_gpool, d_lpool, d_groups, group_capacity, d_levels,
+    hipLaunchKernelGGL(k_coeff_scan, dim3((unsigned)n_lcus), dim3(256), 0, svt_amd_ctx_stream(ctx), d_works, work_stride, d_results, result_stride, d_lcus, d_gpool, d_lpool);
+    hipLaunchKernelGGL(k_coeff_scan_bases, dim3(1), dim3(1024), 0, svt_amd_ctx_stream(ctx), d_lcus, n_lcus, d_totals);
+    hipLaunchKernelGGL(k_coeff_scan_compact, dim3((unsigned)n_lcus), dim3(256), 0, svt_amd_ctx_stream(ctx), d_lcus, d_gpool, d_lpool, d_groups, group_capacity, d_levels,
                        level_capacity);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(totals, d_totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(lcus, d_lcus, n * sizeof(SvtAmdCoeffScanLcu), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(totals, d_totals, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(lcus, d_lcus, n * sizeof(SvtAmdCoeffScanLcu), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     if (totals[0] > group_capacity || totals[1] > level_capacity) {
         svt_amd_set_error("svt_amd_coeff_scan_picture: %u groups / %u levels do not fit the capacities %u / %u", totals[0], totals[1], group_capacity, level_capacity);
         return SVT_AMD_ERR_RESOURCES;
     }
     if (totals[0])
-        HIP_TRY(hipMemcpyAsync(groups, d_groups, (size_t)totals[0] * sizeof(SvtAmdCoeffScanGroup), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(groups, d_groups, (size_t)totals[0] * sizeof(SvtAmdCoeffScanGroup), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     if (totals[1])
-        HIP_TRY(hipMemcpyAsync(levels, d_levels, (size_t)totals[1] * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpyAsync(levels, d_levels, (size_t)totals[1] * sizeof(uint16_t), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }

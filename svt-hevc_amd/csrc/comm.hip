@@ -146,7 +146,7 @@ extern "C" int svt_amd_comm_destroy(SvtAmdContext *ctx)
     if (!ctx)
         return SVT_AMD_ERR_BAD_PARAM;
     if (ctx->comm) {
-        (void)hipStreamSynchronize(ctx->stream);
+        (void)svt_amd_ctx_sync(ctx);
         g_rccl.CommDestroy((RcclComm)ctx->comm);
         ctx->comm = NULL;
     }
@@ -212,7 +212,7 @@ static int xchg_prepare(SvtAmdContext *ctx, const SvtAmdRect *rects, int world, 
     mx = (mx + 255) & ~(size_t)255;
     const size_t need = mx * (size_t)world + (size_t)world * sizeof(SvtAmdRect) + 256;
     if (need > ctx->xchg_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(svt_amd_ctx_sync(ctx));
         if (ctx->d_xchg)
             (void)hipFree(ctx->d_xchg);
         ctx->d_xchg = NULL, ctx->xchg_bytes = 0;
@@ -243,7 +243,7 @@ extern "C" int svt_amd_recon_exchange(SvtAmdContext *ctx, void *const d_planes[3
     if (rc)
         return rc;
     SvtAmdRect *d_rects = (SvtAmdRect *)(ctx->d_xchg + slot * (size_t)world);
-    HIP_TRY(hipMemcpyAsync(d_rects, rects, sizeof(SvtAmdRect) * (size_t)world, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_rects, rects, sizeof(SvtAmdRect) * (size_t)world, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     XchgPlanes P;
     for (int p = 0; p < 3; p++)
         P.p[p] = (uint8_t *)d_planes[p], P.pitch[p] = pitch_bytes[p];
@@ -255,10 +255,10 @@ extern "C" int svt_amd_recon_exchange(SvtAmdContext *ctx, void *const d_planes[3
     }
     const unsigned gx = (unsigned)((mx_items + 255) / 256);
     /* own rectangle -> own slot (in place all-gather: send buffer = own slot of the receive buffer) */
-    hipLaunchKernelGGL(k_xchg_copy, dim3(gx, 1), dim3(256), 0, ctx->stream, P, ctx->d_xchg, slot, d_rects, bytes_per_sample, rank, 1, -1, 1);
-    RCCL_TRY(g_rccl.AllGather(ctx->d_xchg + slot * (size_t)rank, ctx->d_xchg, slot, 0 /* ncclInt8 */, (RcclComm)ctx->comm, ctx->stream));
+    hipLaunchKernelGGL(k_xchg_copy, dim3(gx, 1), dim3(256), 0, svt_amd_ctx_stream(ctx), P, ctx->d_xchg, slot, d_rects, bytes_per_sample, rank, 1, -1, 1);
+    RCCL_TRY(g_rccl.AllGather(ctx->d_xchg + slot * (size_t)rank, ctx->d_xchg, slot, 0 /* ncclInt8 */, (RcclComm)ctx->comm, svt_amd_ctx_stream(ctx)));
     /* everybody else's slots -> the local planes */
-    hipLaunchKernelGGL(k_xchg_copy, dim3(gx, (unsigned)world), dim3(256), 0, ctx->stream, P, ctx->d_xchg, slot, d_rects, bytes_per_sample, 0, world,
+    hipLaunchKernelGGL(k_xchg_copy, dim3(gx, (unsigned)world), dim3(256), 0, svt_amd_ctx_stream(ctx), P, ctx->d_xchg, slot, d_rects, bytes_per_sample, 0, world,
                        rank, 0);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -278,7 +278,7 @@ extern "C" int svt_amd_recon_broadcast(SvtAmdContext *ctx, void *const d_planes[
     }
     HIP_TRY(hipSetDevice(ctx->device));
     for (int p = 0; p < 3; p++)
-        RCCL_TRY(g_rccl.Broadcast(d_planes[p], d_planes[p], bytes[p], 0 /* ncclInt8 */, root, (RcclComm)ctx->comm, ctx->stream));
+        RCCL_TRY(g_rccl.Broadcast(d_planes[p], d_planes[p], bytes[p], 0 /* ncclInt8 */, root, (RcclComm)ctx->comm, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -296,13 +296,13 @@ extern "C" int svt_amd_recon_pack(SvtAmdContext *ctx, void *const d_planes[3], c
     if (rc)
         return rc;
     SvtAmdRect *d_rects = (SvtAmdRect *)(ctx->d_xchg + slot * (size_t)world);
-    HIP_TRY(hipMemcpyAsync(d_rects, rects, sizeof(SvtAmdRect) * (size_t)world, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_rects, rects, sizeof(SvtAmdRect) * (size_t)world, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     XchgPlanes P;
     for (int p = 0; p < 3; p++)
         P.p[p] = (uint8_t *)d_planes[p], P.pitch[p] = pitch_bytes[p];
     const size_t wb = (size_t)rects[r].w * bytes_per_sample;
     const size_t items = ((wb + 15) >> 4) * rects[r].h + 2 * (((wb / 2) + 15) >> 4) * (rects[r].h >> 1);
-    hipLaunchKernelGGL(k_xchg_copy, dim3((unsigned)((items + 255) / 256), 1), dim3(256), 0, ctx->stream, P, (uint8_t *)d_slots, slot_bytes, d_rects,
+    hipLaunchKernelGGL(k_xchg_copy, dim3((unsigned)((items + 255) / 256), 1), dim3(256), 0, svt_amd_ctx_stream(ctx), P, (uint8_t *)d_slots, slot_bytes, d_rects,
                        bytes_per_sample, r, 1, -1, to_slot);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;

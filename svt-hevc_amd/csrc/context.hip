@@ -54,8 +54,7 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
     if (!ctx)
         return;
     (void)hipSetDevice(ctx->device);
-    if (ctx->stream)
-        (void)hipStreamSynchronize(ctx->stream);
+    (void)svt_amd_ctx_sync(ctx);
     (void)svt_amd_comm_destroy(ctx);
     for (int i = 0; !ctx->parent && ctx->slots && i < ctx->num_slots; i++) {
         DevPicture *s = &ctx->slots[i];
@@ -114,6 +113,8 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
         (void)hipFree(ctx->d_ois_jobs);
     if (ctx->d_prep_jobs)
         (void)hipFree(ctx->d_prep_jobs);
+    if (ctx->d_pack_src)
+        (void)hipFree(ctx->d_pack_src);
     if (ctx->d_dbg)
         (void)hipFree(ctx->d_dbg);
     for (int i = 0; i < ctx->cap_stamps; i++) {
@@ -130,16 +131,16 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
     free(ctx);
 }
 
-/* stream, events, descriptor / cost buffers: everything a context or a lane owns besides the picture slots */
+/* events, descriptor / cost buffers: everything a context or a lane owns besides the picture slots and the stream (svt_amd_ctx_stream) */
 static int context_common_create(SvtAmdContext *ctx)
 {
-    HIP_TRY(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
     HIP_TRY(hipEventCreate(&ctx->ev_begin));
     HIP_TRY(hipEventCreate(&ctx->ev_end));
     HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming | hipEventBlockingSync)); /* waited on for milliseconds by several host threads: they sleep */
     const int nlcu = ((ctx->max_w + 63) / 64) * ((ctx->max_h + 63) / 64);
     if (hipMalloc((void **)&ctx->d_me_scratch, (size_t)nlcu * sizeof(SvtAmdMeLcuResult)) != hipSuccess ||
         hipMalloc(&ctx->d_prep_jobs, 128 * SVT_AMD_MAX_BATCH) != hipSuccess ||
+        hipMalloc(&ctx->d_pack_src, sizeof(PackSrc) * SVT_AMD_MAX_BATCH) != hipSuccess ||
         hipMalloc((void **)&ctx->d_ois_jobs, sizeof(OisJobDev) * SVT_AMD_MAX_BATCH) != hipSuccess ||
         hipMalloc((void **)&ctx->d_jobs, sizeof(MeJobDev) * SVT_AMD_MAX_BATCH) != hipSuccess ||
         hipMalloc(&ctx->d_cabac_cost, sizeof(SvtAmdCabacCost)) != hipSuccess) {
@@ -149,10 +150,22 @@ static int context_common_create(SvtAmdContext *ctx)
     return SVT_AMD_OK;
 }
 
+hipStream_t svt_amd_ctx_stream(SvtAmdContext *ctx)
+{
+    if (!ctx->stream && !ctx->stream_failed) {
+        const hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+        if (e != hipSuccess) { /* the null stream keeps this context's work in order from here on; svt_amd_synchronize returns the error */
+            svt_amd_set_error("hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
+            ctx->stream = nullptr, ctx->stream_failed = 1;
+        }
+    }
+    return ctx->stream;
+}
+
 int svt_amd_ctx_scratch(SvtAmdContext *ctx, size_t bytes, uint8_t **out)
 {
     if (bytes > ctx->leaf_scratch_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(svt_amd_ctx_sync(ctx));
         if (ctx->d_leaf_scratch)
             (void)hipFree(ctx->d_leaf_scratch);
         ctx->d_leaf_scratch = nullptr;
@@ -165,12 +178,18 @@ int svt_amd_ctx_scratch(SvtAmdContext *ctx, size_t bytes, uint8_t **out)
     return SVT_AMD_OK;
 }
 
-/* Lanes are streams, and streams only run side by side when each has a hardware queue of its own: with the HIP runtime's default
- * of four, a fifth stream shares a queue and its markers serialise with whatever that queue holds (a result copy of one lane then
- * waits for another lane's kernels and vice versa; measured in bench.py, 1,680 -> 2,450 pictures/s).  The runtime reads the variable when it
- * starts, i.e. at the process's first HIP call - so this is a call the HOST makes, knowingly, before that (the encoder binding does, at
- * EbInitEncoder time: integration/svt_hook_me.c).  The library itself never touches the environment of the process that
- * loaded it; a setting the user made wins. */
+/* Lanes are streams, and streams only run side by side when each has a hardware queue of its own: the HIP runtime hands out
+ * GPU_MAX_HW_QUEUES of them (four by default), a stream beyond that shares one, and whatever it queues then runs in submission order with
+ * the other stream's work (a result copy of one lane waits for another lane's kernels and vice versa: profiles/r02_k_timeline.txt, and
+ * profiles/r08_a_before_timeline.txt for the same signature at four queues).  Two things keep a host's lanes apart:
+ *  - the library takes no queue it does not need: a context gets its stream at its first stream-ordered use (svt_amd_ctx_stream), so the
+ *    root of a host that works on lanes - it allocates, pins, copies blocking and forks - holds none.  A host with three lanes (bench.py:
+ *    copy-in, compute, copy-out) and the null stream of whatever else lives in the process then fits the default four, and its lanes
+ *    overlap with no setting at all (58.1 -> 33.1 ms per step, profiles/r08_d_ab_bench.txt);
+ *  - a host with more lanes than that (the encoder binding: 12 + 4) still has to ask for more queues.  The runtime reads the variable when
+ *    it starts, i.e. at the process's first HIP call - so that is a call the HOST makes, knowingly, before that (the binding does, at
+ *    EbInitEncoder time: integration/svt_hook_me.c): svt_amd_runtime_env_defaults below.  The library itself never
+ *    touches the environment of the process that loaded it; a setting the user made wins. */
 extern "C" int svt_amd_host_wait_mode(int device_ordinal, int blocking)
 {
     HIP_TRY(hipSetDevice(device_ordinal));
@@ -192,7 +211,7 @@ __global__ void __launch_bounds__(256) k_copy_words(uint32_t *__restrict__ dst, 
 int svt_amd_upload_descriptors(SvtAmdContext *ctx, void *d_dst, const void *src, size_t bytes)
 {
     if (bytes > DESC_SLOT_BYTES || (bytes & 3)) {
-        HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
         return SVT_AMD_OK;
     }
     if (!ctx->h_desc_ring) {
@@ -206,9 +225,9 @@ int svt_amd_upload_descriptors(SvtAmdContext *ctx, void *d_dst, const void *src,
     uint8_t *slot = ctx->h_desc_ring + (size_t)i * DESC_SLOT_BYTES;
     memcpy(slot, src, bytes);
     const uint32_t n = (uint32_t)(bytes >> 2);
-    hipLaunchKernelGGL(k_copy_words, dim3((n + 255) / 256 > 64 ? 64 : (n + 255) / 256), dim3(256), 0, ctx->stream, (uint32_t *)d_dst, (const uint32_t *)slot, n);
+    hipLaunchKernelGGL(k_copy_words, dim3((n + 255) / 256 > 64 ? 64 : (n + 255) / 256), dim3(256), 0, svt_amd_ctx_stream(ctx), (uint32_t *)d_dst, (const uint32_t *)slot, n);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ctx->ev_desc[i], ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_desc[i], svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -326,7 +345,7 @@ int svt_amd_stamp_begin(SvtAmdContext *ctx, int cls)
         }
     }
     ctx->stamps[ctx->num_stamps].cls = cls;
-    HIP_TRY(hipEventRecord(ctx->stamps[ctx->num_stamps].a, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->stamps[ctx->num_stamps].a, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -334,7 +353,7 @@ int svt_amd_stamp_end(SvtAmdContext *ctx)
 {
     if (!ctx->timer_armed)
         return SVT_AMD_OK;
-    HIP_TRY(hipEventRecord(ctx->stamps[ctx->num_stamps].b, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->stamps[ctx->num_stamps].b, svt_amd_ctx_stream(ctx)));
     ctx->num_stamps++;
     return SVT_AMD_OK;
 }
@@ -344,10 +363,10 @@ extern "C" int svt_amd_timer_begin(SvtAmdContext *ctx)
     if (!ctx)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* stamps of a previous window may still be pending */
+    HIP_TRY(svt_amd_ctx_sync(ctx)); /* stamps of a previous window may still be pending */
     ctx->num_stamps = 0;
     ctx->timer_armed = 1;
-    HIP_TRY(hipEventRecord(ctx->ev_begin, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_begin, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -355,7 +374,7 @@ extern "C" int svt_amd_timer_end(SvtAmdContext *ctx, float *elapsed_ms)
 {
     if (!ctx || !elapsed_ms)
         return SVT_AMD_ERR_BAD_PARAM;
-    HIP_TRY(hipEventRecord(ctx->ev_end, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_end, svt_amd_ctx_stream(ctx)));
     HIP_TRY(hipEventSynchronize(ctx->ev_end));
     HIP_TRY(hipEventElapsedTime(elapsed_ms, ctx->ev_begin, ctx->ev_end));
     ctx->timer_armed = 0;
@@ -389,7 +408,11 @@ extern "C" int svt_amd_synchronize(SvtAmdContext *ctx)
 {
     if (!ctx)
         return SVT_AMD_ERR_BAD_PARAM;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx)); /* a context that never got a stream has nothing queued */
+    if (ctx->stream_failed) {
+        svt_amd_set_error("svt_amd_synchronize: the context's stream could not be made");
+        return SVT_AMD_ERR_DEVICE;
+    }
     return SVT_AMD_OK;
 }
 
@@ -407,7 +430,7 @@ extern "C" int svt_amd_device_free(SvtAmdContext *ctx, void *d_ptr)
     if (!ctx)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     HIP_TRY(hipFree(d_ptr));
     return SVT_AMD_OK;
 }
@@ -416,8 +439,12 @@ extern "C" int svt_amd_device_upload(SvtAmdContext *ctx, void *d_dst, const void
     if (!ctx || !d_dst || !src)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!svt_amd_ctx_has_stream(ctx)) { /* nothing of this context to be ordered behind: a plain copy, and the context stays without a stream */
+        HIP_TRY(hipMemcpy(d_dst, src, bytes, hipMemcpyHostToDevice));
+        return SVT_AMD_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_device_copy(SvtAmdContext *ctx, void *d_dst, const void *d_src, size_t bytes)
@@ -425,8 +452,12 @@ extern "C" int svt_amd_device_copy(SvtAmdContext *ctx, void *d_dst, const void *
     if (!ctx || !d_dst || !d_src)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!svt_amd_ctx_has_stream(ctx)) {
+        HIP_TRY(hipMemcpy(d_dst, d_src, bytes, hipMemcpyDeviceToDevice));
+        return SVT_AMD_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_device_download(SvtAmdContext *ctx, void *dst, const void *d_src, size_t bytes)
@@ -434,8 +465,12 @@ extern "C" int svt_amd_device_download(SvtAmdContext *ctx, void *dst, const void
     if (!ctx || !dst || !d_src)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!svt_amd_ctx_has_stream(ctx)) {
+        HIP_TRY(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
+        return SVT_AMD_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 
@@ -445,7 +480,7 @@ extern "C" int svt_amd_device_upload_async(SvtAmdContext *ctx, void *d_dst, cons
     if (!ctx || !d_dst || !src)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_device_download_async(SvtAmdContext *ctx, void *dst, const void *d_src, size_t bytes)
@@ -453,7 +488,7 @@ extern "C" int svt_amd_device_download_async(SvtAmdContext *ctx, void *dst, cons
     if (!ctx || !dst || !d_src)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_host_alloc(SvtAmdContext *ctx, size_t bytes, void **h_ptr)
@@ -610,10 +645,10 @@ extern "C" int svt_amd_picture_upload(SvtAmdContext *ctx, int slot, const uint8_
     DevPicture *s = &ctx->slots[slot];
     if ((size_t)width * height > s->staging_bytes)
         return SVT_AMD_ERR_BAD_PARAM;
-    HIP_TRY(hipMemcpy2DAsync(s->d_staging, width, luma, stride, width, height, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpy2DAsync(s->d_staging, width, luma, stride, width, height, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     /* the caller owns `luma` and may release it as soon as we return (the reference
      * copies in EbH265EncSendPicture, EbEncHandle.c:3329): wait for the H2D copy */
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return svt_amd_picture_upload_device(ctx, slot, s->d_staging, width, width, height);
 }
 
@@ -633,7 +668,7 @@ extern "C" int svt_amd_picture_read_plane(SvtAmdContext *ctx, int slot, int whic
     if (dst_capacity < (size_t)w * rows)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     HIP_TRY(hipMemcpy2D(dst, w, p->origin - (size_t)p->pad * p->pitch - p->pad, (size_t)p->pitch, w, rows,
                         hipMemcpyDeviceToHost));
     *out_stride = w;
@@ -691,7 +726,7 @@ static void slot_records_reset(DevPicture *s)
 static int slot_records_before_write(SvtAmdContext *ctx, DevPicture *s)
 {
     if (__atomic_load_n(&s->md_read_pending, __ATOMIC_ACQUIRE)) {
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, s->ev_md_read, 0));
+        HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), s->ev_md_read, 0));
         __atomic_store_n(&s->md_read_pending, 0, __ATOMIC_RELEASE);
     }
     return SVT_AMD_OK;
@@ -709,14 +744,14 @@ static int me_records_written(SvtAmdContext *ctx, int slot, const SvtAmdMeParams
             s->me_cov[i >> 6] |= 1ull << (i & 63), s->me_cov_count++;
     covered = s->me_cov_count;
     __atomic_store_n(&s->me_cov_lock, 0, __ATOMIC_RELEASE);
-    HIP_TRY(hipEventRecord(s->ev_me, ctx->stream));
+    HIP_TRY(hipEventRecord(s->ev_me, svt_amd_ctx_stream(ctx)));
     __atomic_store_n(&s->me_lcus, covered >= n ? n : 0u, __ATOMIC_RELEASE);
     return SVT_AMD_OK;
 }
 static int ois_records_written(SvtAmdContext *ctx, int slot, const SvtAmdOisParams *p)
 {
     DevPicture *s = &ctx->slots[slot];
-    HIP_TRY(hipEventRecord(s->ev_ois, ctx->stream));
+    HIP_TRY(hipEventRecord(s->ev_ois, svt_amd_ctx_stream(ctx)));
     __atomic_store_n(&s->ois_lcus, ((p->luma_width + 63u) / 64u) * ((p->luma_height + 63u) / 64u), __ATOMIC_RELEASE);
     return SVT_AMD_OK;
 }
@@ -805,7 +840,7 @@ extern "C" int svt_amd_debug_me_phase_profile(SvtAmdContext *ctx, size_t workgro
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     if (!out) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream)); /* a launch armed earlier may still write its stamps */
+        HIP_TRY(svt_amd_ctx_sync(ctx)); /* a launch armed earlier may still write its stamps */
         if (ctx->d_dbg)
             (void)hipFree(ctx->d_dbg);
         ctx->d_dbg = NULL;
@@ -816,7 +851,7 @@ extern "C" int svt_amd_debug_me_phase_profile(SvtAmdContext *ctx, size_t workgro
     }
     if (!ctx->d_dbg || workgroups > ctx->dbg_slots)
         return SVT_AMD_ERR_BAD_PARAM;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     HIP_TRY(hipMemcpy(out, ctx->d_dbg, workgroups * 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     (void)hipFree(ctx->d_dbg);
     ctx->d_dbg = NULL;
@@ -844,8 +879,8 @@ extern "C" int svt_amd_me_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtAmd
     DevPicture *c = &ctx->slots[cur_slot];
     const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
     HIP_TRY(hipMemcpyAsync(out, c->d_me_out, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyDeviceToHost,
-                           ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+                           svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 
@@ -860,7 +895,7 @@ extern "C" int svt_amd_me_picture_fetch_async(SvtAmdContext *ctx, int cur_slot, 
     HIP_TRY(hipSetDevice(ctx->device));
     DevPicture *c = &ctx->slots[cur_slot];
     const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(out, c->d_me_out, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_me_out, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_ois_picture_fetch_async(SvtAmdContext *ctx, int cur_slot, SvtAmdOisLcuResult *out)
@@ -873,7 +908,7 @@ extern "C" int svt_amd_ois_picture_fetch_async(SvtAmdContext *ctx, int cur_slot,
     HIP_TRY(hipSetDevice(ctx->device));
     DevPicture *c = &ctx->slots[cur_slot];
     const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(out, c->d_ois_out, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_ois_out, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -887,7 +922,7 @@ extern "C" int svt_amd_lane_event_record(SvtAmdContext *lane, int index)
     HIP_TRY(hipSetDevice(lane->device));
     if (!lane->ev_user[index])
         HIP_TRY(hipEventCreateWithFlags(&lane->ev_user[index], hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(lane->ev_user[index], lane->stream));
+    HIP_TRY(hipEventRecord(lane->ev_user[index], svt_amd_ctx_stream(lane)));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_lane_event_wait(SvtAmdContext *lane, SvtAmdContext *source, int index)
@@ -896,7 +931,7 @@ extern "C" int svt_amd_lane_event_wait(SvtAmdContext *lane, SvtAmdContext *sourc
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(lane->device));
     if (source->ev_user[index])
-        HIP_TRY(hipStreamWaitEvent(lane->stream, source->ev_user[index], 0));
+        HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(lane), source->ev_user[index], 0));
     return SVT_AMD_OK;
 }
 
@@ -904,23 +939,46 @@ extern "C" int svt_amd_lane_event_wait(SvtAmdContext *lane, SvtAmdContext *sourc
  * What the host side of the boundary reads (MeCuResults_t x 85; the OIS candidates the picture's path can write: MAX_OIS_0 / _1 /
  * _2 of EbCodingUnit.h:59-61) is 5,188 of the 9,628 bytes per LCU at BASELINE configs[2]; the device packs it (one pass over the
  * records, ~10 us per 4K picture) so that the D2H copy - the longest stage of the pipelined front half - moves only that. */
-__global__ void __launch_bounds__(256) k_pack_me(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, int nlcu)
+/* One launch packs a whole batch: blockIdx.y is the picture, `tab` names its source records (PackSrc per picture, through
+ * svt_amd_upload_descriptors), picture i lands at out + i * words per picture.  tab == NULL: one picture, read from `one`. */
+__global__ void __launch_bounds__(256) k_pack_me(const PackSrc *__restrict__ tab, const uint32_t *__restrict__ one, uint32_t *__restrict__ out, int nlcu)
 {
     constexpr int IN = sizeof(SvtAmdMeLcuResult) / 4, OUT = SVT_AMD_ME_PU_COUNT * sizeof(SvtAmdMeCuResult) / 4;
+    const uint32_t *__restrict__ in = tab ? tab[blockIdx.y].me : one;
     const int i = blockIdx.x * 256 + threadIdx.x, lcu = i / OUT, k = i - lcu * OUT;
     if (lcu < nlcu)
-        out[(size_t)lcu * OUT + k] = in[(size_t)lcu * IN + k];
+        out[((size_t)blockIdx.y * nlcu + lcu) * OUT + k] = in[(size_t)lcu * IN + k];
 }
-__global__ void __launch_bounds__(256) k_pack_ois(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, int nlcu, int nc)
+/* A workgroup per LCU.  The lane holds the candidate index (kw = 1 << kshift lanes per CU, kw >= nc; the lanes beyond nc idle) and the
+ * workgroup walks the CUs 256 / kw at a time, so no thread divides: the records are only dword-aligned, the copies stay dword copies. */
+__global__ void __launch_bounds__(256) k_pack_ois(const PackSrc *__restrict__ tab, const uint32_t *__restrict__ one, uint32_t *__restrict__ out, int nlcu, int nc, int kshift)
 {
     constexpr int IN = sizeof(SvtAmdOisLcuResult) / 4, TAIL = 22; /* total_intra_luma_mode[85] + pad = 88 bytes */
-    const int per = SVT_AMD_ME_PU_COUNT * nc + TAIL;
-    const int i = blockIdx.x * 256 + threadIdx.x, lcu = i / per, e = i - lcu * per;
-    if (lcu >= nlcu)
-        return;
-    const int cu = e / nc, k = e - cu * nc;
-    out[(size_t)lcu * per + e] =
-        e < SVT_AMD_ME_PU_COUNT * nc ? in[(size_t)lcu * IN + cu * SVT_AMD_OIS_MAX_CAND + k] : in[(size_t)lcu * IN + SVT_AMD_ME_PU_COUNT * SVT_AMD_OIS_MAX_CAND + (e - SVT_AMD_ME_PU_COUNT * nc)];
+    const int per = SVT_AMD_ME_PU_COUNT * nc + TAIL, lcu = blockIdx.x;
+    const uint32_t *__restrict__ src = (tab ? tab[blockIdx.y].ois : one) + (size_t)lcu * IN;
+    uint32_t *__restrict__ dst = out + ((size_t)blockIdx.y * nlcu + lcu) * per;
+    const int k = threadIdx.x & ((1 << kshift) - 1);
+    if (k < nc)
+        for (int cu = threadIdx.x >> kshift; cu < SVT_AMD_ME_PU_COUNT; cu += 256 >> kshift)
+            dst[cu * nc + k] = src[cu * SVT_AMD_OIS_MAX_CAND + k];
+    if (threadIdx.x < TAIL)
+        dst[SVT_AMD_ME_PU_COUNT * nc + threadIdx.x] = src[SVT_AMD_ME_PU_COUNT * SVT_AMD_OIS_MAX_CAND + threadIdx.x];
+}
+/* n pictures of nlcu LCUs: tab (device, n entries) or one picture's records -> d_me / d_ois (either may be NULL) */
+static int launch_pack(SvtAmdContext *ctx, const PackSrc *tab, const PackSrc &one, int n, int nlcu, int candidates, void *d_me, void *d_ois)
+{
+    if (d_me) {
+        const int k = nlcu * (int)(SVT_AMD_ME_PU_COUNT * sizeof(SvtAmdMeCuResult) / 4);
+        hipLaunchKernelGGL(k_pack_me, dim3((k + 255) / 256, n), dim3(256), 0, svt_amd_ctx_stream(ctx), tab, one.me, (uint32_t *)d_me, nlcu);
+    }
+    if (d_ois) {
+        int kshift = 0;
+        while ((1 << kshift) < candidates)
+            kshift++;
+        hipLaunchKernelGGL(k_pack_ois, dim3(nlcu, n), dim3(256), 0, svt_amd_ctx_stream(ctx), tab, one.ois, (uint32_t *)d_ois, nlcu, candidates, kshift);
+    }
+    HIP_TRY(hipGetLastError());
+    return SVT_AMD_OK;
 }
 static_assert(sizeof(SvtAmdOisLcuResult) == (SVT_AMD_ME_PU_COUNT * SVT_AMD_OIS_MAX_CAND + 22) * 4, "OIS record layout");
 static_assert(sizeof(SvtAmdMeCuResult) == 24 && offsetof(SvtAmdMeLcuResult, pu) == 0, "ME record layout");
@@ -933,7 +991,7 @@ extern "C" int svt_amd_ois_compact_candidates(const SvtAmdOisParams *p)
 static int slot_pack_buffer(SvtAmdContext *ctx, DevPicture *c, size_t bytes, uint8_t **out)
 {
     if (bytes > c->pack_bytes) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(svt_amd_ctx_sync(ctx));
         if (c->d_pack)
             (void)hipFree(c->d_pack);
         c->d_pack = nullptr, c->pack_bytes = 0;
@@ -961,9 +1019,9 @@ extern "C" int svt_amd_me_picture_fetch_compact_async(SvtAmdContext *ctx, int cu
     if ((rc = slot_pack_buffer(ctx, c, pack_me_bytes(nlcu) + (size_t)nlcu * sizeof(SvtAmdOisLcuResult), &d)) != 0)
         return rc;
     const int n = nlcu * (int)(SVT_AMD_ME_PU_COUNT * sizeof(SvtAmdMeCuResult) / 4);
-    hipLaunchKernelGGL(k_pack_me, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_me_out, (uint32_t *)d, nlcu);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, d, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = launch_pack(ctx, nullptr, PackSrc{(const uint32_t *)c->d_me_out, nullptr}, 1, nlcu, 1, d, nullptr)) != 0)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, d, (size_t)n * 4, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -982,9 +1040,9 @@ extern "C" int svt_amd_ois_picture_fetch_compact_async(SvtAmdContext *ctx, int c
         return rc;
     d += pack_me_bytes(nlcu);
     const int n = nlcu * (SVT_AMD_ME_PU_COUNT * candidates + 22);
-    hipLaunchKernelGGL(k_pack_ois, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_ois_out, (uint32_t *)d, nlcu, candidates);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, d, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = launch_pack(ctx, nullptr, PackSrc{nullptr, (const uint32_t *)c->d_ois_out}, 1, nlcu, candidates, nullptr, d)) != 0)
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, d, (size_t)n * 4, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -1002,7 +1060,7 @@ extern "C" int svt_amd_records_pack_batch_async(SvtAmdContext *ctx, const int *s
     HIP_TRY(hipSetDevice(ctx->device));
     const DevPicture *c0 = &ctx->slots[slots[0]];
     const int nlcu = ((c0->width + 63) / 64) * ((c0->height + 63) / 64);
-    const size_t meb = (size_t)nlcu * SVT_AMD_ME_PU_COUNT * sizeof(SvtAmdMeCuResult), oisb = (size_t)nlcu * SVT_AMD_OIS_COMPACT_BYTES(candidates);
+    static thread_local PackSrc tab[SVT_AMD_MAX_BATCH];
     for (int i = 0; i < n; i++) {
         if ((rc = check_slot(ctx, slots[i])) != 0)
             return rc;
@@ -1011,19 +1069,11 @@ extern "C" int svt_amd_records_pack_batch_async(SvtAmdContext *ctx, const int *s
             svt_amd_set_error("svt_amd_records_pack_batch_async: pictures of different sizes in one batch");
             return SVT_AMD_ERR_BAD_PARAM;
         }
-        if (d_me) {
-            const int k = nlcu * (int)(SVT_AMD_ME_PU_COUNT * sizeof(SvtAmdMeCuResult) / 4);
-            hipLaunchKernelGGL(k_pack_me, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_me_out,
-                               (uint32_t *)((uint8_t *)d_me + meb * (size_t)i), nlcu);
-        }
-        if (d_ois) {
-            const int k = nlcu * (SVT_AMD_ME_PU_COUNT * candidates + 22);
-            hipLaunchKernelGGL(k_pack_ois, dim3((k + 255) / 256), dim3(256), 0, ctx->stream, (const uint32_t *)c->d_ois_out,
-                               (uint32_t *)((uint8_t *)d_ois + oisb * (size_t)i), nlcu, candidates);
-        }
+        tab[i].me = (const uint32_t *)c->d_me_out, tab[i].ois = (const uint32_t *)c->d_ois_out;
     }
-    HIP_TRY(hipGetLastError());
-    return SVT_AMD_OK;
+    if ((rc = svt_amd_upload_descriptors(ctx, ctx->d_pack_src, tab, sizeof(PackSrc) * (size_t)n)) != 0)
+        return rc;
+    return launch_pack(ctx, (const PackSrc *)ctx->d_pack_src, PackSrc{nullptr, nullptr}, n, nlcu, candidates, d_me, d_ois);
 }
 
 extern "C" int svt_amd_me_picture(SvtAmdContext *ctx, const SvtAmdMeParams *params, int cur_slot,
@@ -1122,8 +1172,8 @@ extern "C" int svt_amd_ois_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtAm
     HIP_TRY(hipSetDevice(ctx->device));
     DevPicture *c = &ctx->slots[cur_slot];
     const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(out, c->d_ois_out, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, c->d_ois_out, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 
@@ -1139,8 +1189,8 @@ extern "C" int svt_amd_ois_picture(SvtAmdContext *ctx, const SvtAmdOisParams *pa
     if (me) {
         HIP_TRY(hipSetDevice(ctx->device));
         const int nlcu = ((params->luma_width + 63) / 64) * ((params->luma_height + 63) / 64);
-        HIP_TRY(hipMemcpyAsync(ctx->d_me_scratch, me, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream)); /* `me` may be freed by the caller on return of a later call */
+        HIP_TRY(hipMemcpyAsync(ctx->d_me_scratch, me, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+        HIP_TRY(svt_amd_ctx_sync(ctx)); /* `me` may be freed by the caller on return of a later call */
         d_me = ctx->d_me_scratch;
     }
     rc = ois_launch(ctx, params, cur_slot, d_me);
@@ -1175,10 +1225,10 @@ extern "C" int svt_amd_picture_upload_async(SvtAmdContext *ctx, int slot, const 
     else
         for (uint32_t y = 0; y < height; y++)
             memcpy(s->h_staging + (size_t)y * width, luma + (size_t)y * stride, width);
-    HIP_TRY(hipMemcpyAsync(s->d_staging, s->h_staging, (size_t)width * height, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s->d_staging, s->h_staging, (size_t)width * height, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     if ((rc = svt_amd_launch_prep(ctx, s, s->d_staging, width)) != 0)
         return rc;
-    HIP_TRY(hipEventRecord(s->ev_ready, ctx->stream));
+    HIP_TRY(hipEventRecord(s->ev_ready, svt_amd_ctx_stream(ctx)));
     slot_records_reset(s); /* the records in the slot's buffers are the previous picture's */
     s->valid = 1;
     return SVT_AMD_OK;
@@ -1191,7 +1241,7 @@ extern "C" int svt_amd_picture_publish(SvtAmdContext *ctx, int slot)
     if (rc)
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipEventRecord(ctx->slots[slot].ev_ready, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->slots[slot].ev_ready, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -1216,20 +1266,20 @@ extern "C" int svt_amd_frontend_submit(SvtAmdContext *ctx, const SvtAmdFrontendJ
     if (!ctx->h_ois)
         HIP_TRY(hipHostMalloc((void **)&ctx->h_ois, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipHostMallocDefault));
     /* pictures may have been prepared on another lane's stream */
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, c->ev_ready, 0));
+    HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), c->ev_ready, 0));
     const int pn = ((c->width + 63) / 64) * ((c->height + 63) / 64);
     if (job->has_me) {
         for (int l = 0; l < job->me.num_lists && l < 2; l++) {
             if ((rc = check_slot(ctx, job->ref_slot[l])) != 0)
                 return rc;
-            HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->slots[job->ref_slot[l]].ev_ready, 0));
+            HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), ctx->slots[job->ref_slot[l]].ev_ready, 0));
         }
         if ((rc = svt_amd_me_picture_launch(ctx, &job->me, job->cur_slot, job->ref_slot)) != 0)
             return rc;
         if (job->compact)
             rc = svt_amd_me_picture_fetch_compact_async(ctx, job->cur_slot, (SvtAmdMeCuResult *)ctx->h_me);
         else
-            HIP_TRY(hipMemcpyAsync(ctx->h_me, c->d_me_out, (size_t)pn * sizeof(SvtAmdMeLcuResult), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(ctx->h_me, c->d_me_out, (size_t)pn * sizeof(SvtAmdMeLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
         if (rc)
             return rc;
     }
@@ -1239,11 +1289,11 @@ extern "C" int svt_amd_frontend_submit(SvtAmdContext *ctx, const SvtAmdFrontendJ
         if (job->compact)
             rc = svt_amd_ois_picture_fetch_compact_async(ctx, job->cur_slot, svt_amd_ois_compact_candidates(&job->ois), ctx->h_ois);
         else
-            HIP_TRY(hipMemcpyAsync(ctx->h_ois, c->d_ois_out, (size_t)pn * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(ctx->h_ois, c->d_ois_out, (size_t)pn * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
         if (rc)
             return rc;
     }
-    HIP_TRY(hipEventRecord(ctx->ev_done, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_done, svt_amd_ctx_stream(ctx)));
     ctx->frontend_busy = 1;
     return SVT_AMD_OK;
 }
@@ -1357,7 +1407,7 @@ extern "C" int svt_amd_zz_sad_picture(SvtAmdContext *ctx, int cur_slot, int prev
     SvtAmdZzLcu *d_out = (SvtAmdZzLcu *)ctx->d_me_scratch;
     if ((rc = svt_amd_launch_zz_sad(ctx, c, p, d_out)) != 0)
         return rc;
-    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)nlcu * sizeof(SvtAmdZzLcu), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)nlcu * sizeof(SvtAmdZzLcu), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }

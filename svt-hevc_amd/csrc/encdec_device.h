@@ -62,7 +62,7 @@ static inline int ep_picture_written(SvtAmdContext *ctx, SvtAmdEncDecPicture *pi
         pic->ev_written = nullptr;
         return SVT_AMD_ERR_RESOURCES;
     }
-    if (hipEventRecord(pic->ev_written, ctx->stream) != hipSuccess)
+    if (hipEventRecord(pic->ev_written, svt_amd_ctx_stream(ctx)) != hipSuccess)
         return SVT_AMD_ERR_DEVICE;
     pic->written = true;
     return SVT_AMD_OK;

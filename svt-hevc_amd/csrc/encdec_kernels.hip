@@ -99,10 +99,10 @@ int svt_amd_ep_launch_behind_md(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, co
     int grid = inter ? 512 : ((wl + 1) / 2 < hl ? (wl + 1) / 2 : hl) * (tiles > 0 ? tiles : 1) + 1;
     grid = grid > n_active ? n_active : grid;
     if (pic->d.bps == 2)
-        hipLaunchKernelGGL(k_encode_picture<uint16_t>, dim3((unsigned)grid), dim3(256), 0, ctx->stream, pic->d, (const SvtAmdLcuWork16 *)d_works, (SvtAmdLcuResult16 *)d_results, n_active, wl,
+        hipLaunchKernelGGL(k_encode_picture<uint16_t>, dim3((unsigned)grid), dim3(256), 0, svt_amd_ctx_stream(ctx), pic->d, (const SvtAmdLcuWork16 *)d_works, (SvtAmdLcuResult16 *)d_results, n_active, wl,
                            pic->d_sync, pic->d_sync + 1, d_order, pic->epoch);
     else
-        hipLaunchKernelGGL(k_encode_picture<uint8_t>, dim3((unsigned)grid), dim3(256), 0, ctx->stream, pic->d, (const SvtAmdLcuWork *)d_works, (SvtAmdLcuResult *)d_results, n_active, wl,
+        hipLaunchKernelGGL(k_encode_picture<uint8_t>, dim3((unsigned)grid), dim3(256), 0, svt_amd_ctx_stream(ctx), pic->d, (const SvtAmdLcuWork *)d_works, (SvtAmdLcuResult *)d_results, n_active, wl,
                            pic->d_sync, pic->d_sync + 1, d_order, pic->epoch);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -177,8 +177,8 @@ extern "C" int svt_amd_encdec_picture_begin(SvtAmdContext *ctx, SvtAmdEncDecPict
     if (!ctx || !pic)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, ctx->stream)); /* nothing coded yet */
-    HIP_TRY(hipStreamSynchronize(ctx->stream));                                   /* other lanes may encode the first LCU */
+    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, svt_amd_ctx_stream(ctx))); /* nothing coded yet */
+    HIP_TRY(svt_amd_ctx_sync(ctx));                                   /* other lanes may encode the first LCU */
     pic->deblocked = pic->sao_done = false;
     return SVT_AMD_OK;
 }
@@ -188,7 +188,7 @@ extern "C" int svt_amd_encdec_picture_destroy(SvtAmdContext *ctx, SvtAmdEncDecPi
     if (!ctx || !pic)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    (void)hipStreamSynchronize(ctx->stream);
+    (void)svt_amd_ctx_sync(ctx);
     for (int k = 0; k < 3; k++)
         if (pic->d.rec[k])
             (void)hipFree(pic->d.rec[k]);
@@ -249,7 +249,7 @@ extern "C" int svt_amd_encdec_picture_set_inter(SvtAmdContext *ctx, SvtAmdEncDec
     }
     HIP_TRY(hipSetDevice(ctx->device));
     memcpy(pic->h_cost, cost, sizeof(*cost)); /* a pageable source would make the copy a staged one the runtime completes inside the call, behind whatever its queue runs */
-    HIP_TRY(hipMemcpyAsync(pic->d_cost, pic->h_cost, sizeof(*cost), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(pic->d_cost, pic->h_cost, sizeof(*cost), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     pic->has_cost = true;
     return SVT_AMD_OK;
 }
@@ -309,13 +309,13 @@ static int encode_lcus(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typen
     int rc = svt_amd_ctx_scratch(ctx, wba + rb, &d);
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(d, works, wb, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_encode_lcu<T>, dim3((unsigned)n), dim3(256), 0, ctx->stream, pic->d, (const WorkT *)d, (ResultT *)(d + wba));
+    HIP_TRY(hipMemcpyAsync(d, works, wb, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    hipLaunchKernelGGL(k_encode_lcu<T>, dim3((unsigned)n), dim3(256), 0, svt_amd_ctx_stream(ctx), pic->d, (const WorkT *)d, (ResultT *)(d + wba));
     HIP_TRY(hipGetLastError());
     if ((rc = ep_picture_written(ctx, pic)) != 0)
         return rc;
-    HIP_TRY(hipMemcpyAsync(results, d + wba, rb, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(results, d + wba, rb, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_encode_lcus(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork *works, int n, SvtAmdLcuResult *results)
@@ -371,8 +371,8 @@ static int encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const ty
         n_active = (int)order.size();
         if (!pic->d_order_rect && hipMalloc((void **)&pic->d_order_rect, sizeof(unsigned) * (size_t)n) != hipSuccess)
             return SVT_AMD_ERR_RESOURCES;
-        HIP_TRY(hipMemcpyAsync(pic->d_order_rect, order.data(), sizeof(unsigned) * order.size(), hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream)); /* the list is a local */
+        HIP_TRY(hipMemcpyAsync(pic->d_order_rect, order.data(), sizeof(unsigned) * order.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+        HIP_TRY(svt_amd_ctx_sync(ctx)); /* the list is a local */
         d_order = pic->d_order_rect;
     }
     if (!d_works) {
@@ -397,15 +397,15 @@ static int encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const ty
         int rc = svt_amd_ctx_scratch(ctx, wba + rb, &d);
         if (rc)
             return rc;
-        HIP_TRY(hipMemcpyAsync(d, works, wb, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d, works, wb, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
         d_works = (const WorkT *)d, d_results = (ResultT *)(d + wba);
         if (rect) /* the other ranks' LCUs: nothing coded here (the filters behind the encode pass read every LCU's flags) */
-            HIP_TRY(hipMemsetAsync(d + wba, 0, rb, ctx->stream));
+            HIP_TRY(hipMemsetAsync(d + wba, 0, rb, svt_amd_ctx_stream(ctx)));
     }
     pic->epoch++;
     pic->deblocked = pic->sao_done = false;
-    HIP_TRY(hipMemsetAsync(pic->d_sync, 0, sizeof(unsigned), ctx->stream));              /* ticket counter */
-    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, ctx->stream));          /* nothing coded yet */
+    HIP_TRY(hipMemsetAsync(pic->d_sync, 0, sizeof(unsigned), svt_amd_ctx_stream(ctx)));              /* ticket counter */
+    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, svt_amd_ctx_stream(ctx)));          /* nothing coded yet */
     /* persistent grid = the widest wavefront (an LCU row advances two LCUs behind the row above) of every tile that can run on its
      * own: more workgroups would only poll, and they would hold the CUs other pictures' launches could use */
     const int hl = (pic->d.height + 63) / 64;
@@ -413,7 +413,7 @@ static int encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const ty
     if (free_lcus * 2 > n) /* a P / B picture: most LCUs have no intra unit and wait for nobody - as many workgroups as the device holds */
         grid = 512;
     grid = grid > n_active ? n_active : grid > 512 ? 512 : grid;
-    hipLaunchKernelGGL(k_encode_picture<T>, dim3((unsigned)grid), dim3(256), 0, ctx->stream, pic->d, d_works, d_results, n_active, wl, pic->d_sync, pic->d_sync + 1, d_order, pic->epoch);
+    hipLaunchKernelGGL(k_encode_picture<T>, dim3((unsigned)grid), dim3(256), 0, svt_amd_ctx_stream(ctx), pic->d, d_works, d_results, n_active, wl, pic->d_sync, pic->d_sync + 1, d_order, pic->epoch);
     HIP_TRY(hipGetLastError());
     {
         const int rcw = ep_picture_written(ctx, pic);
@@ -421,7 +421,7 @@ static int encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const ty
             return rcw;
     }
     if (results)
-        HIP_TRY(hipMemcpyAsync(results, d_results, sizeof(ResultT) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(results, d_results, sizeof(ResultT) * (size_t)n, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 
@@ -432,7 +432,7 @@ extern "C" int svt_amd_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *p
     int rc = encode_picture<uint8_t>(ctx, pic, works, results, nullptr, nullptr, 0);
     if (rc)
         return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_encode_picture16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork16 *works, SvtAmdLcuResult16 *results)
@@ -442,7 +442,7 @@ extern "C" int svt_amd_encode_picture16(SvtAmdContext *ctx, SvtAmdEncDecPicture 
     int rc = encode_picture<uint16_t>(ctx, pic, works, results, nullptr, nullptr, 0);
     if (rc)
         return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 
@@ -457,7 +457,7 @@ extern "C" int svt_amd_encode_picture_rect(SvtAmdContext *ctx, SvtAmdEncDecPictu
     int rc = encode_picture<uint8_t>(ctx, pic, works, results, nullptr, nullptr, 0, 0, rect);
     if (rc)
         return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_encode_picture_rect16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork16 *works, SvtAmdLcuResult16 *results,
@@ -468,7 +468,7 @@ extern "C" int svt_amd_encode_picture_rect16(SvtAmdContext *ctx, SvtAmdEncDecPic
     int rc = encode_picture<uint16_t>(ctx, pic, works, results, nullptr, nullptr, 0, 0, rect);
     if (rc)
         return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 
@@ -565,10 +565,10 @@ extern "C" int svt_amd_encdec_picture_import(SvtAmdContext *ctx, SvtAmdEncDecPic
     if (rc)
         return rc;
     /* behind whatever the owner's stream still has queued on the source picture (its encode pass / filters run on another context, possibly another device) */
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, from->ev_written, 0));
+    HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), from->ev_written, 0));
     uint8_t *const *stage = from->sao_done ? from->fin : from->deblocked ? from->dbk : from->d.rec;
     for (int p = 0; p < 3; p++) /* hipMemcpyDefault: the source may live on a peer device */
-        HIP_TRY(hipMemcpyAsync(pic->fin[p], stage[p], pic->plane_bytes[p], hipMemcpyDefault, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(pic->fin[p], stage[p], pic->plane_bytes[p], hipMemcpyDefault, svt_amd_ctx_stream(ctx)));
     pic->deblocked = pic->sao_done = true;
     pic->epoch++; /* the per-LCU completion marks of the receiver's own earlier picture do not describe this one */
     return ep_picture_written(ctx, pic);
@@ -656,11 +656,11 @@ static int picture_deblock(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const t
     if (rc)
         return rc;
     uint8_t *d_map = d, *d_cbf = d_map + b_map, *d_qp = d_cbf + b_cbf, *d_edge = d_qp + b_qp, *d_bsv = d_edge + b_edge, *d_bsh = d_bsv + b_bs;
-    HIP_TRY(hipMemcpyAsync(d_map, map.data(), map.size() * sizeof(SvtAmdCuMapEntry), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_cbf, cbf.data(), cbf.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_qp, qp.data(), qp.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_edge, edge.data(), edge.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* the host vectors back the copies */
+    HIP_TRY(hipMemcpyAsync(d_map, map.data(), map.size() * sizeof(SvtAmdCuMapEntry), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_cbf, cbf.data(), cbf.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_qp, qp.data(), qp.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_edge, edge.data(), edge.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx)); /* the host vectors back the copies */
     if ((rc = svt_amd_bs_picture(ctx, (const SvtAmdCuMapEntry *)d_map, d_cbf, w, h, prm->slice_type, prm->ref_poc[0], prm->ref_poc[1], d_edge, d_bsv,
                                  d_bsh)) != 0)
         return rc;
@@ -673,7 +673,7 @@ static int picture_deblock(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const t
             svt_amd_set_error("hipMalloc (deblocked picture) failed");
             return SVT_AMD_ERR_RESOURCES;
         }
-        HIP_TRY(hipMemcpyAsync(pic->dbk[k], pic->d.rec[k], pic->plane_bytes[k], hipMemcpyDeviceToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(pic->dbk[k], pic->d.rec[k], pic->plane_bytes[k], hipMemcpyDeviceToDevice, svt_amd_ctx_stream(ctx)));
     }
     if ((rc = svt_amd_dlf_picture(ctx, (int)sizeof(T), pic->dbk[0], pic->d.pitch[0], pic->dbk[1], pic->dbk[2], pic->d.pitch[1], w, h, d_bsv, d_bsh,
                                   d_qp, w8, prm->tc_offset, prm->beta_offset, prm->cb_qp_offset, prm->cr_qp_offset)) != 0)
@@ -686,9 +686,9 @@ static int picture_deblock(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const t
         if (outs[k]) {
             const uint32_t pw = k ? w / 2 : w, ph = k ? h / 2 : h;
             HIP_TRY(hipMemcpy2DAsync(outs[k], (size_t)pw * sizeof(T), pic->dbk[k], (size_t)pic->d.pitch[k] * sizeof(T), (size_t)pw * sizeof(T), ph,
-                                     hipMemcpyDeviceToHost, ctx->stream));
+                                     hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
         }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 
@@ -781,19 +781,19 @@ static int picture_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typen
     int64_t *d_cost = (int64_t *)q;
     q += b_cost;
     uint8_t *d_en = q, *d_follow = q + b_en;
-    HIP_TRY(hipMemcpyAsync(d_works, works, sizeof(WorkT) * nlcu, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_follow, follow.data(), nlcu, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_par, lp.data(), sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_works, works, sizeof(WorkT) * nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_follow, follow.data(), nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_par, lp.data(), sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     if (enable)
-        HIP_TRY(hipMemcpyAsync(d_en, enable, nlcu, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(d_stats[0], 0, 3 * b_stats, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* lp backs its copy */
+        HIP_TRY(hipMemcpyAsync(d_en, enable, nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemsetAsync(d_stats[0], 0, 3 * b_stats, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx)); /* lp backs its copy */
     const int pY = (int)pic->d.pitch[0], pC = (int)pic->d.pitch[1];
-    hipLaunchKernelGGL(k_ep_source_planes<T>, dim3(nlcu), dim3(256), 0, ctx->stream, (const WorkT *)d_works, (T *)d_src[0], (T *)d_src[1], (T *)d_src[2], pY, pC,
+    hipLaunchKernelGGL(k_ep_source_planes<T>, dim3(nlcu), dim3(256), 0, svt_amd_ctx_stream(ctx), (const WorkT *)d_works, (T *)d_src[0], (T *)d_src[1], (T *)d_src[2], pY, pC,
                        (int)w, (int)h);
     for (int k = 0; k < 3 && pic->deblocked; k++) {
         const int pw = k ? w / 2 : w, ph = k ? h / 2 : h;
-        hipLaunchKernelGGL(k_ep_sao_composite<T>, dim3((pw + 255) / 256, ph), dim3(256), 0, ctx->stream, (const T *)pic->dbk[k], (const T *)pic->d.rec[k],
+        hipLaunchKernelGGL(k_ep_sao_composite<T>, dim3((pw + 255) / 256, ph), dim3(256), 0, svt_amd_ctx_stream(ctx), (const T *)pic->dbk[k], (const T *)pic->d.rec[k],
                            (T *)d_cmp[k], k ? pC : pY, pw, ph, k ? 5 : 6, (int)wl, (const uint8_t *)d_follow);
     }
     HIP_TRY(hipGetLastError());
@@ -810,15 +810,15 @@ static int picture_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typen
     if (apply && (rc = svt_amd_sao_apply_picture(ctx, (int)sizeof(T), srcs, dsts, pic->d.pitch[0], pic->d.pitch[1], w, h, d_par, 1, 1)) != 0)
         return rc;
     if (lcu_out)
-        HIP_TRY(hipMemcpyAsync(lcu_out, d_par, sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(lcu_out, d_par, sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     void *outs[3] = {out_y, out_cb, out_cr};
     for (int k = 0; k < 3 && apply; k++)
         if (outs[k]) {
             const uint32_t pw = k ? w / 2 : w, ph = k ? h / 2 : h;
             HIP_TRY(hipMemcpy2DAsync(outs[k], (size_t)pw * sizeof(T), pic->fin[k], (size_t)pic->d.pitch[k] * sizeof(T), (size_t)pw * sizeof(T), ph,
-                                     hipMemcpyDeviceToHost, ctx->stream));
+                                     hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
         }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     pic->sao_done = pic->sao_done || apply;
     return ep_picture_written(ctx, pic);
 }
@@ -859,16 +859,16 @@ extern "C" int svt_amd_encdec_picture_reference(SvtAmdContext *ctx, SvtAmdEncDec
             pic->refp_bytes[k] = need;
         }
         if (bps == 1)
-            hipLaunchKernelGGL(k_ep_pad<uint8_t>, dim3((stride + 255) / 256, rows), dim3(256), 0, ctx->stream, (const uint8_t *)stage[k], (int)pic->d.pitch[k], pw, ph,
+            hipLaunchKernelGGL(k_ep_pad<uint8_t>, dim3((stride + 255) / 256, rows), dim3(256), 0, svt_amd_ctx_stream(ctx), (const uint8_t *)stage[k], (int)pic->d.pitch[k], pw, ph,
                                (uint8_t *)pic->refp[k], stride, ox, oy);
         else
-            hipLaunchKernelGGL(k_ep_pad<uint16_t>, dim3((stride + 255) / 256, rows), dim3(256), 0, ctx->stream, (const uint16_t *)stage[k], (int)pic->d.pitch[k], pw,
+            hipLaunchKernelGGL(k_ep_pad<uint16_t>, dim3((stride + 255) / 256, rows), dim3(256), 0, svt_amd_ctx_stream(ctx), (const uint16_t *)stage[k], (int)pic->d.pitch[k], pw,
                                ph, (uint16_t *)pic->refp[k], stride, ox, oy);
         if (outs[k])
-            HIP_TRY(hipMemcpyAsync(outs[k], pic->refp[k], need, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(outs[k], pic->refp[k], need, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* other lanes' pictures may read the planes right away */
+    HIP_TRY(svt_amd_ctx_sync(ctx)); /* other lanes' pictures may read the planes right away */
     ref->d_y = pic->refp[0], ref->d_cb = pic->refp[1], ref->d_cr = pic->refp[2];
     ref->strideY = w + 2 * origin_x, ref->strideC = (w >> 1) + 2 * (origin_x >> 1), ref->originX = origin_x, ref->originY = origin_y;
     ref->width = w, ref->height = h;
@@ -943,10 +943,10 @@ static int put_borders(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typen
     int rc = svt_amd_ctx_scratch(ctx, sizeof(BorderT) * (size_t)n, &d);
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(d, borders, sizeof(BorderT) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(k_put_borders<T>, dim3((unsigned)n), dim3(256), 0, ctx->stream, pic->d, (const BorderT *)d);
+    HIP_TRY(hipMemcpyAsync(d, borders, sizeof(BorderT) * (size_t)n, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    hipLaunchKernelGGL(k_put_borders<T>, dim3((unsigned)n), dim3(256), 0, svt_amd_ctx_stream(ctx), pic->d, (const BorderT *)d);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return ep_picture_written(ctx, pic);
 }
 extern "C" int svt_amd_encdec_picture_put_borders(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuBorder *borders, int n)
@@ -972,7 +972,7 @@ extern "C" int svt_amd_debug_encdec_profile(SvtAmdContext *ctx, SvtAmdEncDecPict
         HIP_TRY(hipMemset(pic->d.prof, 0, bytes));
     }
     if (out) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(svt_amd_ctx_sync(ctx));
         HIP_TRY(hipMemcpy(out, pic->d.prof, bytes, hipMemcpyDeviceToHost));
     }
     return SVT_AMD_OK;

@@ -68,7 +68,7 @@ extern "C" int svt_amd_fast_loop_distortion_batch(SvtAmdContext *ctx, const uint
         ((d_src_cb || d_src_cr || d_pred_cb || d_pred_cr) && !(d_src_cb && d_src_cr && d_pred_cb && d_pred_cr && srcStrideC && predStrideC)))
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_fast_loop_distortion, dim3((ncand + 3) / 4), dim3(256), 0, ctx->stream, d_src_y, (int)srcStrideY, d_src_cb, d_src_cr,
+    hipLaunchKernelGGL(k_fast_loop_distortion, dim3((ncand + 3) / 4), dim3(256), 0, svt_amd_ctx_stream(ctx), d_src_y, (int)srcStrideY, d_src_cb, d_src_cr,
                        (int)srcStrideC, d_pred_y, (int)predStrideY, d_pred_cb, d_pred_cr, (int)predStrideC, (const FastLoopCand *)d_cands, ncand,
                        (FastLoopDist *)d_out);
     HIP_TRY(hipGetLastError());

@@ -951,10 +951,10 @@ extern "C" int svt_amd_dlf_luma_edges_batch(SvtAmdContext *ctx, void *d_plane, u
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     if (bytes_per_sample == 1)
-        hipLaunchKernelGGL(k_dlf_luma<uint8_t>, grid1d(nedges), dim3(256), 0, ctx->stream, (uint8_t *)d_plane, (int)stride,
+        hipLaunchKernelGGL(k_dlf_luma<uint8_t>, grid1d(nedges), dim3(256), 0, svt_amd_ctx_stream(ctx), (uint8_t *)d_plane, (int)stride,
                            (const DlfLumaEdge *)d_edges, nedges);
     else
-        hipLaunchKernelGGL(k_dlf_luma<uint16_t>, grid1d(nedges), dim3(256), 0, ctx->stream, (uint16_t *)d_plane, (int)stride,
+        hipLaunchKernelGGL(k_dlf_luma<uint16_t>, grid1d(nedges), dim3(256), 0, svt_amd_ctx_stream(ctx), (uint16_t *)d_plane, (int)stride,
                            (const DlfLumaEdge *)d_edges, nedges);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -966,10 +966,10 @@ extern "C" int svt_amd_dlf_chroma_edges_batch(SvtAmdContext *ctx, void *d_cb, vo
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     if (bytes_per_sample == 1)
-        hipLaunchKernelGGL(k_dlf_chroma<uint8_t>, grid1d(nedges), dim3(256), 0, ctx->stream, (uint8_t *)d_cb, (uint8_t *)d_cr,
+        hipLaunchKernelGGL(k_dlf_chroma<uint8_t>, grid1d(nedges), dim3(256), 0, svt_amd_ctx_stream(ctx), (uint8_t *)d_cb, (uint8_t *)d_cr,
                            (int)stride, (const DlfChromaEdge *)d_edges, nedges);
     else
-        hipLaunchKernelGGL(k_dlf_chroma<uint16_t>, grid1d(nedges), dim3(256), 0, ctx->stream, (uint16_t *)d_cb, (uint16_t *)d_cr,
+        hipLaunchKernelGGL(k_dlf_chroma<uint16_t>, grid1d(nedges), dim3(256), 0, svt_amd_ctx_stream(ctx), (uint16_t *)d_cb, (uint16_t *)d_cr,
                            (int)stride, (const DlfChromaEdge *)d_edges, nedges);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -996,9 +996,9 @@ extern "C" int svt_amd_dlf_picture(SvtAmdContext *ctx, int bytes_per_sample, voi
         if (!(nL + nC))
             continue;
         if (bytes_per_sample == 1)
-            hipLaunchKernelGGL(k_dlf_picture<uint8_t>, grid1d(nL + nC), dim3(256), 0, ctx->stream, P, dir, lx, nL, cx ? cx : 1, nC);
+            hipLaunchKernelGGL(k_dlf_picture<uint8_t>, grid1d(nL + nC), dim3(256), 0, svt_amd_ctx_stream(ctx), P, dir, lx, nL, cx ? cx : 1, nC);
         else
-            hipLaunchKernelGGL(k_dlf_picture<uint16_t>, grid1d(nL + nC), dim3(256), 0, ctx->stream, P, dir, lx, nL, cx ? cx : 1, nC);
+            hipLaunchKernelGGL(k_dlf_picture<uint16_t>, grid1d(nL + nC), dim3(256), 0, svt_amd_ctx_stream(ctx), P, dir, lx, nL, cx ? cx : 1, nC);
     }
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -1014,9 +1014,9 @@ extern "C" int svt_amd_bs_picture(SvtAmdContext *ctx, const SvtAmdCuMapEntry *d_
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = 2 * (width / 8) * (height / 8), nlcu = ((width + 63) / 64) * ((height + 63) / 64);
     /* 4x4 positions off the 8x8 grid are never written by the reference either: the arrays start as zeros */
-    HIP_TRY(hipMemsetAsync(d_bs_v, 0, (size_t)nlcu * 256, ctx->stream));
-    HIP_TRY(hipMemsetAsync(d_bs_h, 0, (size_t)nlcu * 256, ctx->stream));
-    hipLaunchKernelGGL(k_bs_picture, grid1d(n), dim3(256), 0, ctx->stream, (const CuMapEntry *)d_map, d_cbf, (int)width, (int)height,
+    HIP_TRY(hipMemsetAsync(d_bs_v, 0, (size_t)nlcu * 256, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemsetAsync(d_bs_h, 0, (size_t)nlcu * 256, svt_amd_ctx_stream(ctx)));
+    hipLaunchKernelGGL(k_bs_picture, grid1d(n), dim3(256), 0, svt_amd_ctx_stream(ctx), (const CuMapEntry *)d_map, d_cbf, (int)width, (int)height,
                        slice_type, (unsigned long long)ref_poc0, (unsigned long long)ref_poc1, d_lcu_edge, d_bs_v, d_bs_h);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -1045,14 +1045,14 @@ extern "C" int svt_amd_sao_apply_picture(SvtAmdContext *ctx, int bytes_per_sampl
     const dim3 grid = grid1d(gy + 2 * gc);
     if (bytes_per_sample == 1) {
         if (vec)
-            hipLaunchKernelGGL((k_sao_apply_picture<uint8_t, true>), grid, dim3(256), 0, ctx->stream, P, gy, gc);
+            hipLaunchKernelGGL((k_sao_apply_picture<uint8_t, true>), grid, dim3(256), 0, svt_amd_ctx_stream(ctx), P, gy, gc);
         else
-            hipLaunchKernelGGL((k_sao_apply_picture<uint8_t, false>), grid, dim3(256), 0, ctx->stream, P, gy, gc);
+            hipLaunchKernelGGL((k_sao_apply_picture<uint8_t, false>), grid, dim3(256), 0, svt_amd_ctx_stream(ctx), P, gy, gc);
     } else {
         if (vec)
-            hipLaunchKernelGGL((k_sao_apply_picture<uint16_t, true>), grid, dim3(256), 0, ctx->stream, P, gy, gc);
+            hipLaunchKernelGGL((k_sao_apply_picture<uint16_t, true>), grid, dim3(256), 0, svt_amd_ctx_stream(ctx), P, gy, gc);
         else
-            hipLaunchKernelGGL((k_sao_apply_picture<uint16_t, false>), grid, dim3(256), 0, ctx->stream, P, gy, gc);
+            hipLaunchKernelGGL((k_sao_apply_picture<uint16_t, false>), grid, dim3(256), 0, svt_amd_ctx_stream(ctx), P, gy, gc);
     }
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -1068,19 +1068,19 @@ extern "C" int svt_amd_sao_decide_picture(SvtAmdContext *ctx, const SvtAmdSaoDec
     SaoDecide P;
     ::memcpy(&P, params, sizeof(P));
     const uint32_t nlcu = lcu_cols * lcu_rows;
-    hipLaunchKernelGGL(k_sao_decide_own, dim3((nlcu + 63) / 64), dim3(64), 0, ctx->stream, P, (const SaoStats *)d_stats_y,
+    hipLaunchKernelGGL(k_sao_decide_own, dim3((nlcu + 63) / 64), dim3(64), 0, svt_amd_ctx_stream(ctx), P, (const SaoStats *)d_stats_y,
                        (const SaoStats *)d_stats_cb, (const SaoStats *)d_stats_cr, nlcu, d_enable, (SaoLcuParams *)d_params, d_costs);
     if (P.mmSao || P.temporalLayer < 2) {
         if (lcu_rows <= 64)
-            hipLaunchKernelGGL(k_sao_decide_merge_lds<64>, dim3(1), dim3(512), 0, ctx->stream, P, (const SaoStats *)d_stats_y,
+            hipLaunchKernelGGL(k_sao_decide_merge_lds<64>, dim3(1), dim3(512), 0, svt_amd_ctx_stream(ctx), P, (const SaoStats *)d_stats_y,
                                (const SaoStats *)d_stats_cb, (const SaoStats *)d_stats_cr, lcu_cols, lcu_rows, d_enable,
                                (SaoLcuParams *)d_params, d_costs);
         else if (lcu_rows <= 128)
-            hipLaunchKernelGGL(k_sao_decide_merge_lds<128>, dim3(1), dim3(1024), 0, ctx->stream, P, (const SaoStats *)d_stats_y,
+            hipLaunchKernelGGL(k_sao_decide_merge_lds<128>, dim3(1), dim3(1024), 0, svt_amd_ctx_stream(ctx), P, (const SaoStats *)d_stats_y,
                                (const SaoStats *)d_stats_cb, (const SaoStats *)d_stats_cr, lcu_cols, lcu_rows, d_enable,
                                (SaoLcuParams *)d_params, d_costs);
         else
-            hipLaunchKernelGGL(k_sao_decide_merge, dim3(1), dim3(256), 0, ctx->stream, P, (const SaoStats *)d_stats_y,
+            hipLaunchKernelGGL(k_sao_decide_merge, dim3(1), dim3(256), 0, svt_amd_ctx_stream(ctx), P, (const SaoStats *)d_stats_y,
                                (const SaoStats *)d_stats_cb, (const SaoStats *)d_stats_cr, lcu_cols, lcu_rows, d_enable,
                                (SaoLcuParams *)d_params, d_costs);
     }
@@ -1115,7 +1115,7 @@ extern "C" int svt_amd_sao_decide_lcu(SvtAmdContext *ctx, const SvtAmdSaoDecisio
                                               (const SvtAmdSaoStats *)dh->st[2], 2, 2, dh->enable, (SvtAmdSaoLcuParams *)dh->lcu, dh->cost);
     if (rc != SVT_AMD_OK)
         return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     if (!d.download(&h, sizeof(h)))
         return SVT_AMD_ERR_DEVICE;
     const uint8_t keep = out->edge_flags;
@@ -1135,11 +1135,11 @@ extern "C" int svt_amd_sao_gather_picture(SvtAmdContext *ctx, int bytes_per_samp
     HIP_TRY(hipSetDevice(ctx->device));
     const int lw = (int)((width + lcu_size - 1) / lcu_size), lh = (int)((height + lcu_size - 1) / lcu_size);
     if (bytes_per_sample == 1)
-        hipLaunchKernelGGL(k_sao_gather<uint8_t>, dim3(lw * lh), dim3(256), 0, ctx->stream, (const uint8_t *)d_input,
+        hipLaunchKernelGGL(k_sao_gather<uint8_t>, dim3(lw * lh), dim3(256), 0, svt_amd_ctx_stream(ctx), (const uint8_t *)d_input,
                            (int)inputStride, (const uint8_t *)d_recon, (int)reconStride, (int)width, (int)height,
                            (int)lcu_size, lw, only_eo_90_45_135, (SaoStats *)d_stats);
     else
-        hipLaunchKernelGGL(k_sao_gather<uint16_t>, dim3(lw * lh), dim3(256), 0, ctx->stream, (const uint16_t *)d_input,
+        hipLaunchKernelGGL(k_sao_gather<uint16_t>, dim3(lw * lh), dim3(256), 0, svt_amd_ctx_stream(ctx), (const uint16_t *)d_input,
                            (int)inputStride, (const uint16_t *)d_recon, (int)reconStride, (int)width, (int)height,
                            (int)lcu_size, lw, only_eo_90_45_135, (SaoStats *)d_stats);
     HIP_TRY(hipGetLastError());
@@ -1152,7 +1152,7 @@ extern "C" int svt_amd_pack_plane(SvtAmdContext *ctx, const uint8_t *d_in8, uint
     if (!ctx || !d_in8 || !d_inn || !d_out16 || !width || !height)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_pack, grid1d(width * height), dim3(256), 0, ctx->stream, d_in8, in8Stride, d_inn, innStride, d_out16,
+    hipLaunchKernelGGL(k_pack, grid1d(width * height), dim3(256), 0, svt_amd_ctx_stream(ctx), d_in8, in8Stride, d_inn, innStride, d_out16,
                        outStride, width, height, compressed);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -1164,7 +1164,7 @@ extern "C" int svt_amd_unpack_plane(SvtAmdContext *ctx, const uint16_t *d_in16, 
     if (!ctx || !d_in16 || !d_out8 || !width || !height)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_unpack, grid1d(width * height), dim3(256), 0, ctx->stream, d_in16, inStride, d_out8, out8Stride, d_outn,
+    hipLaunchKernelGGL(k_unpack, grid1d(width * height), dim3(256), 0, svt_amd_ctx_stream(ctx), d_in16, inStride, d_out8, out8Stride, d_outn,
                        outnStride, width, height);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;

@@ -313,7 +313,7 @@ static void launch_full_loop(SvtAmdContext *ctx, const void *d_in, const int16_t
 {
     constexpr int UPW = 64 / N;
     const uint32_t nseq = CHROMA ? 2 * ncand : ncand;
-    hipLaunchKernelGGL((k_full_loop<N, CHROMA, PM>), dim3((nseq + UPW - 1) / UPW), dim3(64), 0, ctx->stream, (const SvtAmdCabacCost *)ctx->d_cabac_cost, d_in, d_res, d_q, d_r, d_out, ncand,
+    hipLaunchKernelGGL((k_full_loop<N, CHROMA, PM>), dim3((nseq + UPW - 1) / UPW), dim3(64), 0, svt_amd_ctx_stream(ctx), (const SvtAmdCabacCost *)ctx->d_cabac_cost, d_in, d_res, d_q, d_r, d_out, ncand,
                        s1, s2, wrap, d_models);
 }
 
@@ -437,11 +437,11 @@ static int full_loop_luma_host(SvtAmdContext *ctx, const SvtAmdCabacCost *cost, 
     int16_t packed[64 * 64];
     for (uint32_t y = 0; y < S; y++)
         ::memcpy(packed + y * S, residual + (size_t)y * pitch, S * sizeof(int16_t));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_in, in, sizeof(*in), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_res, packed, (size_t)S * S * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_in, in, sizeof(*in), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_res, packed, (size_t)S * S * 2, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     int rc;
     if (model) {
-        HIP_TRY(hipMemcpyAsync(d_scratch + o_m, model, RATE_CTX_WORDS * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_scratch + o_m, model, RATE_CTX_WORDS * 4, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
         rc = svt_amd_full_loop_luma_cabac_batch(ctx, cost, (const SvtAmdFullLoopIn *)(d_scratch + o_in), (const int16_t *)(d_scratch + o_res),
                                                 (int16_t *)(d_scratch + o_q), (int16_t *)(d_scratch + o_r),
                                                 (SvtAmdFullLoopOut *)(d_scratch + o_out), (uint32_t *)(d_scratch + o_m), 1);
@@ -452,12 +452,12 @@ static int full_loop_luma_host(SvtAmdContext *ctx, const SvtAmdCabacCost *cost, 
     if (rc)
         return rc;
     if (model)
-        HIP_TRY(hipMemcpyAsync(model, d_scratch + o_m, RATE_CTX_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(model, d_scratch + o_m, RATE_CTX_WORDS * 4, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     int16_t hq[64 * 64], hr[64 * 64];
-    HIP_TRY(hipMemcpyAsync(out, d_scratch + o_out, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, (size_t)S * S * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, (size_t)S * S * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_scratch + o_out, sizeof(*out), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, (size_t)S * S * 2, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, (size_t)S * S * 2, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     const uint32_t T = S == 64 ? 32 : S, area = T >> in->pf_mode;
     for (uint32_t ty = 0; ty < S; ty += T)
         for (uint32_t tx = 0; tx < S; tx += T)
@@ -505,11 +505,11 @@ static int full_loop_chroma_host(SvtAmdContext *ctx, const SvtAmdCabacCost *cost
     for (int p = 0; p < 2; p++)
         for (uint32_t y = 0; y < C; y++)
             ::memcpy(packed + p * 1024 + y * C, residual[p] + (size_t)y * pitch, C * sizeof(int16_t));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_in, in, sizeof(*in), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_res, packed, sizeof(packed), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_in, in, sizeof(*in), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_res, packed, sizeof(packed), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     int rc;
     if (model) {
-        HIP_TRY(hipMemcpyAsync(d_scratch + o_m, model, RATE_CTX_WORDS * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_scratch + o_m, model, RATE_CTX_WORDS * 4, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
         rc = svt_amd_full_loop_chroma_cabac_batch(ctx, cost, (const SvtAmdChromaLoopIn *)(d_scratch + o_in),
                                                   (const int16_t *)(d_scratch + o_res), (int16_t *)(d_scratch + o_q),
                                                   (int16_t *)(d_scratch + o_r), (SvtAmdChromaLoopOut *)(d_scratch + o_out),
@@ -521,12 +521,12 @@ static int full_loop_chroma_host(SvtAmdContext *ctx, const SvtAmdCabacCost *cost
     if (rc)
         return rc;
     if (model)
-        HIP_TRY(hipMemcpyAsync(model, d_scratch + o_m, RATE_CTX_WORDS * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(model, d_scratch + o_m, RATE_CTX_WORDS * 4, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     int16_t hq[2048], hr[2048];
-    HIP_TRY(hipMemcpyAsync(out, d_scratch + o_out, sizeof(*out), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, sizeof(hq), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, sizeof(hr), hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_scratch + o_out, sizeof(*out), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, sizeof(hq), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, sizeof(hr), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     const uint32_t T = in->size == 64 ? 16 : C;
     const uint32_t area = T >> (T == 4 ? 0 : (T == 8 && in->pf_mode == 2 ? 1 : in->pf_mode));
     for (int p = 0; p < 2; p++)
@@ -627,7 +627,7 @@ extern "C" int svt_amd_pmcore_quantize_batch(SvtAmdContext *ctx, const SvtAmdCab
     int rc = rate_upload_tables(ctx, cost);
     if (rc)
         return rc;
-    hipLaunchKernelGGL(k_pmcore_quant, dim3(nunits), dim3(64), 0, ctx->stream, (const SvtAmdCabacCost *)ctx->d_cabac_cost, (const PmQuantUnit *)d_units, d_coeff, d_quant, d_recon, d_nz);
+    hipLaunchKernelGGL(k_pmcore_quant, dim3(nunits), dim3(64), 0, svt_amd_ctx_stream(ctx), (const SvtAmdCabacCost *)ctx->d_cabac_cost, (const PmQuantUnit *)d_units, d_coeff, d_quant, d_recon, d_nz);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
 }
@@ -651,16 +651,16 @@ extern "C" int svt_amd_pmcore_quantize(SvtAmdContext *ctx, const SvtAmdCabacCost
     int16_t hc[32 * 32], hq[32 * 32], hr[32 * 32];
     for (int y = 0; y < N; y++)
         ::memcpy(hc + y * N, coeff + (size_t)y * coeffStride, (size_t)N * 2);
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_unit, unit, sizeof(*unit), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_c, hc, (size_t)N * N * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_unit, unit, sizeof(*unit), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_c, hc, (size_t)N * N * 2, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     int rc = svt_amd_pmcore_quantize_batch(ctx, cost, (const SvtAmdPmQuantUnit *)(d_scratch + o_unit), (const int16_t *)(d_scratch + o_c),
                                            (int16_t *)(d_scratch + o_q), (int16_t *)(d_scratch + o_r), (uint32_t *)(d_scratch + o_nz), 1);
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(nz, d_scratch + o_nz, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, (size_t)N * N * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, (size_t)N * N * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(nz, d_scratch + o_nz, 4, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, (size_t)N * N * 2, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, (size_t)N * N * 2, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     for (int y = 0; y < N; y++) {
         ::memcpy(quant + (size_t)y * coeffStride, hq + y * N, (size_t)N * 2);
         ::memcpy(recon + (size_t)y * coeffStride, hr + y * N, (size_t)N * 2);

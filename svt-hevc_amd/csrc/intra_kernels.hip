@@ -116,7 +116,7 @@ extern "C" int svt_amd_intra_pred_batch(SvtAmdContext *ctx, int mode, int bytes_
     if (!ctx || !d_refs || !d_pred)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    return svt_amd_launch_intra(ctx->stream, mode, bytes_per_sample, size, skip, intraPredAngle, d_refs, ref_pitch,
+    return svt_amd_launch_intra(svt_amd_ctx_stream(ctx), mode, bytes_per_sample, size, skip, intraPredAngle, d_refs, ref_pitch,
                                 main_offset, d_pred, (uint32_t)size, (uint32_t)size * size, nblocks);
 }
 
@@ -300,10 +300,10 @@ extern "C" int svt_amd_intra_pu_batch(SvtAmdContext *ctx, int bytes_per_sample, 
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     if (bytes_per_sample == 1)
-        hipLaunchKernelGGL(k_intra_pu<uint8_t>, dim3(njobs), dim3(256), 0, ctx->stream, (const IntraPuJob *)d_jobs, (uint8_t *)d_pred_y,
+        hipLaunchKernelGGL(k_intra_pu<uint8_t>, dim3(njobs), dim3(256), 0, svt_amd_ctx_stream(ctx), (const IntraPuJob *)d_jobs, (uint8_t *)d_pred_y,
                            strideY, (uint8_t *)d_pred_cb, (uint8_t *)d_pred_cr, strideC);
     else
-        hipLaunchKernelGGL(k_intra_pu<uint16_t>, dim3(njobs), dim3(256), 0, ctx->stream, (const IntraPuJob *)d_jobs, (uint16_t *)d_pred_y,
+        hipLaunchKernelGGL(k_intra_pu<uint16_t>, dim3(njobs), dim3(256), 0, svt_amd_ctx_stream(ctx), (const IntraPuJob *)d_jobs, (uint16_t *)d_pred_y,
                            strideY, (uint16_t *)d_pred_cb, (uint16_t *)d_pred_cr, strideC);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -330,19 +330,19 @@ extern "C" int svt_amd_intra_pu(SvtAmdContext *ctx, int bytes_per_sample, const 
     j.dst_off_y = 0, j.dst_off_c = 0;
     const uint32_t N = job->size, C = N / 2;
     const size_t bps = (size_t)bytes_per_sample;
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_job, &j, sizeof(j), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_job, &j, sizeof(j), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     int rc = svt_amd_intra_pu_batch(ctx, bytes_per_sample, (const SvtAmdIntraPuJob *)(d_scratch + o_job), 1, d_scratch + o_y, N,
                                     d_scratch + o_cb, d_scratch + o_cr, C);
     if (rc)
         return rc;
     uint8_t hy[2048], hcb[512], hcr[512];
     if (wantY)
-        HIP_TRY(hipMemcpyAsync(hy, d_scratch + o_y, (size_t)N * N * bps, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(hy, d_scratch + o_y, (size_t)N * N * bps, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     if (wantC) {
-        HIP_TRY(hipMemcpyAsync(hcb, d_scratch + o_cb, (size_t)C * C * bps, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(hcr, d_scratch + o_cr, (size_t)C * C * bps, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(hcb, d_scratch + o_cb, (size_t)C * C * bps, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+        HIP_TRY(hipMemcpyAsync(hcr, d_scratch + o_cr, (size_t)C * C * bps, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     }
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     for (uint32_t y = 0; wantY && y < N; y++)
         ::memcpy((uint8_t *)pred_y + (size_t)y * strideY * bps, hy + (size_t)y * N * bps, (size_t)N * bps);
     for (uint32_t y = 0; wantC && y < C; y++) {

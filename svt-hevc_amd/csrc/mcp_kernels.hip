@@ -178,10 +178,10 @@ extern "C" int svt_amd_mcp_batch_sized(SvtAmdContext *ctx, int bytes_per_sample,
         return rc ? rc : SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     if (bytes_per_sample == 1)
-        launch_mcp<uint8_t>(ctx->stream, nblocks, max_block_dim, (const uint8_t *)d_ref, (int)refStride, d_dst, (int)dstStride,
+        launch_mcp<uint8_t>(svt_amd_ctx_stream(ctx), nblocks, max_block_dim, (const uint8_t *)d_ref, (int)refStride, d_dst, (int)dstStride,
                             (const McpBlock *)d_blocks, chroma, out_raw);
     else
-        launch_mcp<uint16_t>(ctx->stream, nblocks, max_block_dim, (const uint16_t *)d_ref, (int)refStride, d_dst, (int)dstStride,
+        launch_mcp<uint16_t>(svt_amd_ctx_stream(ctx), nblocks, max_block_dim, (const uint16_t *)d_ref, (int)refStride, d_dst, (int)dstStride,
                              (const McpBlock *)d_blocks, chroma, out_raw);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -202,10 +202,10 @@ extern "C" int svt_amd_bipred_clip_batch(SvtAmdContext *ctx, int bytes_per_sampl
         return rc ? rc : SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     if (bytes_per_sample == 1)
-        hipLaunchKernelGGL(k_bipred_clip<uint8_t>, dim3(nblocks), dim3(256), 0, ctx->stream, d_l0, d_l1, (uint8_t *)d_dst,
+        hipLaunchKernelGGL(k_bipred_clip<uint8_t>, dim3(nblocks), dim3(256), 0, svt_amd_ctx_stream(ctx), d_l0, d_l1, (uint8_t *)d_dst,
                            (int)dstStride, (const BiBlock *)d_blocks, offset);
     else
-        hipLaunchKernelGGL(k_bipred_clip<uint16_t>, dim3(nblocks), dim3(256), 0, ctx->stream, d_l0, d_l1, (uint16_t *)d_dst,
+        hipLaunchKernelGGL(k_bipred_clip<uint16_t>, dim3(nblocks), dim3(256), 0, svt_amd_ctx_stream(ctx), d_l0, d_l1, (uint16_t *)d_dst,
                            (int)dstStride, (const BiBlock *)d_blocks, offset);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
@@ -417,13 +417,13 @@ static int inter_pu_batch(SvtAmdContext *ctx, const SvtAmdInterPuJob *jobs, uint
     for (int l = 0; l < 2; l++)
         for (int p = 0; p < 3; p++) {
             if (!uni[l][p].empty())
-                HIP_TRY(hipMemcpyAsync(d_slab + off_uni[l][p], uni[l][p].data(), uni[l][p].size() * sizeof(McpBlock), hipMemcpyHostToDevice, ctx->stream));
+                HIP_TRY(hipMemcpyAsync(d_slab + off_uni[l][p], uni[l][p].data(), uni[l][p].size() * sizeof(McpBlock), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
             if (!raw[l][p].empty())
-                HIP_TRY(hipMemcpyAsync(d_slab + off_raw[l][p], raw[l][p].data(), raw[l][p].size() * sizeof(McpBlock), hipMemcpyHostToDevice, ctx->stream));
+                HIP_TRY(hipMemcpyAsync(d_slab + off_raw[l][p], raw[l][p].data(), raw[l][p].size() * sizeof(McpBlock), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
         }
     for (int p = 0; p < 3; p++)
         if (!bi[p].empty())
-            HIP_TRY(hipMemcpyAsync(d_slab + off_bi[p], bi[p].data(), bi[p].size() * sizeof(BiBlock), hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(d_slab + off_bi[p], bi[p].data(), bi[p].size() * sizeof(BiBlock), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     T *dst[3] = {d_pred_y, d_pred_cb, d_pred_cr};
     for (int l = 0; l < 2; l++)
         for (int p = 0; p < 3; p++) {
@@ -439,19 +439,19 @@ static int inter_pu_batch(SvtAmdContext *ctx, const SvtAmdInterPuJob *jobs, uint
                 return m;
             };
             if (!uni[l][p].empty())
-                launch_mcp<T, TS>(ctx->stream, (uint32_t)uni[l][p].size(), max_dim(uni[l][p]), plane, rs, (void *)dst[p], ds,
+                launch_mcp<T, TS>(svt_amd_ctx_stream(ctx), (uint32_t)uni[l][p].size(), max_dim(uni[l][p]), plane, rs, (void *)dst[p], ds,
                                     (const McpBlock *)(d_slab + off_uni[l][p]), p != 0, 0);
             if (!raw[l][p].empty())
-                launch_mcp<T, TS>(ctx->stream, (uint32_t)raw[l][p].size(), max_dim(raw[l][p]), plane, rs, (void *)(d_slab + off_int[l][p]), 0,
+                launch_mcp<T, TS>(svt_amd_ctx_stream(ctx), (uint32_t)raw[l][p].size(), max_dim(raw[l][p]), plane, rs, (void *)(d_slab + off_int[l][p]), 0,
                                     (const McpBlock *)(d_slab + off_raw[l][p]), p != 0, 1);
         }
     for (int p = 0; p < 3; p++)
         if (!bi[p].empty()) /* Offset5 / ChromaOffset5 (Codec/EbDefinitions.h:1022-1030) */
-            hipLaunchKernelGGL(k_bipred_clip<T>, dim3((unsigned)bi[p].size()), dim3(256), 0, ctx->stream,
+            hipLaunchKernelGGL(k_bipred_clip<T>, dim3((unsigned)bi[p].size()), dim3(256), 0, svt_amd_ctx_stream(ctx),
                                (const int16_t *)(d_slab + off_int[0][p]), (const int16_t *)(d_slab + off_int[1][p]), dst[p],
                                (int)(p ? strideC : strideY), (const BiBlock *)(d_slab + off_bi[p]), p ? 64 : 16448);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* the host vectors back the asynchronous uploads */
+    HIP_TRY(svt_amd_ctx_sync(ctx)); /* the host vectors back the asynchronous uploads */
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_inter_pu_batch(SvtAmdContext *ctx, const SvtAmdInterPuJob *jobs, uint32_t njobs, const SvtAmdRefPicture *ref0,

@@ -3540,7 +3540,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     SvtAmdMdState *m = nullptr;
     if ((rc = md_state(pic, &m)) != 0)
         return rc;
-    hipStream_t st = ctx->stream;
+    hipStream_t st = svt_amd_ctx_stream(ctx);
     for (hipEvent_t ev : ev_wait)
         if (ev)
             HIP_TRY(hipStreamWaitEvent(st, ev, 0));
@@ -3830,7 +3830,7 @@ extern "C" int svt_amd_debug_md_profile(SvtAmdContext *ctx, SvtAmdEncDecPicture 
         HIP_TRY(hipMemset(m->d_prof, 0, 10 * bytes));
     }
     if (out) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(svt_amd_ctx_sync(ctx));
         HIP_TRY(hipMemcpy(out, m->d_prof, bytes, hipMemcpyDeviceToHost));
     }
     return SVT_AMD_OK;
@@ -3887,7 +3887,7 @@ extern "C" int svt_amd_debug_md_profile_sub(SvtAmdContext *ctx, SvtAmdEncDecPict
     if (!ctx || !pic || !pic->md || !pic->md->d_prof || !out)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     const size_t bytes = sizeof(unsigned long long) * 16 * (size_t)pic->nlcu;
     HIP_TRY(hipMemcpy(out, pic->md->d_prof + 16 * (size_t)pic->nlcu, bytes, hipMemcpyDeviceToHost));
     return SVT_AMD_OK;
@@ -3909,7 +3909,7 @@ extern "C" int svt_amd_debug_md_trace(SvtAmdContext *ctx, SvtAmdEncDecPicture *p
     if (!m->d_trace)
         HIP_TRY(hipMalloc((void **)&m->d_trace, bytes));
     if (out) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(svt_amd_ctx_sync(ctx));
         HIP_TRY(hipMemcpy(out, m->d_trace, bytes, hipMemcpyDeviceToHost));
     } else {
         HIP_TRY(hipMemset(m->d_trace, 0, bytes));
@@ -3943,7 +3943,7 @@ extern "C" int svt_amd_debug_md_profile_depth(SvtAmdContext *ctx, SvtAmdEncDecPi
     if (!ctx || !pic || !pic->md || !pic->md->d_prof || !out)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     HIP_TRY(hipMemcpy(out, pic->md->d_prof + 32 * (size_t)pic->nlcu, sizeof(unsigned long long) * 128 * (size_t)pic->nlcu, hipMemcpyDeviceToHost));
     return SVT_AMD_OK;
 }

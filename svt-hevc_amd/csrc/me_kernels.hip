@@ -1829,8 +1829,8 @@ int svt_amd_launch_me_batch(SvtAmdContext *ctx, const MeJobDev *host_jobs, int n
         return rc;
     const dim3 grid((unsigned)((max_lcus + 7) & ~7), (unsigned)njobs);
     for (int list = 0; list < max_lists; list++) { /* list 1 depends on list 0's result (direct candidate, bi-pred) */
-        hipLaunchKernelGGL(k_me<0>, grid, dim3(NT), pool0, ctx->stream, ctx->d_jobs, list);
-        hipLaunchKernelGGL(k_me<1>, grid, dim3(NT), pool1, ctx->stream, ctx->d_jobs, list);
+        hipLaunchKernelGGL(k_me<0>, grid, dim3(NT), pool0, svt_amd_ctx_stream(ctx), ctx->d_jobs, list);
+        hipLaunchKernelGGL(k_me<1>, grid, dim3(NT), pool1, svt_amd_ctx_stream(ctx), ctx->d_jobs, list);
     }
     HIP_TRY(hipGetLastError());
     return svt_amd_stamp_end(ctx);

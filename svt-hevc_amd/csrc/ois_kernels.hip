@@ -515,9 +515,9 @@ int svt_amd_launch_ois_batch(SvtAmdContext *ctx, const OisJobDev *host_jobs, int
     for (int i = 0; i < njobs; i++)
         wide |= !host_jobs[i].P.slice_is_intra && host_jobs[i].P.ois_kernel_level;
     if (wide)
-        hipLaunchKernelGGL(k_ois_picture<35>, dim3(max_lcus, njobs), dim3(256), 0, ctx->stream, (const OisJobDev *)ctx->d_ois_jobs);
+        hipLaunchKernelGGL(k_ois_picture<35>, dim3(max_lcus, njobs), dim3(256), 0, svt_amd_ctx_stream(ctx), (const OisJobDev *)ctx->d_ois_jobs);
     else
-        hipLaunchKernelGGL(k_ois_picture<10>, dim3(max_lcus, njobs), dim3(256), 0, ctx->stream, (const OisJobDev *)ctx->d_ois_jobs);
+        hipLaunchKernelGGL(k_ois_picture<10>, dim3(max_lcus, njobs), dim3(256), 0, svt_amd_ctx_stream(ctx), (const OisJobDev *)ctx->d_ois_jobs);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
 }
@@ -558,7 +558,7 @@ __global__ __launch_bounds__(256) void k_zz_sad(const uint8_t *__restrict__ cur1
 int svt_amd_launch_zz_sad(SvtAmdContext *ctx, const DevPicture *cur, const DevPicture *prev, SvtAmdZzLcu *d_out)
 {
     const int lw = (cur->width + 63) / 64, lh = (cur->height + 63) / 64;
-    hipLaunchKernelGGL(k_zz_sad, dim3((lw * lh + 3) / 4), dim3(256), 0, ctx->stream, (const uint8_t *)cur->sixteenth.origin,
+    hipLaunchKernelGGL(k_zz_sad, dim3((lw * lh + 3) / 4), dim3(256), 0, svt_amd_ctx_stream(ctx), (const uint8_t *)cur->sixteenth.origin,
                        (const uint8_t *)prev->sixteenth.origin, (int)cur->sixteenth.pitch, (int)cur->width, (int)cur->height,
                        lw * lh, lw, d_out);
     HIP_TRY(hipGetLastError());

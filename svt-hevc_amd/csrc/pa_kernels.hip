@@ -119,22 +119,22 @@ extern "C" int svt_amd_picture_stats(SvtAmdContext *ctx, int slot, SvtAmdPaLcuSt
     uint32_t *d_hist = (uint32_t *)(d + b_out);
     unsigned long long *d_sums = (unsigned long long *)(d + b_out + b_hist), *d_total = d_sums + regions;
     uint8_t *d_avg = (uint8_t *)(d_total + 1);
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, s->ev_ready, 0)); /* the planes may have been built on another lane */
-    HIP_TRY(hipMemsetAsync(d_hist, 0, b_hist + b_sums, ctx->stream));
-    hipLaunchKernelGGL(k_pa_block_stats, dim3((unsigned)n), dim3(64), 0, ctx->stream, s->full.origin, s->full.pitch, wl, d_out);
+    HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), s->ev_ready, 0)); /* the planes may have been built on another lane */
+    HIP_TRY(hipMemsetAsync(d_hist, 0, b_hist + b_sums, svt_amd_ctx_stream(ctx)));
+    hipLaunchKernelGGL(k_pa_block_stats, dim3((unsigned)n), dim3(64), 0, svt_amd_ctx_stream(ctx), s->full.origin, s->full.pitch, wl, d_out);
     const int strips = 16;
-    hipLaunchKernelGGL(k_pa_histogram, dim3((unsigned)strips, (unsigned)regions), dim3(256), 0, ctx->stream, s->sixteenth.origin, s->sixteenth.pitch, w / 4, h / 4,
+    hipLaunchKernelGGL(k_pa_histogram, dim3((unsigned)strips, (unsigned)regions), dim3(256), 0, svt_amd_ctx_stream(ctx), s->sixteenth.origin, s->sixteenth.pitch, w / 4, h / 4,
                        regions_w, regions_h, d_hist, d_sums);
-    hipLaunchKernelGGL(k_pa_finish, dim3((unsigned)regions), dim3(256), 0, ctx->stream, d_hist, d_sums, w / 4, h / 4, regions_w, regions_h, d_avg, d_total);
+    hipLaunchKernelGGL(k_pa_finish, dim3((unsigned)regions), dim3(256), 0, svt_amd_ctx_stream(ctx), d_hist, d_sums, w / 4, h / 4, regions_w, regions_h, d_avg, d_total);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(SvtAmdPaLcuStats), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(SvtAmdPaLcuStats), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     if (histogram)
-        HIP_TRY(hipMemcpyAsync(histogram, d_hist, b_hist, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(histogram, d_hist, b_hist, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     if (region_average)
-        HIP_TRY(hipMemcpyAsync(region_average, d_avg, (size_t)regions, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(region_average, d_avg, (size_t)regions, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     if (sum_luma)
-        HIP_TRY(hipMemcpyAsync(sum_luma, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(hipMemcpyAsync(sum_luma, d_total, 8, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
 
@@ -213,10 +213,10 @@ extern "C" int svt_amd_picture_ac_energy(SvtAmdContext *ctx, int slot, uint64_t 
     int rc = svt_amd_ctx_scratch(ctx, (size_t)n * 40, &d);
     if (rc)
         return rc;
-    HIP_TRY(hipStreamWaitEvent(ctx->stream, s->ev_ready, 0));
-    hipLaunchKernelGGL(k_sbo_ac_energy, dim3((unsigned)n), dim3(64), 0, ctx->stream, s->full.origin, s->full.pitch, s->width, s->height, wl, (unsigned long long *)d);
+    HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), s->ev_ready, 0));
+    hipLaunchKernelGGL(k_sbo_ac_energy, dim3((unsigned)n), dim3(64), 0, svt_amd_ctx_stream(ctx), s->full.origin, s->full.pitch, s->width, s->height, wl, (unsigned long long *)d);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, d, (size_t)n * 40, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out, d, (size_t)n * 40, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }

@@ -174,7 +174,7 @@ int svt_amd_launch_prep_batch(SvtAmdContext *ctx, DevPicture *const *pics, const
         if (rcd)
             return rcd;
     }
-    hipLaunchKernelGGL(k_prep_fused, dim3(b0 + b1 + b2, n), dim3(256), 0, ctx->stream, (const PrepJobDev *)ctx->d_prep_jobs, b0, b1);
+    hipLaunchKernelGGL(k_prep_fused, dim3(b0 + b1 + b2, n), dim3(256), 0, svt_amd_ctx_stream(ctx), (const PrepJobDev *)ctx->d_prep_jobs, b0, b1);
     HIP_TRY(hipGetLastError());
     return svt_amd_stamp_end(ctx);
 }

@@ -489,7 +489,7 @@ static int rate_upload_tables(SvtAmdContext *ctx, const SvtAmdCabacCost *cost)
     if (rc)
         return rc;
     /* pageable source: staged by the runtime before the call returns */
-    HIP_TRY(hipMemcpyAsync(ctx->d_cabac_cost, cost, sizeof(*cost), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_cabac_cost, cost, sizeof(*cost), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     return SVT_AMD_OK;
 }
 #endif

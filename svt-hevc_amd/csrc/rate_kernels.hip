@@ -55,7 +55,7 @@ extern "C" int svt_amd_coeff_bits_batch(SvtAmdContext *ctx, const SvtAmdCabacCos
     int rc = rate_upload_tables(ctx, cost);
     if (rc)
         return rc;
-    return launch_rate(ctx->stream, (const SvtAmdCabacCost *)ctx->d_cabac_cost, size, d_coeff, size, (size_t)size * size, d_info, (unsigned long long *)d_bits, nblocks);
+    return launch_rate(svt_amd_ctx_stream(ctx), (const SvtAmdCabacCost *)ctx->d_cabac_cost, size, d_coeff, size, (size_t)size * size, d_info, (unsigned long long *)d_bits, nblocks);
 }
 
 extern "C" int svt_amd_EstimateQuantizedCoefficients_Lossy(SvtAmdCabacCost *CabacCost, void *cabacEncodeCtxPtr, uint32_t size,
@@ -125,7 +125,7 @@ extern "C" int svt_amd_coeff_bits_update_batch(SvtAmdContext *ctx, uint32_t size
     int rc = rate_tables_once(ctx->device);
     if (rc)
         return rc;
-    hipLaunchKernelGGL(k_coeff_bits_update, dim3((nblocks + chain_len - 1) / chain_len), dim3(64), 0, ctx->stream, d_coeff, size,
+    hipLaunchKernelGGL(k_coeff_bits_update, dim3((nblocks + chain_len - 1) / chain_len), dim3(64), 0, svt_amd_ctx_stream(ctx), d_coeff, size,
                        (size_t)size * size, d_info, d_ctx_models, (unsigned long long *)d_bits, nblocks, chain_len, lg);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;

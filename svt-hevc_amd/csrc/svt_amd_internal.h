@@ -81,10 +81,16 @@ struct OisJobDev {
     SvtAmdOisLcuResult *out;
 };
 
+/* where the pack kernels find picture i of a batch (svt_amd_records_pack_batch_async) */
+struct PackSrc {
+    const uint32_t *me, *ois;      /* the slot's d_me_out / d_ois_out */
+};
+
 struct SvtAmdContext {
     int device;
     SvtAmdContext *parent;         /* lane (svt_amd_context_fork): shares the parent's picture slots, owns everything else */
-    hipStream_t stream;
+    hipStream_t stream;            /* made at the first stream-ordered use: read it through svt_amd_ctx_stream() only */
+    int stream_failed;             /* the stream could not be made: svt_amd_synchronize reports it */
     uint16_t max_w, max_h;
     int num_slots;
     DevPicture *slots;
@@ -107,10 +113,11 @@ struct SvtAmdContext {
     SvtAmdOisLcuResult *h_ois;
     hipEvent_t ev_done;
     int frontend_busy;
-    hipEvent_t ev_user[8];
+    hipEvent_t ev_user[8];         /* svt_amd_lane_event_record / _wait */
     uint8_t *h_desc_ring;          /* pinned ring of launch descriptors (svt_amd_upload_descriptors) */
     hipEvent_t ev_desc[8];
-    int desc_next;         /* svt_amd_lane_event_record / _wait */
+    int desc_next;
+    void *d_pack_src;              /* device table of the pack kernels' per-picture sources (svt_amd_records_pack_batch_async) */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
@@ -127,6 +134,18 @@ int svt_amd_ctx_scratch(SvtAmdContext *ctx, size_t bytes, uint8_t **out);
 const void *svt_amd_registered_device_ptr(const void *h_ptr, size_t bytes);
 
 void svt_amd_set_error(const char *fmt, ...);
+
+/* The context's stream.  A context holds none until its first stream-ordered use (a launch, an asynchronous copy, an event
+ * record or wait, a timer): one that only allocates, pins host memory, copies blocking and forks lanes - the root of a host that
+ * does all its work on lanes - never takes a hardware queue from them (context.hip, above svt_amd_runtime_env_defaults). */
+hipStream_t svt_amd_ctx_stream(SvtAmdContext *ctx);
+static inline bool svt_amd_ctx_has_stream(const SvtAmdContext *ctx) { return ctx->stream != nullptr; }
+/* waits for whatever the context has queued; a context without a stream has queued nothing (one whose stream could not be made has
+ * queued on the null stream) */
+static inline hipError_t svt_amd_ctx_sync(SvtAmdContext *ctx)
+{
+    return ctx->stream || ctx->stream_failed ? hipStreamSynchronize(ctx->stream) : hipSuccess;
+}
 #define HIP_TRY(expr)                                                                      \
     do {                                                                                   \
         hipError_t e_ = (expr);                                                            \

@@ -610,7 +610,7 @@ extern "C" int svt_amd_fwd_transform_batch(SvtAmdContext *ctx, int kind, int siz
     if (!ctx || !d_residual || !d_coeff)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    return svt_amd_launch_fwd_transform(ctx->stream, kind, size, bitIncrement, d_residual, d_coeff, nblocks);
+    return svt_amd_launch_fwd_transform(svt_amd_ctx_stream(ctx), kind, size, bitIncrement, d_residual, d_coeff, nblocks);
 }
 extern "C" int svt_amd_inv_transform_batch(SvtAmdContext *ctx, int kind, int size, uint32_t bitIncrement,
                                            const int16_t *d_coeff, int16_t *d_residual, uint32_t nblocks)
@@ -618,7 +618,7 @@ extern "C" int svt_amd_inv_transform_batch(SvtAmdContext *ctx, int kind, int siz
     if (!ctx || !d_residual || !d_coeff)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    return svt_amd_launch_inv_transform(ctx->stream, kind, size, bitIncrement, d_coeff, d_residual, nblocks);
+    return svt_amd_launch_inv_transform(svt_amd_ctx_stream(ctx), kind, size, bitIncrement, d_coeff, d_residual, nblocks);
 }
 extern "C" int svt_amd_quantize_batch(SvtAmdContext *ctx, int size, uint32_t qFunc, uint32_t q_offset,
                                       int32_t shiftedQBits, int32_t shiftedFFunc, int32_t iq_offset, int32_t shiftNum,
@@ -628,7 +628,7 @@ extern "C" int svt_amd_quantize_batch(SvtAmdContext *ctx, int size, uint32_t qFu
     if (!ctx || !d_coeff || !d_quant || !d_recon || !d_nz)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    return svt_amd_launch_quant(ctx->stream, size, qFunc, q_offset, shiftedQBits, shiftedFFunc, iq_offset, shiftNum,
+    return svt_amd_launch_quant(svt_amd_ctx_stream(ctx), size, qFunc, q_offset, shiftedQBits, shiftedFFunc, iq_offset, shiftNum,
                                 d_coeff, d_quant, d_recon, d_nz, nblocks);
 }
 extern "C" int svt_amd_full_distortion_batch(SvtAmdContext *ctx, int size, int mode, const int16_t *d_coeff,
@@ -637,7 +637,7 @@ extern "C" int svt_amd_full_distortion_batch(SvtAmdContext *ctx, int size, int m
     if (!ctx || !d_coeff || !d_recon || !d_result)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    return svt_amd_launch_full_distortion(ctx->stream, size, mode, d_coeff, d_recon, (unsigned long long *)d_result, nblocks);
+    return svt_amd_launch_full_distortion(svt_amd_ctx_stream(ctx), size, mode, d_coeff, d_recon, (unsigned long long *)d_result, nblocks);
 }
 extern "C" int svt_amd_satd_batch(SvtAmdContext *ctx, int size, const int16_t *d_diff, uint64_t *d_satd,
                                   uint32_t nblocks)
@@ -645,7 +645,7 @@ extern "C" int svt_amd_satd_batch(SvtAmdContext *ctx, int size, const int16_t *d
     if (!ctx || !d_diff || !d_satd)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    return svt_amd_launch_satd(ctx->stream, size, d_diff, nullptr, 0, (unsigned long long *)d_satd, nullptr, nblocks);
+    return svt_amd_launch_satd(svt_amd_ctx_stream(ctx), size, d_diff, nullptr, 0, (unsigned long long *)d_satd, nullptr, nblocks);
 }
 
 extern "C" int svt_amd_recon_tu_batch(SvtAmdContext *ctx, int bytes_per_sample, int size, const int16_t *d_coeff,
@@ -659,7 +659,7 @@ extern "C" int svt_amd_recon_tu_batch(SvtAmdContext *ctx, int bytes_per_sample, 
     const int s1 = 7, s2 = bytes_per_sample == 1 ? 12 : 10; /* SHIFT_INV_1ST, SHIFT_INV_2ND - bitIncrement (0 / 2) */
     const ReconUnit *un = (const ReconUnit *)d_units;
 #define SVT_RECON_LAUNCH(N, T)                                                                                               \
-    hipLaunchKernelGGL((k_recon_tu<N, T>), dim3((nunits + (64 / N) * 4 - 1) / ((64 / N) * 4)), dim3(TX_THREADS), 0, ctx->stream, \
+    hipLaunchKernelGGL((k_recon_tu<N, T>), dim3((nunits + (64 / N) * 4 - 1) / ((64 / N) * 4)), dim3(TX_THREADS), 0, svt_amd_ctx_stream(ctx), \
                        d_coeff, un, (const T *)d_pred, predStride, (T *)d_recon, reconStride, nunits, s1, s2)
     if (bytes_per_sample == 1) {
         if (size == 32) SVT_RECON_LAUNCH(32, uint8_t);
@@ -702,16 +702,16 @@ extern "C" int svt_amd_recon_tu(SvtAmdContext *ctx, int bytes_per_sample, int si
         ::memcpy(hp + (size_t)y * size * bps, (const uint8_t *)pred + (size_t)y * predStride * bps, (size_t)size * bps);
     }
     SvtAmdReconUnit u = {0, 0, (uint8_t)(only_dc != 0), (uint8_t)(dst != 0), {0, 0}};
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_unit, &u, sizeof(u), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_coeff, hc, (size_t)size * size * 2, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_pix, hp, (size_t)size * size * bps, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_unit, &u, sizeof(u), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_coeff, hc, (size_t)size * size * 2, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_pix, hp, (size_t)size * size * bps, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     int rc = svt_amd_recon_tu_batch(ctx, bytes_per_sample, size, (const int16_t *)(d_scratch + o_coeff),
                                     (const SvtAmdReconUnit *)(d_scratch + o_unit), d_scratch + o_pix, (uint32_t)size,
                                     d_scratch + o_pix, (uint32_t)size, 1);
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(hp, d_scratch + o_pix, (size_t)size * size * bps, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hp, d_scratch + o_pix, (size_t)size * size * bps, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     for (int y = 0; y < size; y++)
         ::memcpy((uint8_t *)recon + (size_t)y * reconStride * bps, hp + (size_t)y * size * bps, (size_t)size * bps);
     return SVT_AMD_OK;
@@ -814,7 +814,7 @@ extern "C" int svt_amd_unified_quantize_batch(SvtAmdContext *ctx, const SvtAmdQu
     if (!ctx || !d_units || !d_coeff || !d_quant || !d_recon || !d_nz || !nunits)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(k_unified_quant, dim3(nunits), dim3(256), 0, ctx->stream, (const QuantUnit *)d_units, d_coeff, d_quant, d_recon, d_nz);
+    hipLaunchKernelGGL(k_unified_quant, dim3(nunits), dim3(256), 0, svt_amd_ctx_stream(ctx), (const QuantUnit *)d_units, d_coeff, d_quant, d_recon, d_nz);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
 }
@@ -838,16 +838,16 @@ extern "C" int svt_amd_unified_quantize(SvtAmdContext *ctx, const SvtAmdQuantUni
     int16_t hc[32 * 32], hq[32 * 32], hr[32 * 32];
     for (int y = 0; y < N; y++)
         ::memcpy(hc + y * N, coeff + (size_t)y * coeffStride, (size_t)N * 2);
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_unit, unit, sizeof(*unit), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(d_scratch + o_c, hc, (size_t)N * N * 2, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_unit, unit, sizeof(*unit), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(d_scratch + o_c, hc, (size_t)N * N * 2, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     int rc = svt_amd_unified_quantize_batch(ctx, (const SvtAmdQuantUnit *)(d_scratch + o_unit), (const int16_t *)(d_scratch + o_c),
                                             (int16_t *)(d_scratch + o_q), (int16_t *)(d_scratch + o_r), (uint32_t *)(d_scratch + o_nz), 1);
     if (rc)
         return rc;
-    HIP_TRY(hipMemcpyAsync(nz, d_scratch + o_nz, 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, (size_t)N * N * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, (size_t)N * N * 2, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpyAsync(nz, d_scratch + o_nz, 4, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hq, d_scratch + o_q, (size_t)N * N * 2, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(hr, d_scratch + o_r, (size_t)N * N * 2, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
     for (int y = 0; y < area; y++) { /* like the reference, only the active area is written */
         ::memcpy(quant + (size_t)y * coeffStride, hq + y * N, (size_t)area * 2);
         ::memcpy(recon + (size_t)y * coeffStride, hr + y * N, (size_t)area * 2);
@@ -961,7 +961,7 @@ extern "C" int svt_amd_encode_tu_batch(SvtAmdContext *ctx, int bytes_per_sample,
     const int fs1 = (size == 32 ? 6 : size == 16 ? 4 : size == 8 ? 2 : 1) + inc, fs2 = size == 4 ? 8 : 9, wrap = size == 32 ? 2 : size == 16 ? 1 : 0;
     const EncodeUnit *un = (const EncodeUnit *)d_units;
 #define SVT_ENC_LAUNCH(N, T)                                                                                                  \
-    hipLaunchKernelGGL((k_encode_tu<N, T>), dim3((nunits + (64 / N) * 4 - 1) / ((64 / N) * 4)), dim3(TX_THREADS), 0, ctx->stream, un, \
+    hipLaunchKernelGGL((k_encode_tu<N, T>), dim3((nunits + (64 / N) * 4 - 1) / ((64 / N) * 4)), dim3(TX_THREADS), 0, svt_amd_ctx_stream(ctx), un, \
                        (const T *)d_src, srcStride, (T *)d_rec, recStride, d_quant, d_nz, nunits, fs1, fs2, wrap, 7, 12 - inc)
     if (bytes_per_sample == 1) {
         if (size == 32) SVT_ENC_LAUNCH(32, uint8_t);

@@ -219,10 +219,10 @@ extern "C" int svt_amd_fwd_transform_mfma_batch(SvtAmdContext *ctx, int kind, in
             return rc;
     }
     const unsigned grid = (nblocks + 3) / 4 < 2048 ? (nblocks + 3) / 4 : 2048;
-    hipLaunchKernelGGL(k_fwd32_mfma, dim3(grid), dim3(256), 0, ctx->stream, d_residual, d_coeff, nblocks, s1, s2, flags);
+    hipLaunchKernelGGL(k_fwd32_mfma, dim3(grid), dim3(256), 0, svt_amd_ctx_stream(ctx), d_residual, d_coeff, nblocks, s1, s2, flags);
     HIP_TRY(hipGetLastError());
     if (kind == 1)
-        return svt_amd_launch_fwd_transform_flagged(ctx->stream, kind, size, bitIncrement, d_residual, d_coeff, nblocks, flags);
+        return svt_amd_launch_fwd_transform_flagged(svt_amd_ctx_stream(ctx), kind, size, bitIncrement, d_residual, d_coeff, nblocks, flags);
     return SVT_AMD_OK;
 }
 
@@ -233,7 +233,7 @@ extern "C" int svt_amd_inv_transform_mfma_batch(SvtAmdContext *ctx, int size, ui
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     const unsigned grid = (nblocks + 3) / 4 < 2048 ? (nblocks + 3) / 4 : 2048;
-    hipLaunchKernelGGL(k_inv32_mfma, dim3(grid), dim3(256), 0, ctx->stream, d_coeff, d_residual, nblocks, 7, 12 - (int)bitIncrement);
+    hipLaunchKernelGGL(k_inv32_mfma, dim3(grid), dim3(256), 0, svt_amd_ctx_stream(ctx), d_coeff, d_residual, nblocks, 7, 12 - (int)bitIncrement);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;
 }

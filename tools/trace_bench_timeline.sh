@@ -11,7 +11,8 @@ ev = []
 for f in glob.glob(O + "/tr/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         n = r["Kernel_Name"]
-        tag = "ME" if "k_me" in n else "OIS" if "ois" in n else "PREP" if "prep" in n else "PACK" if "pack" in n else None
+        # a copy the runtime makes with a kernel of its own does not appear in the memory-copy trace
+        tag = "PACK" if "pack" in n else "ME" if "k_me" in n else "OIS" if "ois" in n else "PREP" if "prep" in n else "COPY KERNEL (runtime)" if "copyBuffer" in n else None
         if tag:
             ev.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), tag))
 for f in glob.glob(O + "/tr/**/*memory_copy_trace.csv", recursive=True):
