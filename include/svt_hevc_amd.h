@@ -261,6 +261,7 @@ SVT_AMD_API int svt_amd_ois_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtA
  * ComputeDecimatedZzSad (EbMotionEstimationProcess.c:176-300, called per ME segment at :828 when lookAheadDistance != 0
  * and pictureNumber > 0).  prev_slot = the previous picture in display order; results are what the reference stores
  * into the PREVIOUS picture's zzCostArray / nonMovingIndexArray.  out: HOST array, one record per LCU.  Blocking.
+ * Batched, stream-ordered form (results stay on the device): svt_amd_side_stats_batch_launch.
  */
 typedef struct SvtAmdZzLcu {
     uint32_t sad;              /* decimatedLcuCollocatedSad (0xFFFFFFFF for incomplete LCUs)     */
@@ -380,6 +381,7 @@ SVT_AMD_API int svt_amd_recon_pack(SvtAmdContext *ctx, void *const d_planes[3], 
  *            SubSampleLumaGeneratePixelIntensityHistogramBins :3384), the regions' average intensity and the picture's luma sum (<< 4 per region).
  * out: HOST, LCUs of the picture in raster order; histogram: HOST [regions_w][regions_h][256] or NULL; region_average: HOST [regions_w][regions_h]
  * or NULL; sum_luma: HOST or NULL.  Blocking.
+ * Batched, stream-ordered form (results stay on the device): svt_amd_side_stats_batch_launch.
  */
 typedef struct SvtAmdPaLcuStats {
     uint16_t variance[SVT_AMD_ME_PU_COUNT];  /* pictureControlSetPtr->variance[lcu]  */
@@ -396,6 +398,7 @@ SVT_AMD_API int svt_amd_picture_stats(SvtAmdContext *ctx, int slot, SvtAmdPaLcuS
  * (EbModeDecisionConfiguration.c:409-426) and the encode pass's skin / contour tests (EbModeDecisionProcess.c:542).  LCUs the picture does not cover completely
  * get the reference's 100000000 (:351).  Which pictures the values are read for (I pictures outside low-delay P) is the caller's rule.
  * out: HOST, [LCUs in raster order][5].  Blocking.
+ * Batched, stream-ordered form (results stay on the device): svt_amd_side_stats_batch_launch.
  */
 SVT_AMD_API int svt_amd_picture_ac_energy(SvtAmdContext *ctx, int slot, uint64_t *out);
 
@@ -405,6 +408,51 @@ typedef struct SvtAmdOisJob {
     int32_t cur_slot;
 } SvtAmdOisJob;
 SVT_AMD_API int svt_amd_ois_batch_launch(SvtAmdContext *ctx, const SvtAmdOisJob *jobs, int num_jobs);
+
+/*
+ * Batched side statistics: the three per-picture results above that belong to the same stage as ME / OIS, for up to 256 pictures of ONE geometry per call,
+ * stream-ordered on the context's lane like svt_amd_me_batch_launch / svt_amd_ois_batch_launch / svt_amd_records_pack_batch_async - the call never blocks and
+ * never copies to the host:
+ *   block_stats     ComputeBlockMeanComputeVariance (Codec/EbPictureAnalysisProcess.c:1646)      } one kernel, ONE read of the luma plane: a wave per LCU,
+ *   ac_energy       CalculateAcEnergy (Codec/EbSourceBasedOperationsProcess.c:302-362;           } a lane per 8x8 block (svt_amd_picture_stats and
+ *                   ComputeNxMSatdSadLCU, Codec/EbPictureOperators.c:232)                        } svt_amd_picture_ac_energy read it once each)
+ *   histogram, region_average, sum_luma
+ *                   SubSampleLumaGeneratePixelIntensityHistogramBins (Codec/EbPictureAnalysisProcess.c:3384) on the 1/16 pictures, regions_w x regions_h
+ *                   regions (at most 64; only read when some job wants histograms); region_average and sum_luma are written for the pictures that want
+ *                   histograms where those arrays are given, the bytes of a picture's region_average beyond its regions are 0
+ *   zz              ComputeDecimatedZzSad (Codec/EbMotionEstimationProcess.c:176-300) of cur_slot against prev_slot: record i is what the reference stores into
+ *                   the PREVIOUS picture's zzCostArray / nonMovingIndexArray, as for svt_amd_zz_sad_picture
+ * Values are those of the three blocking entries, byte for byte.  The arrays are DEVICE memory (svt_amd_device_alloc), picture i of the batch at i times
+ * svt_amd_side_stats_bytes(...) bytes of each; a picture that does not want a result leaves its part of that array untouched.  The histogram and sum_luma parts
+ * the kernels accumulate into are zeroed by the call.  The call waits, on the device, for the planes of every slot it reads - each job's prev_slot included -
+ * so they may have been built on another lane.  Move the results with svt_amd_device_download_async on any lane behind svt_amd_lane_event_record / _wait: one
+ * copy per kind for the whole batch.  Everything is checked before anything is queued: a job that wants a result whose array is NULL, a slot that holds no
+ * picture or one of another size than job 0's, or bad regions return SVT_AMD_ERR_BAD_PARAM (svt_amd_last_error says which) and queue nothing.
+ */
+typedef struct SvtAmdSideJob {
+    int32_t cur_slot;
+    int32_t prev_slot;          /* previous picture in display order; < 0: no zz-SAD for this picture */
+    uint8_t want_block_stats, want_ac_energy, want_histogram, pad;
+} SvtAmdSideJob;                /* 12 bytes */
+typedef struct SvtAmdSideArrays {          /* DEVICE pointers, picture i of the batch at index i; any may be NULL */
+    SvtAmdPaLcuStats *block_stats;         /* [n][lcus]            pictureControlSetPtr->variance / yMean (EbPictureAnalysisProcess.c:1646)  */
+    uint64_t         *ac_energy;           /* [n][lcus][5]         lcuYSrcEnergyCuArray[lcu][0..4] (EbSourceBasedOperationsProcess.c:302)    */
+    SvtAmdZzLcu      *zz;                  /* [n][lcus]            zzCostArray / nonMovingIndexArray (EbMotionEstimationProcess.c:176-300)   */
+    uint32_t         *histogram;           /* [n][regions_w][regions_h][256]   pictureHistogram (EbPictureAnalysisProcess.c:3384)            */
+    uint8_t          *region_average;      /* [n][regions_w][regions_h], each picture padded to 64 bytes   averageIntensityPerRegion (:3428) */
+    uint64_t         *sum_luma;            /* [n]                  the sum CalculateInputAverageIntensity (:3953) divides                    */
+} SvtAmdSideArrays;
+SVT_AMD_API int svt_amd_side_stats_batch_launch(SvtAmdContext *ctx, const SvtAmdSideJob *jobs, int num_jobs, int regions_w, int regions_h,
+                                                const SvtAmdSideArrays *out);
+/* bytes ONE picture of luma_width x luma_height takes in array `which` (picture i of a batch starts at i times this); 0 for an unknown `which` or bad
+ * regions.  Host arithmetic: no context, no device. */
+#define SVT_AMD_SIDE_BLOCK_STATS 0
+#define SVT_AMD_SIDE_AC_ENERGY   1
+#define SVT_AMD_SIDE_ZZ          2
+#define SVT_AMD_SIDE_HISTOGRAM   3
+#define SVT_AMD_SIDE_REGION_AVG  4
+#define SVT_AMD_SIDE_SUM_LUMA    5
+SVT_AMD_API size_t svt_amd_side_stats_bytes(uint16_t luma_width, uint16_t luma_height, int which, int regions_w, int regions_h);
 
 
 /* Device-side timing of the launches issued between begin/end on the context's

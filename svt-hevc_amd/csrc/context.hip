@@ -115,6 +115,8 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
         (void)hipFree(ctx->d_prep_jobs);
     if (ctx->d_pack_src)
         (void)hipFree(ctx->d_pack_src);
+    if (ctx->d_side)
+        (void)hipFree(ctx->d_side);
     if (ctx->d_dbg)
         (void)hipFree(ctx->d_dbg);
     for (int i = 0; i < ctx->cap_stamps; i++) {
