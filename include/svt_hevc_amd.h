@@ -1763,6 +1763,9 @@ SVT_AMD_API int svt_amd_debug_md_flights(int *in_flight, int *workgroups_held, i
 SVT_AMD_API int svt_amd_md_picture_warmup(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic);
 /* measurement: dynamic LDS bytes a workgroup of k_md_encode_picture<inter, sample bytes> is launched with (the whole LCU state: one workgroup per CU) */
 SVT_AMD_API int svt_amd_debug_md_kernel_lds_bytes(int inter, int bytes_per_sample);
+/* measurement: LDS bytes (static + dynamic) a workgroup of the motion-estimation kernel of `phase` (0 = HME, 1 = search) is launched with for a job with
+ * these controls; params == NULL: what the last svt_amd_me_* launch of the process requested (compiler's static size + the launcher's pool) */
+SVT_AMD_API int svt_amd_debug_me_kernel_lds_bytes(const SvtAmdMeParams *params, int phase);
 
 #ifdef __cplusplus
 }

@@ -31,7 +31,7 @@
 #define NT 256
 #define LCU 64
 #ifndef ME_MIN_WAVES_PER_SIMD
-#define ME_MIN_WAVES_PER_SIMD 3 /* LDS (static + windows ~ 53 KB at cfg2) admits 3 workgroups per CU */
+#define ME_MIN_WAVES_PER_SIMD 4 /* LDS (static + pool = 40,208 B at cfg2, see me_pool_bytes) admits 4 workgroups per CU */
 #endif
 #ifndef ME_HME_WAVES_PER_SIMD
 /* 4 workgroups per CU = a 128-VGPR budget: the HME kernel needs 119 and then has NO private segment.  At 6 (80 VGPRs) it spilled
@@ -210,6 +210,13 @@ __device__ __forceinline__ int win_pitch(int x0, int x1, int odd)
         wa += 16;
     return wa;
 }
+/* row pitches of the staged search windows.  F (stored from registers, dword stores): 16-byte items, pitch = 1 dword mod 4 dwords, so
+ * that the four 8x8 block rows of a wave's quadrant (8 window rows apart) start 8 banks apart - ds_read_b32 banks are dword mod 32 and
+ * a half wave reads 8 consecutive dwords of each of the four rows: conflict-free, where a pitch of whole 16-byte units puts all four
+ * rows on the same banks.  b / h / j (LDS-DMA: a wave instruction fills 1 KiB of consecutive LDS, so the pitch is whole 16-byte
+ * items): first column on a dword boundary of the plane, cols = columns from there. */
+__host__ __device__ __forceinline__ int me_f_pitch(int cols) { return ((cols + 15) & ~15) + 4; }
+__host__ __device__ __forceinline__ int me_hp_pitch(int cols) { return (cols + 15) & ~15; }
 __device__ __forceinline__ const uint8_t *wat(const LWin &w, int x, int y)
 {
     return w.p + (y - w.y0) * w.stride + (x - w.x0);
@@ -276,11 +283,12 @@ __device__ __forceinline__ int load_window_async(LWin &w, int off, const uint8_t
     return off + rows * wa;
 }
 
-/* The three half-pel windows of the search kernel share their geometry: one pass derives (row, 16-byte column) of an item once and issues the three LDS-DMA loads */
+/* The three half-pel windows of the search kernel share their geometry: one pass derives (row, 16-byte column) of an item once and issues the three LDS-DMA loads.
+ * Their first column is the last dword boundary of the plane at or before x0 (LDS-DMA items take any global address; the LDS side stays 16-byte aligned). */
 __device__ __forceinline__ int load_windows3_async(LWin &wa_, LWin &wb_, LWin &wc_, int off, const uint8_t *pa, const uint8_t *pb, const uint8_t *pc, int pitch, int x0, int y0,
                                                    int x1, int y1, int t)
 {
-    const int xa = x0 & ~15, wa = win_pitch(x0, x1, 1), n16 = wa >> 4, rows = y1 - y0, total = rows * n16, bytes = rows * wa;
+    const int xa = x0 & ~3, wa = me_hp_pitch(x1 - xa), n16 = wa >> 4, rows = y1 - y0, total = rows * n16, bytes = rows * wa;
     uint8_t *dst = g_pool + off;
     wa_.p = dst, wb_.p = dst + bytes, wc_.p = dst + 2 * bytes;
     wa_.x0 = wb_.x0 = wc_.x0 = xa, wa_.y0 = wb_.y0 = wc_.y0 = y0, wa_.stride = wb_.stride = wc_.stride = wa;
@@ -390,7 +398,7 @@ __device__ uint32_t mvd_fraction_bits(int mvdX, int mvdY, const uint32_t *bits)
     return n;
 }
 
-/* LDS state shared by both kernels of the split (static allocation) */
+/* LDS state of the HME kernel (static allocation) */
 struct MeShared {
     uint8_t src[LCU * LCU + 16];   /* source LCU rows (padded-plane content)              */
     uint8_t qsrc[32 * 16 + 16];    /* 1/4 LCU, even rows                                   */
@@ -403,27 +411,32 @@ struct MeShared {
     int cand[6][4];                /* LCU-SAD candidates {unclamped x, y, clamped x, y}                     */
     uint32_t mvd_bits[12];         /* P.mvd_bits (dynamically indexed by the rate function)                 */
 };
-/* LDS state of the search kernel only; lives at the start of the dynamic pool (the staged windows follow), so the
- * HME kernel does not pay for it and fits ~3x more workgroups per CU */
+/* ... and of the search kernel (static allocation): the source LCU is all it shares with the HME kernel's state */
+struct MeSearchShared {
+    uint8_t src[LCU * LCU + 16];
+};
+template <int PHASE> struct MeStatic { typedef MeShared type; };
+template <> struct MeStatic<1> { typedef MeSearchShared type; };
+/* LDS state of the search kernel only; lives at the start of the dynamic pool, so the HME kernel does not pay for it.  The pool is laid
+ * out per job: MeSearch, then MeSearchSsd where the job searches by SSD (the SAD methods never read it), then the staged windows */
 struct MeSearch {
     union {                        /* the full-pel SAD trees and the sub-pel accumulators are never live together */
-        struct {
-            uint32_t sad32[256][4]; /* 32x32 SADs of a chunk of search rows, [position][quadrant]: the 64x64 sums */
-        };
-        struct {
-            uint32_t dist[85][8];  /* sub-pel distortions (search metric)                  */
-            uint32_t dsad[85][8];  /* full SAD at the same positions (SSD search only)     */
-        };
+        uint32_t sad32[256][4];    /* 32x32 SADs of a chunk of search rows, [position][quadrant]: the 64x64 sums */
+        uint32_t dist[85][8];      /* sub-pel distortions (search metric)                  */
     };
     uint32_t key[85];              /* packed (sad,index) minima, PUs 1..84                 */
     unsigned long long key64;      /* 64x64 */
-    uint32_t best_sad[2][85], best_mv[2][85], best_ssd[2][85];
+    uint32_t best_sad[2][85], best_mv[2][85];
     uint8_t dir[2][85];
     uint32_t bipred[85];
-    int e32, e16, e8, eq;
-    int sums[9];                   /* SuPelEnable: per tier {sum mvx, sum mvy, sum sad} */
+    int sums[12];                  /* SuPelEnable: per tier {sum mvx, sum mvy, sum sad}; [9..11] = wave 1's share of the 8x8 tier */
+};
+struct MeSearchSsd {               /* SVT_AMD_SSD_SEARCH only */
+    uint32_t dsad[85][8];          /* full SAD at the sub-pel positions                    */
+    uint32_t best_ssd[2][85];
 };
 #define ME_SEARCH_BYTES ((int)((sizeof(MeSearch) + 15) & ~(size_t)15))
+#define ME_SEARCH_SSD_BYTES ((int)((sizeof(MeSearchSsd) + 15) & ~(size_t)15))
 /* what the HME kernel hands to the search kernel (and to itself for list 1: trap A21) per LCU */
 struct MeCarry {
     int16_t hx[3][2][2], hy[3][2][2];
@@ -671,12 +684,12 @@ __device__ __forceinline__ int pick4(int i, int a, int b, int c, int d) { return
  *   PHASE 0  "hme"     TestSearchAreaBounds + HME L0/L1/L2 + CheckZeroZeroCenter -> search centre (MeCarry)
  *   PHASE 1  "search"  full-pel 85-PU search + sub-pel refinement of that list; after the last list also
  *                      bi-prediction and the candidate records
- * The HME part needs ~15 KB of LDS and few registers, the search part ~55 KB: as separate kernels the
- * latency-bound HME phases run at ~3x the occupancy instead of inheriting the search kernel's footprint. */
+ * Each kernel has its own LDS state (MeStatic<PHASE> + its pool) and register budget: the HME kernel's 113 VGPRs hold it at four
+ * waves a SIMD, the search kernel's 40 KB of LDS at the 16 x 9 search area at four workgroups a CU (me_pool_bytes). */
 template <int PHASE>
 __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAVES_PER_SIMD) void k_me(const MeJobDev *__restrict__ jobs, int list)
 {
-    __shared__ MeShared S;
+    __shared__ typename MeStatic<PHASE>::type S;
     const MeJobDev &J = jobs[blockIdx.y];
     /* XCD-aware placement: workgroups are dealt round-robin to the 8 XCDs (gridDim.x is a multiple of 8), so
      * XCD x gets blockIdx.x = x, x+8, ...; give it a CONTIGUOUS run of LCUs - neighbouring LCUs share most of
@@ -703,6 +716,7 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
     MeCarry *__restrict__ carry = &J.carry[lcu];
     SvtAmdMeLcuResult *o = &out[lcu];
     MeSearch &B = *(MeSearch *)g_pool; /* PHASE 1 only */
+    MeSearchSsd &BS = *(MeSearchSsd *)(g_pool + ME_SEARCH_BYTES); /* ... and there only under SVT_AMD_SSD_SEARCH */
     const PicView &R = list ? ref1 : ref0;
     (void)method;
 
@@ -722,7 +736,7 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
     const bool tsab_early = PHASE == 0 && (P.temporal_layer_index > 0 || list == 0) && P.update_hme_search_center && lw == LCU;
     const int tsab_nc = list == 1 ? 6 : 5;
     uint4 tsab_b[3];
-    if (PHASE == 0) {
+    if constexpr (PHASE == 0) {
         uint32_t sv[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -769,7 +783,7 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
 
     LWin wF, wB, wH, wJ; /* LDS windows of the current list's reference planes */
 
-    if (PHASE == 0) {
+    if constexpr (PHASE == 0) {
         int hme_init_done = list ? carry->hme_init_done : 0;
         int zero_sad_valid = 0;
         if (P.temporal_layer_index > 0 || list == 0) {
@@ -1016,12 +1030,13 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
             uint32_t i_sad = 0, i_mv = 0;
             if (list && t < 85)
                 i_sad = o->best_sad[0][t], i_mv = o->best_mv[0][t];
-            int wa = ((wx1 - (wx0 - 2)) + 15) & ~15;
-            if (!((wa >> 4) & 1))
-                wa += 16;
+            const int wa = me_f_pitch(wx1 - (wx0 - 2));
             const int n16 = wa >> 4, rows = wy1 - wy0, total = rows * n16;
             const uint32_t rc = (1u << 20) / (uint32_t)n16 + 1u;
-            uint8_t *dst = g_pool + ME_SEARCH_BYTES;
+            /* pool order: MeSearch, MeSearchSsd, the b / h / j windows, the F window LAST: an LDS-DMA wave instruction addresses 1 KiB of LDS from its base whatever lanes
+             * are active, and the last, partial chunk of the j window must not reach past the workgroup's allocation - behind it lies the F window, never less than 1 KiB */
+            const int hp_off = ME_SEARCH_BYTES + (method == SVT_AMD_SSD_SEARCH ? ME_SEARCH_SSD_BYTES : 0);
+            uint8_t *dst = g_pool + hp_off + 3 * (wy1 - wy0) * me_hp_pitch(wx1 - (wx0 & ~3));
             wF.p = dst, wF.x0 = wx0 - 2, wF.y0 = wy0, wF.stride = wa;
             uint4 fw[ME_F_ITEMS];
 #pragma unroll
@@ -1034,10 +1049,12 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
             }
             *(uint4 *)&S.src[(t >> 2) * LCU + ((t & 3) << 4)] = sv;
             if (t < 85) {
-                B.best_sad[list][t] = 0, B.best_mv[list][t] = 0, B.best_ssd[list][t] = 0, B.dir[list][t] = 0;
+                B.best_sad[list][t] = 0, B.best_mv[list][t] = 0, B.dir[list][t] = 0;
                 /* the other list: zero for a one-list picture, list 0's final result for list 1 */
                 B.best_sad[1 - list][t] = i_sad, B.best_mv[1 - list][t] = i_mv;
-                B.best_ssd[1 - list][t] = 0, B.dir[1 - list][t] = 0;
+                B.dir[1 - list][t] = 0;
+                if (method == SVT_AMD_SSD_SEARCH)
+                    BS.best_ssd[list][t] = 0, BS.best_ssd[1 - list][t] = 0;
                 B.bipred[t] = 0;
                 B.key[t] = 0xffffffffu;
             }
@@ -1046,14 +1063,19 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
 #pragma unroll
             for (int k = 0; k < ME_F_ITEMS; k++) {
                 const int i = t + k * NT;
-                if (i < total)
-                    *(uint4 *)(dst + i * 16) = fw[k];
+                if (i < total) {
+                    const int r = (int)(((uint32_t)i * rc) >> 20), c = i - r * n16;
+                    uint32_t *d4 = (uint32_t *)(dst + r * wa + c * 16); /* rows start on a dword, not on 16 bytes */
+                    d4[0] = fw[k].x, d4[1] = fw[k].y, d4[2] = fw[k].z, d4[3] = fw[k].w;
+                }
             }
             for (int i = t + ME_F_ITEMS * NT; i < total; i += NT) { /* search areas beyond 48 x 48: the rest of the window the plain way */
                 const int r = (int)(((uint32_t)i * rc) >> 20), c = i - r * n16;
-                *(uint4 *)(dst + i * 16) = ldu16(R.full + (ptrdiff_t)(wy0 + r) * R.pitch_full + (wx0 - 2) + c * 16);
+                const uint4 v = ldu16(R.full + (ptrdiff_t)(wy0 + r) * R.pitch_full + (wx0 - 2) + c * 16);
+                uint32_t *d4 = (uint32_t *)(dst + r * wa + c * 16);
+                d4[0] = v.x, d4[1] = v.y, d4[2] = v.z, d4[3] = v.w;
             }
-            win_off = ME_SEARCH_BYTES + rows * wa;
+            win_off = hp_off;
         }
         LDS_BARRIER(); /* source, F window, search state are in LDS (their global loads are waited for by the stores that carry them) */
 
@@ -1254,6 +1276,7 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
 #if ME_EXP >= 10
             STAMP(2);
 #endif
+            int vx = 0, vy = 0, vs = 0; /* PU t's vector and SAD: what SuPelEnable sums per tier */
             if (t < 85) {
                 uint32_t s;
                 int p;
@@ -1268,8 +1291,28 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                     p = (int)(k & 0x3fff);
                 }
                 const int sy = (int)fastdiv((uint32_t)p, rcs), sx = p - sy * saw;
+                const uint32_t mv = mvpack((sx + sox) * 4, (sy + soy) * 4);
                 B.best_sad[list][t] = 2 * s;
-                B.best_mv[list][t] = mvpack((sx + sox) * 4, (sy + soy) * 4);
+                B.best_mv[list][t] = mv;
+                vx = mvx(mv), vy = mvy(mv), vs = (int)(2 * s);
+            }
+            /* SuPelEnable (:3035-3361), the sums: PU t's values are in thread t's registers - 32x32 PUs in lanes 1..4 and 16x16 PUs in lanes 5..20 of wave 0, 8x8 PUs in
+             * lanes 21..63 of wave 0 and 0..20 of wave 1: masked wave sums, and the flags are evaluated by every thread behind the barrier that ends this stage */
+            if (P.fractional_search_model == 1 && t < 128) {
+                const bool in8 = t >= 21 && t < 85;
+                const int s8x = (int)wave_sum((uint32_t)(in8 ? vx : 0)), s8y = (int)wave_sum((uint32_t)(in8 ? vy : 0)), s8s = (int)wave_sum((uint32_t)(in8 ? vs : 0));
+                if (t < 64) {
+                    const bool in32 = t >= 1 && t < 5, in16 = t >= 5 && t < 21;
+                    const int s32x = (int)wave_sum((uint32_t)(in32 ? vx : 0)), s32y = (int)wave_sum((uint32_t)(in32 ? vy : 0)), s32s = (int)wave_sum((uint32_t)(in32 ? vs : 0));
+                    const int s16x = (int)wave_sum((uint32_t)(in16 ? vx : 0)), s16y = (int)wave_sum((uint32_t)(in16 ? vy : 0)), s16s = (int)wave_sum((uint32_t)(in16 ? vs : 0));
+                    if (t == 0) {
+                        B.sums[0] = s32x, B.sums[1] = s32y, B.sums[2] = s32s;
+                        B.sums[3] = s16x, B.sums[4] = s16y, B.sums[5] = s16s;
+                        B.sums[6] = s8x, B.sums[7] = s8y, B.sums[8] = s8s;
+                    }
+                } else if (t == 64) {
+                    B.sums[9] = s8x, B.sums[10] = s8y, B.sums[11] = s8s;
+                }
             }
             STAMP(14);
             __builtin_amdgcn_s_waitcnt(0); /* sub-pel windows landed (LDS-DMA issued before the search) */
@@ -1278,65 +1321,36 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
 
         STAMP(7);
         /* ---- sub-pel (:4236-4318) ---- */
-        /* SuPelEnable (:3035-3361): tier sums of MV components and SADs, one PU per thread */
-        if (P.fractional_search_model == 1) {
-            /* wave 0 speaks for the 64 8x8 PUs (21..84); wave 1: lanes 0..15 the 16x16 PUs (5..20), lanes 16..19 the 32x32 PUs (1..4), the rest of its first 32 lanes
-             * zeros - xor-shuffle sums (steps 1, 2, 4, 8 inside 16 lanes; 16, 32 as well in wave 0) instead of 252 LDS atomics on 9 addresses */
-            if (t < 128) {
-                const int lane = t & 63, n = t < 64 ? 21 + lane : lane < 16 ? 5 + lane : lane < 20 ? lane - 15 : -1;
-                int vx = 0, vy = 0, vs = 0;
-                if (n >= 0)
-                    vx = mvx(B.best_mv[list][n]), vy = mvy(B.best_mv[list][n]), vs = (int)B.best_sad[list][n];
-                if (t < 64) {
-                    vx = (int)wave_sum((uint32_t)vx), vy = (int)wave_sum((uint32_t)vy), vs = (int)wave_sum((uint32_t)vs);
-                } else {
-                    vx = (int)group_sum<16>((uint32_t)vx), vy = (int)group_sum<16>((uint32_t)vy), vs = (int)group_sum<16>((uint32_t)vs);
-                }
-                if (t == 0 || t == 64 || t == 80) {
-                    const int tier = t == 0 ? 2 : t == 64 ? 1 : 0;
-                    B.sums[tier * 3 + 0] = vx, B.sums[tier * 3 + 1] = vy, B.sums[tier * 3 + 2] = vs;
-                }
-            }
-            __syncthreads();
+        /* SuPelEnable, the decision: every thread evaluates the same scalars */
+        int e32 = 0, e16 = 0, e8 = 0, eq = 0;
+        if (P.fractional_search_model == 0) {
+            e32 = e16 = e8 = eq = 1;
+        } else if (P.fractional_search_model == 1) {
+            const int sx32 = B.sums[0], sy32 = B.sums[1], ss32 = B.sums[2], ss16 = B.sums[5];
+            const int sx8 = B.sums[6] + B.sums[9], sy8 = B.sums[7] + B.sums[10], ss8 = B.sums[8] + B.sums[11];
+            const uint32_t ux32 = (uint32_t)(sx32 >> 2), uy32 = (uint32_t)(sy32 >> 2), ux8 = (uint32_t)(sx8 >> 6), uy8 = (uint32_t)(sy8 >> 6);
+            const uint32_t mag32 = ux32 * ux32 + uy32 * uy32, mag8 = ux8 * ux8 + uy8 * uy8;
+            const uint32_t avg32 = (uint32_t)ss32 >> 2, avg16 = (uint32_t)ss16 >> 4, avg8 = (uint32_t)ss8 >> 6;
+            const int tl = P.temporal_layer_index;
+            const uint32_t th = tl == 0 ? 48 * 48 : tl == 1 ? 32 * 32 : tl == 2 ? 80 * 80 : 48 * 48;
+            const int small32 = mag32 < th, low32 = avg32 < 32 * 32 * 6;
+            e32 = (tl == 0 || tl == 2) ? low32 : (tl == 1 ? (small32 ? low32 : 1) : (small32 ? 1 : low32));
+            e16 = !(avg16 < 16 * 16 * 2);
+            e8 = (tl <= 2) ? !(avg8 < 8 * 8 * 2) : ((mag8 < th) ? !(avg8 < 8 * 8 * 2) : 0);
+            eq = 1;
         }
-        if (t == 0) {
-            int e32 = 0, e16 = 0, e8 = 0, eq = 0;
-            if (P.fractional_search_model == 0) {
-                e32 = e16 = e8 = eq = 1;
-            } else if (P.fractional_search_model == 1) {
-                const int shift[3] = {2, 4, 6};
-                uint32_t mag[3], avgsad[3];
-#pragma unroll
-                for (int tt = 0; tt < 3; tt++) {
-                    const uint32_t ux = (uint32_t)(B.sums[tt * 3 + 0] >> shift[tt]), uy = (uint32_t)(B.sums[tt * 3 + 1] >> shift[tt]);
-                    mag[tt] = ux * ux + uy * uy;
-                    avgsad[tt] = (uint32_t)B.sums[tt * 3 + 2] >> shift[tt];
-                }
-                const int tl = P.temporal_layer_index;
-                const uint32_t th = tl == 0 ? 48 * 48 : tl == 1 ? 32 * 32 : tl == 2 ? 80 * 80 : 48 * 48;
-                const int small32 = mag[0] < th, low32 = avgsad[0] < 32 * 32 * 6;
-                e32 = (tl == 0 || tl == 2) ? low32 : (tl == 1 ? (small32 ? low32 : 1) : (small32 ? 1 : low32));
-                e16 = !(avgsad[1] < 16 * 16 * 2);
-                e8 = (tl <= 2) ? !(avgsad[2] < 8 * 8 * 2) : ((mag[2] < th) ? !(avgsad[2] < 8 * 8 * 2) : 0);
-                eq = 1;
-            }
-            B.e32 = e32, B.e16 = e16 && P.cu16x16_mode == 0, B.e8 = e8 && P.cu8x8_mode != 1, B.eq = eq;
-        }
-        __syncthreads();
-        const int any_sub = B.e32 || B.e16 || B.e8 || B.eq || 0;
+        e16 = e16 && P.cu16x16_mode == 0, e8 = e8 && P.cu8x8_mode != 1;
+        const int any_sub = e32 || e16 || e8 || eq || 0;
         const int run_sub = (P.fractional_search_model != 2) && any_sub;
         if (run_sub) {
             const int f64 = P.fractional_search_64x64;
-            const int en0 = f64, en1 = B.e32, en2 = B.e16, en3 = B.e8;
+            const int en0 = f64, en1 = e32, en2 = e16, en3 = e8;
 #define EN(tier_) pick4(tier_, en0, en1, en2, en3)
             const int rstep = (method == SVT_AMD_SUB_SAD_SEARCH) ? 2 : 1;
             STAMP(8);
             /* ===== half-pel: EbHevcHalfPelSearch_LCU / PU_HalfPelRefinement (:733-1187) ===== */
-            for (int i = t; i < 85 * 8; i += NT) {
-                (&B.dist[0][0])[i] = 0;
-                (&B.dsad[0][0])[i] = 0;
-            }
-            __syncthreads();
+            /* B.dist / BS.dsad are not cleared: every (PU, k) cell the decision below reads - all eight k of the PUs of an enabled tier - is written exactly once by this
+             * stage, and the last reads of B.sad32 (the same bytes) are behind the barriers of the full-pel stage */
             /* item = (PU, position k, row chunk): chunk counts {32, 8, 2, 1} per tier give every lane the same
              * ~16 dword SADs; the chunks of one (PU, k) sit on adjacent lanes and are summed with a segmented
              * shuffle, so B.dist is written once per (PU, k) - no LDS atomics. */
@@ -1392,7 +1406,8 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                         sd = group_sum_rt(sd, lc);
                     if (ch == 0) {
                         B.dist[n][k] = d;
-                        B.dsad[n][k] = sd;
+                        if (method == SVT_AMD_SSD_SEARCH)
+                            BS.dsad[n][k] = sd;
                     }
                 }
             }
@@ -1415,7 +1430,7 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                             lds_ld_unaligned<2>(r + x, v);
                             d += ssd4(*(const uint32_t *)(s + x), v[0]) + ssd4(*(const uint32_t *)(s + x + 4), v[1]);
                         }
-                        atomicAdd(&B.best_ssd[list][n], d);
+                        atomicAdd(&BS.best_ssd[list][n], d);
                     }
                 }
             }
@@ -1425,14 +1440,14 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                 if (EN(tier)) {
                     const int mdx[8] = {-2, 2, 0, 0, -2, 2, 2, -2}, mdy[8] = {0, 0, -2, 2, -2, -2, 2, 2};
                     const uint32_t mv0 = B.best_mv[list][t];
-                    uint32_t bsad = B.best_sad[list][t], bmv = mv0, bssd = B.best_ssd[list][t];
+                    uint32_t bsad = B.best_sad[list][t], bmv = mv0, bssd = method == SVT_AMD_SSD_SEARCH ? BS.best_ssd[list][t] : 0u;
                     uint32_t dmin = 0xffffffffu;
                     for (int k = 0; k < 8; k++) {
                         const uint32_t d = (method == SVT_AMD_SUB_SAD_SEARCH) ? (B.dist[t][k] << 1) : B.dist[t][k];
                         dmin = d < dmin ? d : dmin;
                         if (method == SVT_AMD_SSD_SEARCH) {
                             if (d < bssd)
-                                bsad = B.dsad[t][k], bmv = mvpack(mvx(mv0) + mdx[k], mvy(mv0) + mdy[k]), bssd = d;
+                                bsad = BS.dsad[t][k], bmv = mvpack(mvx(mv0) + mdx[k], mvy(mv0) + mdy[k]), bssd = d;
                         } else if (d < bsad) {
                             bsad = d, bmv = mvpack(mvx(mv0) + mdx[k], mvy(mv0) + mdy[k]);
                         }
@@ -1446,7 +1461,9 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                         if (d == dmin)
                             dirv = code[chk[i]];
                     }
-                    B.best_sad[list][t] = bsad, B.best_mv[list][t] = bmv, B.best_ssd[list][t] = bssd;
+                    B.best_sad[list][t] = bsad, B.best_mv[list][t] = bmv;
+                    if (method == SVT_AMD_SSD_SEARCH)
+                        BS.best_ssd[list][t] = bssd;
                     B.dir[list][t] = dirv;
                 }
             }
@@ -1454,26 +1471,31 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
 
             STAMP(9);
             /* ===== quarter-pel: QuarterPelSearch_LCU / PU_QuarterPelRefinementOnTheFly (:1226-1846) ===== */
-            const int qen0 = f64, qen1 = B.eq && B.e32, qen2 = B.eq && B.e16, qen3 = B.eq && B.e8;
+            const int qen0 = f64, qen1 = eq && e32, qen2 = eq && e16, qen3 = eq && e8;
 #define QEN(tier_) pick4(tier_, qen0, qen1, qen2, qen3)
-            for (int i = t; i < 85 * 8; i += NT) {
-                (&B.dist[0][0])[i] = 0;
-                (&B.dsad[0][0])[i] = 0;
-            }
-            __syncthreads();
+            /* B.dist / BS.dsad are not cleared here either: the decision below reads, of a PU of an enabled tier, the cells k whose direction code is the half-pel winner's
+             * - 1, + 0, + 1 (+ 4 on a half-pel vector) - the three this stage writes, each once (k = the position index of code, kcode[k] == code) */
             /* only the three positions next to the half-pel winner are evaluated (:1252-1273): item =
              * (PU, j in 0..2, row chunk); position code = winner direction + j - 1 on the ring
-             * TL,T,TR,R,BR,B,BL,L (mirrored when the MV already sits on a half-pel position). */
-            for (int tier = 0; tier < 4; tier++) {
-                if (!QEN(tier))
-                    continue;
-                const int sz = tier == 0 ? 32 : tier_sz_of(tier); /* the 64x64 call passes 32x32 (:1677) */
-                const int lc = tier == 0 ? 3 : tier_lc_of(tier), rows = sz >> (rstep - 1), rpc = rows >> lc;
-                const int items = tier_cnt_of(tier) * 3 << lc;
-                for (int i0 = 0; i0 < items; i0 += NT) { /* uniform trips: whole waves join the shuffles */
+             * TL,T,TR,R,BR,B,BL,L (mirrored when the MV already sits on a half-pel position).
+             * All enabled tiers in ONE index space, as in the bi-prediction stage below: 24, 96, 96 and 192 items, every one of eight 8- or 16-byte segments, each tier's
+             * share rounded up to whole waves (the chunk sums are wave shuffles of a wave-uniform width) - two trips of the workgroup at most instead of one per tier. */
+            int qcum[5];
+            qcum[0] = 0;
+#pragma unroll
+            for (int tier = 0; tier < 4; tier++)
+                qcum[tier + 1] = qcum[tier] + (QEN(tier) ? (((tier_cnt_of(tier) * 3 << (tier == 0 ? 3 : tier_lc_of(tier))) + 63) & ~63) : 0);
+            {
+                for (int i0 = 0; i0 < qcum[4]; i0 += NT) {
                     const int i = i0 + t;
-                    const bool live = i < items;
-                    const int ii = live ? i : 0;
+                    if (i >= qcum[4]) /* whole waves */
+                        continue;
+                    const int tier = __builtin_amdgcn_readfirstlane(i < qcum[1] ? 0 : i < qcum[2] ? 1 : i < qcum[3] ? 2 : 3);
+                    const int sz = tier == 0 ? 32 : tier_sz_of(tier); /* the 64x64 call passes 32x32 (:1677) */
+                    const int lc = tier == 0 ? 3 : tier_lc_of(tier), rows = sz >> (rstep - 1), rpc = rows >> lc;
+                    const int items = tier_cnt_of(tier) * 3 << lc, ti = i - pick4(tier, qcum[0], qcum[1], qcum[2], qcum[3]);
+                    const bool live = ti < items;
+                    const int ii = live ? ti : 0;
                     const int ch = ii & ((1 << lc) - 1), pj = ii >> lc, pidx = pj / 3, j = pj - pidx * 3;
                     const int n = tier_first_of(tier) + pidx;
                     int px_, py_, psz;
@@ -1532,7 +1554,8 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                         sdv = group_sum_rt(sdv, lc);
                     if (live && ch == 0) {
                         B.dist[n][k] = d;
-                        B.dsad[n][k] = sdv;
+                        if (method == SVT_AMD_SSD_SEARCH)
+                            BS.dsad[n][k] = sdv;
                     }
                 }
             }
@@ -1545,7 +1568,7 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                     const uint32_t mv0 = B.best_mv[list][t];
                     const int qm = (mvy(mv0) & 2) + ((mvx(mv0) & 2) >> 1);
                     const int sd = B.dir[list][t];
-                    uint32_t bsad = B.best_sad[list][t], bmv = mv0, bssd = B.best_ssd[list][t];
+                    uint32_t bsad = B.best_sad[list][t], bmv = mv0, bssd = method == SVT_AMD_SSD_SEARCH ? BS.best_ssd[list][t] : 0u;
                     for (int k = 0; k < 8; k++) {
                         const int target = qm ? ((kcode[k] + 4) & 7) : kcode[k];
                         const int diff = (sd - target) & 7;
@@ -1554,12 +1577,14 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
                         const uint32_t d = (method == SVT_AMD_SUB_SAD_SEARCH) ? (B.dist[t][k] << 1) : B.dist[t][k];
                         if (method == SVT_AMD_SSD_SEARCH) {
                             if (d < bssd)
-                                bsad = B.dsad[t][k], bmv = mvpack(mvx(mv0) + mdx[k], mvy(mv0) + mdy[k]), bssd = d;
+                                bsad = BS.dsad[t][k], bmv = mvpack(mvx(mv0) + mdx[k], mvy(mv0) + mdy[k]), bssd = d;
                         } else if (d < bsad) {
                             bsad = d, bmv = mvpack(mvx(mv0) + mdx[k], mvy(mv0) + mdy[k]);
                         }
                     }
-                    B.best_sad[list][t] = bsad, B.best_mv[list][t] = bmv, B.best_ssd[list][t] = bssd;
+                    B.best_sad[list][t] = bsad, B.best_mv[list][t] = bmv;
+                    if (method == SVT_AMD_SSD_SEARCH)
+                        BS.best_ssd[list][t] = bssd;
                 }
             }
             __syncthreads();
@@ -1741,7 +1766,7 @@ __global__ __launch_bounds__(NT, PHASE == 0 ? ME_HME_WAVES_PER_SIMD : ME_MIN_WAV
 }
 
 /* upper bounds of the dynamic LDS pools a job needs: HME kernel = the largest per-level window set;
- * search kernel = MeSearch + the four staged search windows */
+ * search kernel = MeSearch (+ MeSearchSsd under the SSD search method) + the four staged search windows */
 static void me_pool_bytes(const SvtAmdMeParams *p, size_t *hme_pool, size_t *search_pool)
 {
     auto win = [](int w, int rows) { return (size_t)((w + 30) & ~15) * (size_t)rows; };
@@ -1775,16 +1800,28 @@ static void me_pool_bytes(const SvtAmdMeParams *p, size_t *hme_pool, size_t *sea
     *hme_pool = (need + 64 + 255) & ~(size_t)255; /* +64: the aligned over-read of the last window row */
     const int saw = p->search_area_width > 127 ? 127 : p->search_area_width;
     const int sah = p->search_area_height > 127 ? 127 : p->search_area_height;
-    /* the four search windows are staged with an odd 16-byte pitch (win_pitch(.., 1)): the widest a window of w columns gets is
-     * w + 15 (alignment of its first column) rounded up to 16 and then to an odd multiple.  The bound is exact on purpose: at
-     * BASELINE configs[2] (16 x 9 search) it is what lets a third workgroup share a CU's 160 KiB. */
-    auto win_odd = [](int w, int rows) {
-        int wa = (w + 15 + 15) & ~15;
-        if (!((wa >> 4) & 1))
-            wa += 16;
-        return (size_t)wa * (size_t)rows;
-    };
-    *search_pool = ((size_t)ME_SEARCH_BYTES + 4 * win_odd(saw + 67, sah + 67) + 64 + 255) & ~(size_t)255;
+    /* the search kernel's pool as k_me<1> lays it out: MeSearch, MeSearchSsd (SSD search only), the b / h / j windows (saw + 67 columns, up to three more in front:
+     * their first column is a dword boundary of the plane), the F window (saw + 69 columns from four samples left of search position 0), sah + 67 rows each; the
+     * clamps of the search area only make them smaller.  The bound is exact on purpose: at BASELINE configs[2] (16 x 9 search, SAD) pool + static state are
+     * 36,096 + 4,112 B, which is what lets a fourth workgroup share a CU's 160 KiB. */
+    const size_t rows = (size_t)sah + 67;
+    const size_t fwin = ((size_t)me_f_pitch(saw + 69) * rows + 15) & ~(size_t)15, hwin = (size_t)me_hp_pitch(saw + 67 + 3) * rows;
+    const size_t ssd = p->fractional_search_method == SVT_AMD_SSD_SEARCH ? (size_t)ME_SEARCH_SSD_BYTES : 0;
+    *search_pool = ((size_t)ME_SEARCH_BYTES + ssd + fwin + 3 * hwin + 64 + 255) & ~(size_t)255; /* +64: the aligned over-read of the last window row */
+}
+
+/* static + dynamic LDS bytes of a workgroup of k_me<phase> for a job with these controls; with p == NULL what the last launch requested (the compiler's static size
+ * and the launcher's pool: tests/test_gpu_me_lds.py holds the two against each other) */
+static size_t g_me_last_lds[2];
+extern "C" int svt_amd_debug_me_kernel_lds_bytes(const SvtAmdMeParams *p, int phase)
+{
+    if (phase != 0 && phase != 1)
+        return SVT_AMD_ERR_BAD_PARAM;
+    if (!p)
+        return (int)g_me_last_lds[phase];
+    size_t pool[2];
+    me_pool_bytes(p, &pool[0], &pool[1]);
+    return (int)(pool[phase] + (phase ? sizeof(MeSearchShared) : sizeof(MeShared)));
 }
 
 int svt_amd_launch_me_batch(SvtAmdContext *ctx, const MeJobDev *host_jobs, int njobs, int max_lcus)
@@ -1800,15 +1837,22 @@ int svt_amd_launch_me_batch(SvtAmdContext *ctx, const MeJobDev *host_jobs, int n
         pool1 = b > pool1 ? b : pool1;
         max_lists = host_jobs[i].P.num_lists > max_lists ? host_jobs[i].P.num_lists : max_lists;
     }
-    if (pool1 + sizeof(MeShared) > 160 * 1024 || pool0 + sizeof(MeShared) > 160 * 1024) {
-        svt_amd_set_error("motion estimation: search windows need %zu B of LDS (> 160 KiB)", pool1 + sizeof(MeShared));
+    if (pool1 + sizeof(MeSearchShared) > 160 * 1024 || pool0 + sizeof(MeShared) > 160 * 1024) {
+        svt_amd_set_error("motion estimation: search windows need %zu B of LDS (> 160 KiB)", pool1 + sizeof(MeSearchShared));
         return SVT_AMD_ERR_BAD_PARAM;
     }
     {   /* dynamic-LDS limits of the two kernels: high-water marks PER DEVICE (function attributes are per device) */
         static std::mutex mu;
-        static size_t attr0[64], attr1[64];
+        static size_t attr0[64], attr1[64], stat0[64], stat1[64];
         std::lock_guard<std::mutex> g(mu);
         const int dv = ctx->device & 63;
+        if (!stat1[dv]) { /* the kernels' static LDS as the compiler laid it out (svt_amd_debug_me_kernel_lds_bytes) */
+            hipFuncAttributes fa0, fa1;
+            HIP_TRY(hipFuncGetAttributes(&fa0, (const void *)k_me<0>));
+            HIP_TRY(hipFuncGetAttributes(&fa1, (const void *)k_me<1>));
+            stat0[dv] = fa0.sharedSizeBytes, stat1[dv] = fa1.sharedSizeBytes;
+        }
+        g_me_last_lds[0] = stat0[dv] + pool0, g_me_last_lds[1] = stat1[dv] + pool1;
         if (pool0 > attr0[dv]) {
             HIP_TRY(hipFuncSetAttribute((const void *)k_me<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pool0));
             attr0[dv] = pool0;

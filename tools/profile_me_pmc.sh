@@ -43,8 +43,10 @@ with open(O + "/me_pmc.txt", "w") as out:
             wc = a["SQ_WAVE_CYCLES"]
             print("  of wave cycles: wait_any %.2f wait_inst_any %.2f active_any %.2f active_valu %.2f active_lds %.2f active_sca %.2f" % tuple(
                 a.get(c, 0) / wc for c in ("SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_ACTIVE_INST_ANY", "SQ_ACTIVE_INST_VALU", "SQ_ACTIVE_INST_LDS", "SQ_ACTIVE_INST_SCA")), file=out)
+            if a.get("SQ_BUSY_CYCLES"):  # resident waves: the ratio is 7.5 per workgroup a CU (22.8 at three workgroups, 30.0 at four: profiles/r10_*_me_pmc.txt)
+                print("  wave cycles / busy cycles %.2f" % (wc / a["SQ_BUSY_CYCLES"]), file=out)
         if a.get("SQ_LDS_IDX_ACTIVE"):
-            print("  LDS bank conflict cycles / active %.2f" % (a["SQ_LDS_BANK_CONFLICT"] / a["SQ_LDS_IDX_ACTIVE"]), file=out)
+            print("  LDS bank conflict cycles / active %.3f" % (a["SQ_LDS_BANK_CONFLICT"] / a["SQ_LDS_IDX_ACTIVE"]), file=out)
         if "FETCH_SIZE" in a:
             print("  FETCH_SIZE %.1f MB raw (x2 gfx950 correction: %.1f MB)  WRITE_SIZE %.1f MB" % (a["FETCH_SIZE"] / 1024, a["FETCH_SIZE"] / 512, a.get("WRITE_SIZE", 0) / 1024), file=out)
 print(open(O + "/me_pmc.txt").read())
