@@ -454,6 +454,110 @@ SVT_AMD_API int svt_amd_side_stats_batch_launch(SvtAmdContext *ctx, const SvtAmd
 #define SVT_AMD_SIDE_SUM_LUMA    5
 SVT_AMD_API size_t svt_amd_side_stats_bytes(uint16_t luma_width, uint16_t luma_height, int which, int regions_w, int regions_h);
 
+/*
+ * Batched chroma statistics: the chroma half of GatheringPictureStatistics (Codec/EbPictureAnalysisProcess.c:3995) for up to 256 pictures of ONE geometry per
+ * call, stream-ordered on the context's lane like svt_amd_side_stats_batch_launch - the call never blocks and never copies to the host.  A batch of one picture
+ * is the single-picture form.
+ *   means           ComputeChromaBlockMean (:1448) / ZeroOutChromaBlockMean (:1383): per LCU cb_mean[21] / cr_mean[21] in ME_TIER_ZERO_PU order (64x64, four
+ *                   32x32, sixteen 16x16, each raster).  A 16x16 luma unit is an 8x8 chroma block; its mean is ComputeSubMean8x8_SSE2_INTRIN
+ *                   (ASM_SSE2/EbComputeMean_Intrinsic_SSE2.c:53): the sum of rows 0, 2, 4 and 6 << 3, MEAN_PRECISION (8) fractional bits; 32x32 and 64x64 are averaged
+ *                   up the tree with >> 2.  As in the reference, the 64x64 mean adds 32x32 block 3 twice and never reads block 2 (:1586-1587).  LCUs the picture
+ *                   does not cover completely get zeros.  One wave per LCU, a lane per 8x8 chroma block of one plane (v_sad_u8), the tree by lane shuffles.
+ *   histogram, region_average, sum_chroma
+ *                   SubSampleChromaGeneratePixelIntensityHistogramBins (:3440) with CalculateHistogram (:204) at decimStep 4: regions are cut on the LUMA
+ *                   dimensions (width / regions_w, the remainder to the last region); the chroma origin is the luma region origin >> 1 and the area the luma
+ *                   region size >> 1; every 4th sample of every 4th row is counted; bins start at 1, bins and sums end << 4.  region_average has the rounding
+ *                   of :3491 (divisor area >> 2, rounding term area >> 3, truncated to a byte); sum_chroma holds the two sums CalculateInputAverageIntensity
+ *                   (:3983-3984) divides.  Index 0 of every [2] is Cb, 1 is Cr.
+ * cb / cr: DEVICE pointers to sample (0,0) of the 8-bit, unpadded 4:2:0 planes of the input picture (luma_width / 2 x luma_height / 2 samples, `pitch` bytes a
+ * row for both, any alignment).  The caller puts them there (svt_amd_device_upload_async) or already has them; picture slots are not touched, and ORDERING AGAINST
+ * WHATEVER WROTE THE PLANES IS THE CALLER'S: queue the call on the lane that wrote them, or behind svt_amd_lane_event_record / _wait.  A job that wants
+ * neither result reads no plane (cb / cr may be NULL).  The arrays are DEVICE memory, picture i of the batch at i times svt_amd_chroma_stats_bytes(...) bytes of each; a picture that does not want a result
+ * leaves its part of that array untouched; the histogram and sum_chroma parts the kernels accumulate into are zeroed by the call.  Everything is checked before
+ * anything is queued: a job that wants a result whose array is NULL, a plane pointer without the other, a pitch below luma_width / 2, odd or zero dimensions, or
+ * regions that do not fit (more than 64, or a region below 8 luma samples a side) return SVT_AMD_ERR_BAD_PARAM (svt_amd_last_error names the job) and queue nothing.
+ */
+typedef struct SvtAmdPaLcuChroma {
+    uint8_t cb_mean[21];        /* pictureControlSetPtr->cbMean[lcu][0..20] */
+    uint8_t cr_mean[21];        /* pictureControlSetPtr->crMean[lcu][0..20] */
+    uint8_t pad[6];             /* 0 */
+} SvtAmdPaLcuChroma;            /* 48 bytes */
+typedef struct SvtAmdChromaJob {
+    const uint8_t *cb, *cr;     /* DEVICE; only read when the job wants a result */
+    uint32_t pitch;             /* bytes a row, both planes */
+    uint8_t want_means, want_histogram, pad[2];
+} SvtAmdChromaJob;              /* 24 bytes */
+typedef struct SvtAmdChromaArrays {        /* DEVICE pointers, picture i of the batch at index i; any may be NULL */
+    SvtAmdPaLcuChroma *means;              /* [n][lcus]                           cbMean / crMean (EbPictureAnalysisProcess.c:1448)          */
+    uint32_t          *histogram;          /* [n][regions_w][regions_h][2][256]   pictureHistogram[..][..][1..2] (:3440)                     */
+    uint8_t           *region_average;     /* [n][64][2], regions in [regions_w][regions_h] order, the rest 0   averageIntensityPerRegion[..][..][1..2] (:3491) */
+    uint64_t          *sum_chroma;         /* [n][2]                              sumAverageIntensityTotalRegionsCb / Cr (:3490, :3983-3984) */
+} SvtAmdChromaArrays;
+SVT_AMD_API int svt_amd_chroma_stats_batch_launch(SvtAmdContext *ctx, const SvtAmdChromaJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
+                                                  int regions_w, int regions_h, const SvtAmdChromaArrays *out);
+#define SVT_AMD_CHROMA_MEANS      0
+#define SVT_AMD_CHROMA_HISTOGRAM  1
+#define SVT_AMD_CHROMA_REGION_AVG 2
+#define SVT_AMD_CHROMA_SUM        3
+/* bytes ONE picture takes in array `which`; 0 for an unknown `which` or bad regions.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_chroma_stats_bytes(uint16_t luma_width, uint16_t luma_height, int which, int regions_w, int regions_h);
+
+/*
+ * Batched picture detectors: what ComputePictureSpatialStatistics (Codec/EbPictureAnalysisProcess.c:3879) derives from the block statistics, for up to 256 pictures of
+ * ONE geometry per call, stream-ordered on the context's lane, never blocking, never copying to the host.  A batch of one picture is the single-picture form.
+ *   stats           DEVICE, required: the SvtAmdPaLcuStats[lcus] svt_amd_side_stats_batch_launch left (same lane: no further ordering needed)
+ *   chroma          DEVICE or NULL: the SvtAmdPaLcuChroma[lcus] of svt_amd_chroma_stats_batch_launch; required only with want_edge16
+ *   want_edge16     the reference computes the 16x16 edge map only when (pictureNumber & 3) == 0 and clears it otherwise (:3535): that rule is the caller's
+ *   resolution_class  SequenceControlSet_t.inputResolution (0 = 576p range or lower .. 3 = 4K range, Codec/EbSequenceControlSet.c:288): it selects the
+ *                   potentialLogoLcu map, which is derived on the device from the geometry as Codec/EbSequenceControlSet.c:216-273 does
+ * Per picture: pic_avg_variance (:3930-3933) = the sum of the 64x64 variances of ALL LCUs / the LCU count, truncated to 16 bits.
+ * DetermineHomogeneousRegionInPicture (:3751): var_of_var_32x32 (all-ones for incomplete LCUs) and homogeneous (1 for incomplete LCUs); very_low_var_pic and
+ * logo_pic are counted over complete LCUs only.  The squares of the 16-bit variances are summed in 64 bits, then >> 4 (32x32) / >> 6 (64x64); the subtraction is
+ * unsigned 64-bit as written, so a mean square below the squared mean wraps.
+ * EdgeDetection (:3627), restated as it is: edge_block_num (the 64x64 variance above 70 % of pic_avg_variance), sharp_edge (variance above 200 with more than four
+ * 16x16 variances below 20) and lcu_block_percentage for LCUs with a neighbour on every side; the high-intensity test (mean above 180 next to a mean below 120)
+ * for LCUs with four LCUs on every side.  isolated_high_intensity is ORDER-DEPENDENT in the reference: every LCU clears its own flag when the raster loop reaches it,
+ * so the 9x9 mark a triggering LCU m sets on a later LCU n > m is wiped and one on n <= m stays.  The device gives that final state - the flag of n is 1 exactly
+ * when some triggering LCU m >= n lies within +-4 LCU columns and rows of n - and does not repair it.
+ * EdgeDetectionMeanLumaChroma16x16 (:3522): for complete potentialLogoLcu LCUs the gradient of the 16x16 means (Y, Cr, Cb; integer division by the number of
+ * neighbours), maxGrad = the picture-wide maximum starting at 1, edge_cu bit i = min(grad * 765 / maxGrad, 255) >= 30; every other LCU gets 0, and every LCU gets 0
+ * without want_edge16.
+ * Three stages in stream order - per LCU (a lane per 8x8 variance, lane shuffles, 64-bit sums) with the picture reduction by vector atomics into a context-owned
+ * scratch the call zeroes, then what needs the reduced values (per LCU, and a workgroup per picture for the 9x9 gather and the picture record).  Everything is checked before anything is queued: a NULL stats pointer, want_edge16 without chroma,
+ * a resolution class above 3, a NULL output array or a picture of more than 16384 LCUs return SVT_AMD_ERR_BAD_PARAM (svt_amd_last_error names the job) and queue nothing.
+ */
+typedef struct SvtAmdPaLcuDetect {
+    uint64_t var_of_var_32x32[4];       /* varOfVar32x32BasedLcuArray[lcu][0..3]; 0xFFFFFFFFFFFFFFFF for incomplete LCUs (:3850)   */
+    uint16_t edge_cu;                   /* bit i: lcuStatArray[lcu].cuStatArray[RASTER_SCAN_CU_INDEX_16x16_0 + i].edgeCu (:3609)    */
+    uint8_t  homogeneous;               /* lcuHomogeneousAreaArray[lcu] (:3774, :3842)                                              */
+    uint8_t  edge_block_num;            /* edgeResultsPtr[lcu].edgeBlockNum (:3682)                                                 */
+    uint8_t  isolated_high_intensity;   /* edgeResultsPtr[lcu].isolatedHighIntensityLcu after the whole raster loop (:3669, :3729)  */
+    uint8_t  sharp_edge;                /* sharpEdgeLcuFlag[lcu] (:3691)                                                            */
+    uint8_t  pad[10];                   /* 0 */
+} SvtAmdPaLcuDetect;                    /* 48 bytes */
+typedef struct SvtAmdPaPicDetect {
+    uint16_t pic_avg_variance;          /* picAvgVariance (:3933)      */
+    uint8_t  very_low_var_pic;          /* veryLowVarPicFlag (:3856)   */
+    uint8_t  logo_pic;                  /* logoPicFlag (:3863)         */
+    uint8_t  lcu_block_percentage;      /* lcuBlockPercentage (:3743)  */
+    uint8_t  pad[3];                    /* 0 */
+} SvtAmdPaPicDetect;                    /* 8 bytes */
+typedef struct SvtAmdDetectJob {
+    const SvtAmdPaLcuStats  *stats;     /* DEVICE [lcus], required */
+    const SvtAmdPaLcuChroma *chroma;    /* DEVICE [lcus] or NULL   */
+    uint8_t want_edge16, resolution_class, pad[6];
+} SvtAmdDetectJob;                      /* 24 bytes */
+typedef struct SvtAmdDetectArrays {     /* DEVICE pointers, picture i of the batch at index i; both required */
+    SvtAmdPaLcuDetect *lcu;             /* [n][lcus] */
+    SvtAmdPaPicDetect *picture;         /* [n]       */
+} SvtAmdDetectArrays;
+SVT_AMD_API int svt_amd_picture_detect_batch_launch(SvtAmdContext *ctx, const SvtAmdDetectJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
+                                                    const SvtAmdDetectArrays *out);
+#define SVT_AMD_DETECT_LCU     0
+#define SVT_AMD_DETECT_PICTURE 1
+/* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_picture_detect_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+
 
 /* Device-side timing of the launches issued between begin/end on the context's
  * own stream (HIP events); used for roofline.achieved in bench.py. */

@@ -117,6 +117,10 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
         (void)hipFree(ctx->d_pack_src);
     if (ctx->d_side)
         (void)hipFree(ctx->d_side);
+    if (ctx->d_chroma)
+        (void)hipFree(ctx->d_chroma);
+    if (ctx->d_detect)
+        (void)hipFree(ctx->d_detect);
     if (ctx->d_dbg)
         (void)hipFree(ctx->d_dbg);
     for (int i = 0; i < ctx->cap_stamps; i++) {

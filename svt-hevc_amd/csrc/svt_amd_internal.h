@@ -119,6 +119,8 @@ struct SvtAmdContext {
     int desc_next;
     void *d_pack_src;              /* device table of the pack kernels' per-picture sources (svt_amd_records_pack_batch_async) */
     void *d_side;                  /* descriptor table + per-region sums of svt_amd_side_stats_batch_launch (side_kernels.hip), allocated at its first call */
+    void *d_chroma;                /* descriptor table + per-region sums of svt_amd_chroma_stats_batch_launch (detect_kernels.hip), allocated at its first call */
+    void *d_detect;                /* descriptor table + per-picture reduction of svt_amd_picture_detect_batch_launch (detect_kernels.hip), allocated at its first call */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
