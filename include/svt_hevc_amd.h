@@ -558,6 +558,59 @@ SVT_AMD_API int svt_amd_picture_detect_batch_launch(SvtAmdContext *ctx, const Sv
 /* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
 SVT_AMD_API size_t svt_amd_picture_detect_bytes(uint16_t luma_width, uint16_t luma_height, int which);
 
+/*
+ * Batched noise detection: what PicturePreProcessingOperations (Codec/EbPictureAnalysisProcess.c:3338) leaves behind for later stages - picNoiseClass and
+ * lcuFlatNoiseArray - for up to 256 pictures of ONE geometry per call, stream-ordered on the context's lane like svt_amd_side_stats_batch_launch: the call never
+ * blocks and never copies to the host.  A batch of one picture is the single-picture form.  enableDenoiseSrcFlag is EB_FALSE in every configuration of the
+ * reference (Codec/EbResourceCoordinationProcess.c:304), so the denoise filters never run and the input picture is never rewritten: detection is all there is.
+ *   method          the reference's EB_NOISE_DETECT_MODE: SVT_AMD_NOISE_FULL = DetectInputPictureNoise (:2539) on the input luma, 64x64 blocks;
+ *                   SVT_AMD_NOISE_QUARTER = QuarterSampleDetectNoise (:2909) on the 1/4 picture, 32x32 blocks; SVT_AMD_NOISE_HALF = SubSampleDetectNoise (:3052)
+ *                   on the 1/16 picture, 16x16 blocks.  A block stands for one LCU of the input picture.  The planes are those of the picture slot.
+ *   noise_detection_th  the reference's noiseDetectionTh, 0 or 1: the noise variance of a flat-noise block must exceed 120000 (0) or 70000 (1).
+ *                   Deriving method and threshold from encMode and the resolution class (Codec/EbResourceCoordinationProcess.c:248-284) is the caller's.
+ * The weak luma filter (getFilteredTypes(.., 0), :956-961): denoised = (top + left + 4 * centre + right + bottom) / 8, noise = centre - denoised clamped at 0; the
+ * first and last row and column of the plane the method reads are copied, with noise 0 (:1303-1312).  Block variances are ComputeVariance64x64 / 32x32 / 16x16
+ * (:431, :231, :377): 8x8 means << 8 and means of squares << 16 (ComputeMeanFunc, Codec/EbComputeMean.h:25), averaged up the tree with >> 2, the subtraction
+ * unsigned 64-bit as written.  A block is flat noise when its denoised variance >> 16 is below 50 and its noise variance exceeds the threshold.
+ * The reference's noise picture is ONE 64-row strip reused for every block row (noiseOriginIndex has no vertical term: :2573, :2983, :3127).  In the two
+ * decimated methods every vertically stacked 16x16 (32x32) block of a 64x64 block of the decimated picture therefore shares the noise variance of the TOP rows
+ * of that 64x64 block, while its denoised variance comes from its own rows; restated as it is.  The full method evaluates complete LCUs only; the decimated
+ * methods only the blocks inside floor(width / 64) x floor(height / 64) 64x64 blocks of the decimated picture (4K: the last two LCU rows are left out), so a
+ * decimated picture below 64 samples a side evaluates nothing - block_count 0, sum 0, class 1, no flags - and is no error.
+ * Class ladders on noise_variance_sum / block_count (integer), noiseTh by the slot's luma height: full (:2635-2664) noiseTh 25 up to 720 rows, else 0, rungs
+ * 5 / 10 / 17 + noiseTh for classes 2 / 3 / 3_1, everything above folded to 3_1; half (:3171-3186) noiseTh 25 / 10 / 0 up to 720 / 1080 / above, rungs 5 / 10 / 55 +
+ * noiseTh; quarter (:3032-3042) noiseTh 0, rungs 5 / 10 and the strict > 60.  picNoiseVarianceFloat (read by the dead denoiser only) is noise_variance_sum /
+ * block_count, exactly, on the host; the device does no floating point.
+ * The arrays are DEVICE memory, both required, picture i of the batch at i times svt_amd_noise_detect_bytes(...) bytes of each.  The call waits on the device for
+ * the planes of every slot it reads, zeroes what it accumulates into, and checks everything before it queues anything: a NULL array, an unknown method, a
+ * threshold above 1, a slot that holds no picture or one of another size than job 0's return SVT_AMD_ERR_BAD_PARAM (svt_amd_last_error names the job) and queue
+ * nothing.
+ */
+#define SVT_AMD_NOISE_HALF    0         /* NOISE_DETECT_HALF_PRECISION    (Codec/EbDefinitions.h:1207) */
+#define SVT_AMD_NOISE_QUARTER 1         /* NOISE_DETECT_QUARTER_PRECISION */
+#define SVT_AMD_NOISE_FULL    2         /* NOISE_DETECT_FULL_PRECISION    */
+typedef struct SvtAmdNoiseJob {
+    int32_t cur_slot;
+    uint8_t method;                     /* SVT_AMD_NOISE_* */
+    uint8_t noise_detection_th;         /* 0 or 1 */
+    uint8_t pad[2];
+} SvtAmdNoiseJob;                       /* 8 bytes */
+typedef struct SvtAmdNoisePic {
+    uint64_t noise_variance_sum;        /* the sum of noiseBlkVar >> 16 over the evaluated blocks (:2612, :2991, :3135) */
+    uint32_t block_count;               /* totLcuCount */
+    uint8_t  pic_noise_class;           /* picNoiseClass: PIC_NOISE_CLASS_1 = 1, _2 = 2, _3 = 3, _3_1 = 4 */
+    uint8_t  pad[3];                    /* 0 */
+} SvtAmdNoisePic;                       /* 16 bytes */
+typedef struct SvtAmdNoiseArrays {      /* DEVICE pointers, picture i of the batch at index i; both required */
+    uint8_t        *flat_noise;         /* [n][lcus rounded up to a multiple of 64]   lcuFlatNoiseArray; 0 for LCUs the method never evaluates and in the tail */
+    SvtAmdNoisePic *picture;            /* [n] */
+} SvtAmdNoiseArrays;
+SVT_AMD_API int svt_amd_noise_detect_batch_launch(SvtAmdContext *ctx, const SvtAmdNoiseJob *jobs, int num_jobs, const SvtAmdNoiseArrays *out);
+#define SVT_AMD_NOISE_FLAT    0
+#define SVT_AMD_NOISE_PICTURE 1
+/* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_noise_detect_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+
 
 /* Device-side timing of the launches issued between begin/end on the context's
  * own stream (HIP events); used for roofline.achieved in bench.py. */

@@ -121,6 +121,7 @@ struct SvtAmdContext {
     void *d_side;                  /* descriptor table + per-region sums of svt_amd_side_stats_batch_launch (side_kernels.hip), allocated at its first call */
     void *d_chroma;                /* descriptor table + per-region sums of svt_amd_chroma_stats_batch_launch (detect_kernels.hip), allocated at its first call */
     void *d_detect;                /* descriptor table + per-picture reduction of svt_amd_picture_detect_batch_launch (detect_kernels.hip), allocated at its first call */
+    void *d_noise;                 /* descriptor table + per-picture reduction of svt_amd_noise_detect_batch_launch (noise_kernels.hip), allocated at its first call */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
