@@ -39,6 +39,13 @@ CASES = {
     # kept (top, two interior, the partial bottom row) to bound the fixture size
     "b_3840x2160_m7": ("motion", 3840, 2160, 5, 7,
                        ["-encMode", "7", "-pred-struct", "2", "-hierarchical-levels", "2", "-sao", "1", "-fps", "60"], 1),
+    # saturated clips (every sample 0 or 255): the largest SADs the record fields hold, half-pel filters clipped at both ends
+    # two lists, SSD sub-pel search, 16x16 full-pel search on fresh binary noise every frame
+    "x_binary_320x256_m4": ("x_binary", 320, 256, 5, 3, ["-encMode", "4", "-pred-struct", "2", "-hierarchical-levels", "2"], 3),
+    # one list, 16x7 search: black / white / binary noise in turn, the 64x64 SAD at its maximum of 2 * 32 * 64 * 255
+    "x_whiteblack_320x256_m9": ("x_whiteblack", 320, 256, 4, 3, ["-encMode", "9", "-pred-struct", "0"], 3),
+    # two lists, 16x9 search: one-sample columns, rows and checkerboard
+    "x_stripes_320x256_m7": ("x_stripes", 320, 256, 5, 3, ["-encMode", "7", "-pred-struct", "2", "-hierarchical-levels", "2"], 3),
 }
 ROWS_KEPT = {"b_3840x2160_m7": [0, 11, 22, 33]}
 

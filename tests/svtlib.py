@@ -285,6 +285,19 @@ def load_product():
 
 def gen_luma(kind, w, h, t, seed):
     """One 8-bit luma frame of clip `kind` at time t."""
+    if kind in ("x_whiteblack", "x_binary", "x_stripes"):
+        # saturated clips: every sample is 0 or 255, so block SADs reach the largest value their fields hold (64x64: 2 * 32 * 64 * 255) and
+        # the period-2 patterns send the half-pel filters past both ends of the sample range
+        frame_rng = np.random.default_rng(seed * 100 + t)
+        x = np.arange(w)[None, :]
+        y = np.arange(h)[:, None]
+        if kind == "x_whiteblack" and t % 3 != 2:
+            return np.full((h, w), 255 * (t % 3), np.uint8)
+        if kind == "x_stripes":
+            # columns, rows, a one-sample checkerboard
+            bits = ((x + t) & 1) + 0 * y if t % 3 == 0 else ((y + t) & 1) + 0 * x if t % 3 == 1 else (x + y) & 1
+            return (bits * 255).astype(np.uint8)
+        return (frame_rng.integers(0, 2, (h, w)) * 255).astype(np.uint8)
     if kind == "flat":
         return np.full((h, w), 128, np.uint8)
     if kind == "static":
