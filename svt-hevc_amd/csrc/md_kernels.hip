@@ -171,16 +171,16 @@ struct MdInterShared {
     int n_me, n_mg;
     alignas(16) uint8_t wpred[4][64 * 64];     /* a wave's prediction of the candidate it works on, pitch = unit size */
     uint8_t cpred[MD_PRED_SLOTS][64 * 64]; /* the fast loop's predictions of the first motion-compensated candidates, kept for the full loop */
-    int8_t slot[MD_MAX_CAND];      /* candidate -> cpred slot, -1 = none */
+    int8_t slot[MD_MAX_CAND];      /* unused (md_units_inter keeps the slots in registers); still here because removing a member moves every LDS offset behind it */
     EpMcScratch<uint8_t> mc[4];
     alignas(16) uint8_t src_c[2][32 * 32];     /* the LCU's chroma source (CHROMA_MODE_FULL candidates; merge / skip decision of the encode pass) */
     /* CHROMA_MODE_FULL LCUs (chroma in both loops of every candidate, EbModeDecisionProcess.c:439-441) */
     alignas(16) uint8_t cpred_c[MD_PRED_SLOTS][2][32 * 32]; /* the chroma predictions beside cpred, pitch = unit size / 2 */
     int16_t refc[2][132];          /* the unit's open-loop chroma intra references (Cb, Cr) in pu_predict's layout */
-    uint32_t sadc[MD_MAX_CAND];    /* Cb + Cr SAD of the fast loop */
-    uint32_t sadc2[MD_MAX_CAND][2]; /* ... per plane, one owner per entry (md_units_inter) */
-    uint8_t heavyc[MD_MAX_CAND];   /* the candidates whose chroma the fast loop predicts and measures, packed */
-    int nheavyc;
+    uint32_t sadc[MD_MAX_CAND];    /* unused, kept like slot */
+    uint32_t sadc2[MD_MAX_CAND][2]; /* Cb and Cr SAD of the fast loop, one owner per entry */
+    uint8_t heavyc[MD_MAX_CAND];   /* unused, kept like slot */
+    int nheavyc;                   /* unused, kept like slot */
     MdFl flc[MD_MAX_BUF][2][4];    /* the chroma full loop's sums per buffer, plane and transform unit */
     EpRefPlanes refs[2];           /* the reference pictures' plane pointers and geometry beside the LCU (the kernel argument they come from lives in memory as soon as a
                                     * function takes it by reference: a chain of loads per interpolation otherwise) */
@@ -190,7 +190,6 @@ struct MdInterShared {
     uint8_t ep_kind[SVT_AMD_MD_LEAVES]; /* SVT_AMD_EP_INTER_* of the final tree's inter units */
     uint8_t fin_leaf[SVT_AMD_LCU_MAX_CUS];
     int nfin;
-    __device__ __forceinline__ MdMvUnit *mv_at(int x, int y) { return &mvu[((y >> 3) + 1) * 18 + (x >> 3) + 1]; }
 };
 template <bool INTER> struct MdVariant { typedef MdClosedLoop type; };
 template <> struct MdVariant<true> { typedef MdInterShared type; };
@@ -2160,244 +2159,117 @@ __device__ __forceinline__ void md_lcu(const MdPictureDev &D, const SvtAmdMdPict
     MD_PROF(0);
     const SvtAmdOisLcuResult *ois = &M.ois;
     const int pf = md_pf_mode(&P);
-    constexpr bool NEW_INTER_LOOP = INTER; /* P / B pictures: md_units_inter (round 6); the loop below is the I pictures' */
-    if constexpr (NEW_INTER_LOOP)
+    /* ---- the LCU's units, one after the other: P / B pictures run md_units_inter, the loop below is the I pictures' alone ---- */
+    if constexpr (INTER) {
         if (M.lcu.chroma_encode_mode == 1)
             md_units_inter<PROF, true>(D, lcu, lcu_x, lcu_y, M);
         else
             md_units_inter<PROF, false>(D, lcu, lcu_x, lcu_y, M);
-    else
-    for (;;) {
-        MD_TR(10);
-        /* ---- lane 0: the unit, its contexts and its candidates ---- */
-        if (t == 0) {
-            const int cuIdx = M.cu_idx, leaf = M.lcu.leaf_index[cuIdx];
-            const MdStats st = md_stats(leaf);
-            M.leaf = leaf;
-            if (prof_on)
-                M.prof_depth = st.depth;
-            M.S.local[leaf].tested = 1;
-            M.S.cu[leaf].split = (uint8_t)((islice && st.depth == 0) ? 1 : M.lcu.leaf_split[cuIdx]);
-            uint32_t l = L.info_at(st.x - 1, st.y), tp = L.info_at(st.x, st.y - 1);
-            if ((M.lcu.tile_left && st.x == 0) || (l & 0xFF) == 0xFE)
-                l = 0xFFFFFFFFu;
-            if ((M.lcu.tile_top && st.y == 0) || (tp & 0xFF) == 0xFE)
-                tp = 0xFFFFFFFFu;
-            MdNeighbors Nb;
-            Nb.left_mode = (uint8_t)l, Nb.left_intra = (uint8_t)(l >> 8), Nb.left_depth = (uint8_t)(l >> 16), Nb.left_skip = (uint8_t)(l >> 24);
-            Nb.top_mode = (uint8_t)tp, Nb.top_intra = (uint8_t)(tp >> 8), Nb.top_depth = (uint8_t)(tp >> 16), Nb.top_skip = (uint8_t)(tp >> 24);
-            md_context_generation(&M.S, leaf, st.y, &Nb);
-            M.S.cu[leaf].split = (uint8_t)md_skip_small_cu(&P, &M.lcu, &M.S, leaf, st.depth);
-            int ncand = 0;
-            if (st.depth != 0 && (islice || st.depth == 3 || !M.lcu.restrict_intra_global_motion))
-                if (!(P.limit_intra && st.x == 0 && st.y == 0))
-                    ncand = md_intra_candidates(&P, &M.lcu, ois, leaf, &st, M.cand);
-            M.ncand = ncand; /* the intra candidates so far (P / B pictures: the lists below are made by three waves) */
-        }
-        if (wave == 0)
-            MD_TR(11);
-        MD_SUB(0);
-        if constexpr (INTER) {
-            /* GenerateL0L1AmvpMergeLists: the AMVP candidates of list 0, of list 1 and the merge candidates share their inputs and nothing else - and none of them needs
-             * what lane 0 of the first wave derives meanwhile (contexts, intra candidates).  Waves 1 and 2 therefore start at the unit's first moment: five lanes of each
-             * fetch the spatial neighbours with the availability GenerateL0L1AmvpMergeLists derives (EbAdaptiveMotionVectorPrediction.c:2256-2340) into the wave's OWN copy
-             * (no workgroup barrier between the fetch and the list), lane 0 then makes the wave's lists - four chains side by side instead of a barrier after the first. */
-            if (wave >= 1) {
-                const MdStats st = md_stats(M.lcu.leaf_index[M.cu_idx]);
-                if (wave < 3) {
-                    /* the five spatial neighbours (A0, A1, B0, B1, B2): a lane each, then every lane of the wave holds all five IN REGISTERS (v_readlane) - the list code
-                     * below runs on registers in every lane alike, with no trip through LDS between the fetch and the lists */
-                    uint32_t w0 = 0, w1 = 0, w2 = 0;
-                    if (lane < 5) {
-                        const int N = st.size, k = lane;
-                        const bool left = M.lcu.tile_left && st.x == 0, top = M.lcu.tile_top && st.y == 0, right = M.lcu.tile_right && ((st.x + N) & 63) == 0;
-                        const int px = k == 2 ? st.x + N : k == 3 ? st.x + N - 1 : st.x - 1, py = k == 0 ? st.y + N : k == 1 ? st.y + N - 1 : st.y - 1;
-                        const bool ok = k == 0 ? md_bottom_left_ok(&st) && !left : k == 1 ? !left : k == 2 ? md_top_right_ok(&st) && !top && !right : k == 3 ? !top : !left && !top;
-                        if (ok && (L.info_at(px, py) & 0xFF) == MD_INTER) {
-                            const uint32_t *q = reinterpret_cast<const uint32_t *>(M.V.mv_at(px, py));
-                            w0 = q[0], w1 = q[1], w2 = (q[2] & 0xFFu) | 0x100u; /* mv[0], mv[1], dir | avail << 8 */
-                        }
-                    }
-                    MdMvUnit nbr[5];
-#pragma unroll
-                    for (int k = 0; k < 5; k++) {
-                        const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)w0, k), b = (uint32_t)__builtin_amdgcn_readlane((int)w1, k),
-                                       c = (uint32_t)__builtin_amdgcn_readlane((int)w2, k);
-                        nbr[k].mv[0].x = (int16_t)(a & 0xFFFF), nbr[k].mv[0].y = (int16_t)(a >> 16), nbr[k].mv[1].x = (int16_t)(b & 0xFFFF), nbr[k].mv[1].y = (int16_t)(b >> 16);
-                        nbr[k].dir = (uint8_t)(c & 0xFF), nbr[k].avail = (uint8_t)((c >> 8) & 1), nbr[k].pad[0] = nbr[k].pad[1] = 0;
-                    }
-                    MD_TR(12);
-                    MdInterLists T;
-                    T.amvp_count[0] = T.amvp_count[1] = 0, T.merge_count = 0, T.pad = 0;
-                    const int ox = lcu_x + st.x, oy = lcu_y + st.y, totalMerge = md_nmm(&P, st.size);
-                    /* wave 1: both AMVP lists, wave 2: the merge candidates (the longest of the three) */
-                    md_amvp_merge_lists_parts(&P, &M.V.X, nbr, M.V.X.tmvp_enable ? M.V.tmvp : nullptr, ox, oy, st.size, totalMerge, &T, wave == 1 ? 3 : 4);
-                    MD_TR(13);
-                    bool keep = false;
-                    MdCand c;
-                    c.type = MD_INTER, c.intra_mode = 0, c.mpm = 0, c.dist_ready = 0, c.me_dist = 0, c.dir = 0, c.merge_flag = 0, c.merge_index = 0;
-                    c.mvp_idx[0] = c.mvp_idx[1] = 0, c.pad[0] = c.pad[1] = c.pad[2] = 0;
-                    c.mv[0].x = c.mv[0].y = c.mv[1].x = c.mv[1].y = 0, c.mvp[0].x = c.mvp[0].y = c.mvp[1].x = c.mvp[1].y = 0;
-                    if (wave == 1) { /* Me2Nx2NCandidatesInjection: a lane per motion-estimation candidate (md_inter_candidates, md_logic.h) */
-                        const SvtAmdMeCuResult *me = &M.V.me[md_raster_index(&st)];
-                        if (lane < 3 && lane < me->total_me_candidate_index) {
-                            const int dir = me->direction[lane];
-                            if (!(dir == MD_BI && P.depth_mode == 0 && M.lcu.lcu_md_mode == 10)) {
-                                keep = true;
-                                c.dist_ready = 1, c.me_dist = me->distortion[lane], c.dir = (uint8_t)dir;
-                                c.mv[0].x = me->x_mv_l0, c.mv[0].y = me->y_mv_l0, c.mv[1].x = me->x_mv_l1, c.mv[1].y = me->y_mv_l1;
-                                md_choose_mvp(&P, (uint32_t)ox, (uint32_t)oy, &T, &c);
-                            }
-                        }
-                    } else { /* ProductMergeSkip2Nx2NCandidatesInjection: a lane per merge candidate, duplicates of earlier ones dropped */
-                        const int k = lane;
-                        if (k < 5 && k < totalMerge && k < T.merge_count) {
-                            const MdMergeCand mc = k == 0 ? T.merge[0] : k == 1 ? T.merge[1] : k == 2 ? T.merge[2] : k == 3 ? T.merge[3] : T.merge[4];
-                            bool dup = false;
-#pragma unroll
-                            for (int j = 0; j < 4; j++) {
-                                const MdMergeCand d = T.merge[j];
-                                const bool f0 = mc.mv[0].x == d.mv[0].x && mc.mv[0].y == d.mv[0].y;
-                                const bool f1 = mc.dir != MD_L0 && mc.mv[1].x == d.mv[1].x && mc.mv[1].y == d.mv[1].y;
-                                const bool same = mc.dir == MD_L0 ? f0 : (mc.dir == MD_L1 ? f1 : (f0 && f1));
-                                dup = dup || (j < k && mc.dir == d.dir && same);
-                            }
-                            if (!dup) {
-                                keep = true;
-                                c.dir = mc.dir, c.merge_flag = 1, c.merge_index = (uint8_t)k, c.mv[0] = mc.mv[0], c.mv[1] = mc.mv[1];
-                            }
-                        }
-                    }
-                    const unsigned long long km = __ballot(keep);
-                    if (keep)
-                        (wave == 1 ? M.V.me_c : M.V.mg_c)[__popcll(km & ((1ull << lane) - 1ull))] = c;
-                    if (lane == 0)
-                        (wave == 1 ? M.V.n_me : M.V.n_mg) = __popcll(km);
-                    MD_TR(16);
-                }
-                /* ... and the fourth wave the unit's intra reference (only units below 64x64 have intra candidates) - source samples from HBM in the open-loop decision, a
-                 * round trip under the other waves' chains */
-                if (wave == 3 && st.depth != 0) {
-                    if (open_loop)
-                        md_build_refs_ol(D, M, st, lcu_x + st.x, lcu_y + st.y, W, H, lane);
-                    else
-                        md_build_refs(M, st, lane);
-                    if (M.lcu.chroma_encode_mode == 1 && open_loop)
-                        md_build_refs_ol_chroma(D, M.V.refc, st.size, lcu_x + st.x, lcu_y + st.y, W, H, lane);
-                }
-                if (wave == 3)
-                    MD_TR(14);
+    } else {
+        for (;;) {
+            MD_TR(10);
+            /* ---- lane 0: the unit, its contexts and its candidates ---- */
+            if (t == 0) {
+                const int cuIdx = M.cu_idx, leaf = M.lcu.leaf_index[cuIdx];
+                const MdStats st = md_stats(leaf);
+                M.leaf = leaf;
+                if (prof_on)
+                    M.prof_depth = st.depth;
+                M.S.local[leaf].tested = 1;
+                M.S.cu[leaf].split = (uint8_t)((islice && st.depth == 0) ? 1 : M.lcu.leaf_split[cuIdx]);
+                uint32_t l = L.info_at(st.x - 1, st.y), tp = L.info_at(st.x, st.y - 1);
+                if ((M.lcu.tile_left && st.x == 0) || (l & 0xFF) == 0xFE)
+                    l = 0xFFFFFFFFu;
+                if ((M.lcu.tile_top && st.y == 0) || (tp & 0xFF) == 0xFE)
+                    tp = 0xFFFFFFFFu;
+                MdNeighbors Nb;
+                Nb.left_mode = (uint8_t)l, Nb.left_intra = (uint8_t)(l >> 8), Nb.left_depth = (uint8_t)(l >> 16), Nb.left_skip = (uint8_t)(l >> 24);
+                Nb.top_mode = (uint8_t)tp, Nb.top_intra = (uint8_t)(tp >> 8), Nb.top_depth = (uint8_t)(tp >> 16), Nb.top_skip = (uint8_t)(tp >> 24);
+                md_context_generation(&M.S, leaf, st.y, &Nb);
+                M.S.cu[leaf].split = (uint8_t)md_skip_small_cu(&P, &M.lcu, &M.S, leaf, st.depth);
+                int ncand = 0;
+                if (st.depth != 0 && (islice || st.depth == 3 || !M.lcu.restrict_intra_global_motion))
+                    if (!(P.limit_intra && st.x == 0 && st.y == 0))
+                        ncand = md_intra_candidates(&P, &M.lcu, ois, leaf, &st, M.cand);
+                M.ncand = ncand; /* the intra candidates so far */
             }
-            MD_SUB(2);
-            __syncthreads();
-            MD_TR(15);
-            MD_SUB(3);
-            /* wave 0 appends the two waves' candidates to the intra candidates: motion-estimation candidates first, merge candidates behind them (md_inter_candidates' order) */
-            if (wave == 0) {
-                const int n0 = M.ncand, nme = M.V.n_me, nmg = M.V.n_mg;
-                if (lane < nme)
-                    M.cand[n0 + lane] = M.V.me_c[lane];
-                else if (lane < nme + nmg)
-                    M.cand[n0 + lane] = M.V.mg_c[lane - nme];
-                if (lane == 0)
-                    M.ncand = n0 + nme + nmg;
+            if (wave == 0)
+                MD_TR(11);
+            MD_SUB(0);
+            MD_SUB(4);
+            if (t == 0) {
+                const int leaf = M.leaf;
+                const MdStats st = md_stats(leaf);
+                int ncand = M.ncand;
+                uint32_t mpm[3] = {0, 0, 0};
+                if (P.mpm_search && !M.lcu.restrict_intra_global_motion)
+                    md_mpm_modes(M.S.cu[leaf].left_intra_mode, M.S.cu[leaf].top_intra_mode, mpm);
+                int bufferTotal = md_nfl(&P, &M.lcu, st.size);
+                ncand = md_mpm_injection(&P, &M.lcu, &st, M.cand, ncand, &bufferTotal, mpm);
+                bufferTotal = ncand < bufferTotal ? ncand : bufferTotal;
+                const int width = st.depth == 0 ? 5 : 8;
+                M.ncand = ncand, M.buffer_total = bufferTotal, M.max_buffers = bufferTotal + 1 < width ? bufferTotal + 1 : width;
+            }
+            if (wave == 0)
+                MD_TR(17);
+            MD_SUB(5);
+            if (wave == 0) { /* a lane per candidate (MD_MAX_CAND <= 64): what the candidate list implies for the loops below */
                 EP_WAVE_SYNC();
-            }
-        }
-        MD_SUB(4);
-        if (t == 0) {
-            const int leaf = M.leaf;
-            const MdStats st = md_stats(leaf);
-            int ncand = M.ncand;
-            uint32_t mpm[3] = {0, 0, 0};
-            if (P.mpm_search && !M.lcu.restrict_intra_global_motion)
-                md_mpm_modes(M.S.cu[leaf].left_intra_mode, M.S.cu[leaf].top_intra_mode, mpm);
-            int bufferTotal = md_nfl(&P, &M.lcu, st.size);
-            ncand = md_mpm_injection(&P, &M.lcu, &st, M.cand, ncand, &bufferTotal, mpm);
-            bufferTotal = ncand < bufferTotal ? ncand : bufferTotal;
-            const int width = st.depth == 0 ? 5 : 8;
-            M.ncand = ncand, M.buffer_total = bufferTotal, M.max_buffers = bufferTotal + 1 < width ? bufferTotal + 1 : width;
-        }
-        if (wave == 0)
-            MD_TR(17);
-        MD_SUB(5);
-        if (wave == 0) { /* a lane per candidate (MD_MAX_CAND <= 64): what the candidate list implies for the loops below */
-            EP_WAVE_SYNC();
-            const int nc = M.ncand, lf = M.leaf;
-            const MdStats s1 = md_stats(lf);
-            const bool in = lane < nc;
-            MdCand c = M.cand[in ? lane : 0];
-            M.any_intra = __ballot(in && c.type == MD_INTRA) != 0;
-            /* the first fast loop (EbProductCodingLoop.c:1948-1988): the best of the candidates whose distortion the open-loop stages left; the reference
-             * walks from the last candidate down with <=: the LOWEST index among equal costs */
-            int bestFirst = -1;
-            if (!P.single_fast_loop) {
-                const bool ready = in && c.dist_ready;
-                unsigned long long cost = ~0ull;
-                if (ready) {
-                    uint64_t r;
-                    cost = c.type == MD_INTER ? md_inter_fast_cost(&P, &s1, &M.S.cu[lf], &c, c.me_dist, &r)
-                           : islice          ? md_intra_fast_cost_islice(&P, &s1, &M.S.cu[lf], c.intra_mode, c.me_dist, &r)
-                                             : md_intra_fast_cost_pslice(&P, &s1, &M.S.cu[lf], c.intra_mode, c.me_dist, &r);
+                const int nc = M.ncand, lf = M.leaf;
+                const MdStats s1 = md_stats(lf);
+                const bool in = lane < nc;
+                MdCand c = M.cand[in ? lane : 0];
+                M.any_intra = __ballot(in && c.type == MD_INTRA) != 0;
+                /* the first fast loop (EbProductCodingLoop.c:1948-1988): the best of the candidates whose distortion the open-loop stages left; the reference
+                 * walks from the last candidate down with <=: the LOWEST index among equal costs */
+                int bestFirst = -1;
+                if (!P.single_fast_loop) {
+                    const bool ready = in && c.dist_ready;
+                    unsigned long long cost = ~0ull;
+                    if (ready) {
+                        uint64_t r;
+                        cost = c.type == MD_INTER ? md_inter_fast_cost(&P, &s1, &M.S.cu[lf], &c, c.me_dist, &r)
+                               : islice          ? md_intra_fast_cost_islice(&P, &s1, &M.S.cu[lf], c.intra_mode, c.me_dist, &r)
+                                                 : md_intra_fast_cost_pslice(&P, &s1, &M.S.cu[lf], c.intra_mode, c.me_dist, &r);
+                    }
+                    /* few candidates are ready: a scalar walk over them instead of a 64-lane reduction */
+                    unsigned long long m = ~0ull, rm = __ballot(ready);
+                    while (rm) {
+                        const int l = __ffsll((long long)rm) - 1;
+                        rm &= rm - 1;
+                        const unsigned long long v = md_readlane64(cost, l);
+                        if (bestFirst < 0 || v < m)
+                            m = v, bestFirst = l;
+                    }
                 }
-                /* few candidates are ready: a scalar walk over them instead of a 64-lane reduction */
-                unsigned long long m = ~0ull, rm = __ballot(ready);
-                while (rm) {
-                    const int l = __ffsll((long long)rm) - 1;
-                    rm &= rm - 1;
-                    const unsigned long long v = md_readlane64(cost, l);
-                    if (bestFirst < 0 || v < m)
-                        m = v, bestFirst = l;
-                }
-            }
-            uint8_t e = (uint8_t)(in && (!c.dist_ready || lane == bestFirst || P.single_fast_loop));
-            if (e && lane == bestFirst && c.type == MD_INTRA && open_loop)
-                e = 3; /* the open-loop distortion stands, no luma prediction (:1660, :2042) */
-            if (in)
-                M.evaluated[lane] = e;
-            {   /* what the fast loop really has to do: predict + measure the evaluated candidates that are neither most-probable-mode placeholders nor the open-loop
-                 * intra candidate whose distortion stands (:2042).  Most P / B candidates are not among them (the motion-estimation candidates bring their distortion:
-                 * only the best of them is evaluated), so the list is packed - a wave per LIST entry keeps all four waves on real work */
-                const bool heavy = in && e && !c.mpm && !(lane == bestFirst && c.type == MD_INTRA);
-                const unsigned long long hm = __ballot(heavy);
-                if (heavy)
-                    M.heavy[__popcll(hm & ((1ull << lane) - 1ull))] = (uint8_t)lane;
-                if (in) /* the heavy candidates' distortion is summed up by the fast loop (several waves may add to it) */
-                    M.sad[lane] = (!heavy && e && !c.mpm) ? c.me_dist : 0u;
-                if (lane == 0)
-                    M.nheavy = __popcll(hm);
-                if constexpr (INTER) { /* CHROMA_MODE_FULL: the chroma pair of EVERY evaluated candidate is predicted and measured - the open-loop intra candidate that won
-                                        * the first loop included (only its luma distortion stands, :1651-1654) */
-                    const bool hc = in && e && !c.mpm && M.lcu.chroma_encode_mode == 1;
-                    const unsigned long long cm = __ballot(hc);
-                    if (hc)
-                        M.V.heavyc[__popcll(cm & ((1ull << lane) - 1ull))] = (uint8_t)lane;
-                    if (in)
-                        M.V.sadc[lane] = 0u;
-                    if (lane == 0)
-                        M.V.nheavyc = __popcll(cm);
-                }
-            }
-            if constexpr (INTER) { /* the first eight inter candidates the loop evaluates keep their prediction for the full loop */
-                const bool q = e && c.type == MD_INTER;
-                const unsigned long long qm = __ballot(q);
-                const int rank = __popcll(qm & ((1ull << lane) - 1ull));
+                uint8_t e = (uint8_t)(in && (!c.dist_ready || lane == bestFirst || P.single_fast_loop));
+                if (e && lane == bestFirst && c.type == MD_INTRA && open_loop)
+                    e = 3; /* the open-loop distortion stands, no luma prediction (:1660, :2042) */
                 if (in)
-                    M.V.slot[lane] = (int8_t)((q && rank < MD_PRED_SLOTS) ? rank : -1);
+                    M.evaluated[lane] = e;
+                {   /* what the fast loop really has to do: predict + measure the evaluated candidates that are neither most-probable-mode placeholders nor the open-loop
+                     * intra candidate whose distortion stands (:2042).  The list is packed - a wave per LIST entry keeps all four waves on real work */
+                    const bool heavy = in && e && !c.mpm && !(lane == bestFirst && c.type == MD_INTRA);
+                    const unsigned long long hm = __ballot(heavy);
+                    if (heavy)
+                        M.heavy[__popcll(hm & ((1ull << lane) - 1ull))] = (uint8_t)lane;
+                    if (in) /* the heavy candidates' distortion is summed up by the fast loop (several waves may add to it) */
+                        M.sad[lane] = (!heavy && e && !c.mpm) ? c.me_dist : 0u;
+                    if (lane == 0)
+                        M.nheavy = __popcll(hm);
+                }
+                if (lane == 0)
+                    M.best_first = bestFirst;
+                MD_TR(18);
             }
-            if (lane == 0)
-                M.best_first = bestFirst;
-            MD_TR(18);
-        }
-        MD_SUB(6);
-        __syncthreads();
-        MD_TR(19);
-        MD_PROF(1);
-        const int leaf = M.leaf, ncand = M.ncand;
-        const MdStats st = md_stats(leaf);
-        const int N = st.size, lgN = st.lg, x0 = lcu_x + st.x, y0 = lcu_y + st.y;
-        /* ---- wave 0: the unit's intra reference (P / B pictures: made beside the motion-vector lists above) ---- */
-        if constexpr (!INTER) {
+            MD_SUB(6);
+            __syncthreads();
+            MD_TR(19);
+            MD_PROF(1);
+            const int leaf = M.leaf, ncand = M.ncand;
+            const MdStats st = md_stats(leaf);
+            const int N = st.size, lgN = st.lg, x0 = lcu_x + st.x, y0 = lcu_y + st.y;
+            /* ---- wave 0: the unit's intra reference ---- */
             if (wave == 0 && M.any_intra) {
                 if (open_loop)
                     md_build_refs_ol(D, M, st, x0, y0, W, H, lane);
@@ -2405,405 +2277,224 @@ __device__ __forceinline__ void md_lcu(const MdPictureDev &D, const SvtAmdMdPict
                     md_build_refs(M, st, lane);
             }
             __syncthreads();
-        }
-        MD_PROF(2);
-        if (prof_on && t == 0)
-            M.prof[13] += (unsigned long long)ncand, M.prof[14] += 1, M.prof_d[M.prof_depth][13] += (unsigned long long)ncand, M.prof_d[M.prof_depth][14] += 1;
-        /* ---- fast loop (ProductPerformFastLoop's second loop): ONE list of tasks = (candidate, plane, tile) dealt to the four waves ----
-         * luma tasks first - a candidate of a 64x64 unit is motion-compensated in four 32x32 tiles, a task each (wave w takes tile w of EVERY candidate: all four waves work
-         * whatever the number of candidates) -, then, in CHROMA_MODE_FULL LCUs, the Cb and the Cr block of every evaluated candidate.  A task predicts its block (inter:
-         * ep_inter_predict_core into the candidate's slot - kept for the full loop - or the wave's scratch; intra: per sample in closed form), measures it against the source
-         * (v_sad_u8 on words) and adds its part to the candidate's distortion. */
-        {
-            bool tiled64 = false;
-            int nhc = 0;
-            if constexpr (INTER) {
-                tiled64 = N == 64 && !M.any_intra;
-                nhc = M.V.nheavyc;
-            }
-            const int T = tiled64 ? 4 : 1, nl = M.nheavy * T, ntask = nl + 2 * nhc;
-            for (int tk = wave; tk < ntask; tk += 4) {
-                const bool luma = tk < nl;
-                const int k = luma ? (tiled64 ? tk >> 2 : tk) : (tk - nl) >> 1, ti = luma ? (tiled64 ? tk & 3 : 0) : 0, pl = luma ? 0 : 1 + ((tk - nl) & 1);
-                int c;
-                if constexpr (INTER)
-                    c = luma ? M.heavy[k] : M.V.heavyc[k];
-                else
-                    c = M.heavy[k];
+            MD_PROF(2);
+            if (prof_on && t == 0)
+                M.prof[13] += (unsigned long long)ncand, M.prof[14] += 1, M.prof_d[M.prof_depth][13] += (unsigned long long)ncand, M.prof_d[M.prof_depth][14] += 1;
+            /* ---- fast loop (ProductPerformFastLoop's second loop): the packed list of candidates dealt to the four waves, a wave per candidate ----
+             * A task predicts its luma block (per sample in closed form), measures it against the source and adds its part to the candidate's distortion. */
+            for (int k = wave, nheavy = M.nheavy; k < nheavy; k += 4) {
+                const int c = M.heavy[k];
                 MD_TR(20);
                 const MdCand cd = M.cand[c];
                 uint32_t sad = 0;
-                if (cd.type == MD_INTER) {
-                    if constexpr (INTER) {
-                        const int sl = M.V.slot[c], n = luma ? N : N >> 1, lgn = luma ? lgN : lgN - 1;
-                        uint8_t *pr = luma ? (sl >= 0 ? M.V.cpred[sl] : M.V.wpred[wave]) : (sl >= 0 ? M.V.cpred_c[sl][pl - 1] : M.V.wpred_c(wave, pl - 1));
-                        md_predict_inter_plane(M.V.refs, cd, x0, y0, N, pl, lane, M.V.mc[wave], pr, tiled64 && luma ? ti : 0, tiled64 && luma ? 4 : 1, &M.V.rw, &M.V.rwc);
-                        MD_TR(22);
-                        MD_SUB(7);
-                        if (luma && tiled64) {
-                            const int ty0 = (ti >> 1) << 5, tx0 = (ti & 1) << 5;
-                            for (int e = 4 * lane; e < 32 * 32; e += 256) { /* v_sad_u8: four samples a word */
-                                const int y = ty0 + (e >> 5), x = tx0 + (e & 31);
-                                sad = __builtin_amdgcn_sad_u8(*reinterpret_cast<const uint32_t *>(&pr[y * 64 + x]), *reinterpret_cast<const uint32_t *>(&L.src[(st.y + y) * 64 + st.x + x]), sad);
-                            }
-                        } else if (luma) {
-                            for (int e = 4 * lane; e < N * N; e += 256)
-                                sad = __builtin_amdgcn_sad_u8(*reinterpret_cast<const uint32_t *>(&pr[e]), *reinterpret_cast<const uint32_t *>(&L.src[(st.y + (e >> lgN)) * 64 + st.x + (e & (N - 1))]), sad);
-                        } else { /* chroma blocks are 4 .. 32 samples wide: rows of words */
-                            const uint8_t *sc = &M.V.src_c[pl - 1][(st.y >> 1) * 32 + (st.x >> 1)];
-                            for (int e = 4 * lane; e < n * n; e += 256)
-                                sad = __builtin_amdgcn_sad_u8(*reinterpret_cast<const uint32_t *>(&pr[e]), *reinterpret_cast<const uint32_t *>(&sc[(e >> lgn) * 32 + (e & (n - 1))]), sad);
-                        }
-                    }
-                } else if (luma) {
+                if (cd.type != MD_INTER) {
                     const int mode = cd.intra_mode;
                     sad = md_intra_block(mode, N, lgN, (!open_loop && md_mode_filtered(mode, lgN)) ? M.reff : M.ref, 1, lane, &L.src[st.y * 64 + st.x], 64, nullptr);
-                } else {
-                    if constexpr (INTER) { /* IntraPredictionOl's chroma pair: the chroma mode is always DM (Codec/EbIntraPrediction.c:5530); kept for the full loop like the inter ones */
-                        sad = md_intra_block(cd.intra_mode, N >> 1, lgN - 1, M.V.refc[pl - 1], 0, lane, &M.V.src_c[pl - 1][(st.y >> 1) * 32 + (st.x >> 1)], 32, nullptr);
-                    }
                 }
                 sad = md_wave_sum(sad);
                 MD_TR(23);
                 MD_SUB(8);
-                if (lane == 0 && sad) {
-                    if (luma)
-                        atomicAdd(&M.sad[c], sad);
-                    else if constexpr (INTER)
-                        atomicAdd(&M.V.sadc[c], sad);
-                }
+                if (lane == 0 && sad)
+                    atomicAdd(&M.sad[c], sad);
                 MD_TR(24);
             }
-        }
-        __syncthreads();
-        MD_TR(25);
-        MD_PROF(3);
-        /* ---- wave 0: fast costs (a lane per candidate: MD_MAX_CAND <= 64), candidate buffers (a lane per buffer), PreModeDecision ---- */
-        if (wave == 0) {
-            const int i = lane;
-            unsigned long long rate = 0, cst = ~0ull;
-            int evl = 0;
-            if (i < ncand) {
-                evl = M.evaluated[i];
-                if (evl) {
-                    const uint64_t dist = M.cand[i].mpm ? 0 : M.sad[i];
-                    uint64_t distc = 0;
-                    uint32_t cw = 0;
-                    if constexpr (INTER) {
-                        if (M.lcu.chroma_encode_mode == 1) /* the chroma pair's SAD with the noise-class rule (:2079-2094) */
-                            distc = M.cand[i].mpm ? 0 : md_fast_chroma_noise_rule(&M.lcu, N, &M.cand[i], M.V.sadc[i]), cw = M.V.X.chroma_weight;
+            __syncthreads();
+            MD_TR(25);
+            MD_PROF(3);
+            /* ---- wave 0: fast costs (a lane per candidate: MD_MAX_CAND <= 64), candidate buffers (a lane per buffer), PreModeDecision ---- */
+            if (wave == 0) {
+                const int i = lane;
+                unsigned long long rate = 0, cst = ~0ull;
+                int evl = 0;
+                if (i < ncand) {
+                    evl = M.evaluated[i];
+                    if (evl) {
+                        const uint64_t dist = M.cand[i].mpm ? 0 : M.sad[i];
+                        const uint64_t distc = 0; /* luma-only candidates: no chroma distortion, no chroma weight */
+                        const uint32_t cw = 0;
+                        cst = M.cand[i].type == MD_INTER ? md_inter_fast_cost_c(&P, &st, &M.S.cu[leaf], &M.cand[i], dist, distc, cw, !M.lcu.cmplx_noise, (uint64_t *)&rate)
+                              : islice                  ? md_intra_fast_cost_islice(&P, &st, &M.S.cu[leaf], M.cand[i].intra_mode, dist, (uint64_t *)&rate)
+                                                        : md_intra_fast_cost_pslice_c(&P, &st, &M.S.cu[leaf], M.cand[i].intra_mode, dist, distc, cw, (uint64_t *)&rate);
+                        if (M.cand[i].mpm)
+                            cst = 0;
                     }
-                    cst = M.cand[i].type == MD_INTER ? md_inter_fast_cost_c(&P, &st, &M.S.cu[leaf], &M.cand[i], dist, distc, cw, !M.lcu.cmplx_noise, (uint64_t *)&rate)
-                          : islice                  ? md_intra_fast_cost_islice(&P, &st, &M.S.cu[leaf], M.cand[i].intra_mode, dist, (uint64_t *)&rate)
-                                                    : md_intra_fast_cost_pslice_c(&P, &st, &M.S.cu[leaf], M.cand[i].intra_mode, dist, distc, cw, (uint64_t *)&rate);
-                    if (M.cand[i].mpm)
-                        cst = 0;
+                    M.costs[i] = cst, M.fast_rate[i] = rate;
                 }
-                M.costs[i] = cst, M.fast_rate[i] = rate;
-            }
-            MD_TR(26);
-            MD_SUB(9);
-            /* md_fast_loop_buffers (md_logic.h; ProductPerformFastLoop's second loop, :1990-2179) with the buffers in lanes 0..7 instead of LDS: the candidates
-             * arrive from the last to the first, each goes into the buffer with the highest cost (an unused one first) = the FIRST buffer holding the maximum
-             * over [0, maxBuffers) - the reference's scan starts at buffer 0, moves on a strictly greater cost and stops at an unused (all-ones) one; its
-             * do-while looks at buffer 1 even when maxBuffers is 1.  Scalar, the replay of 35 intra candidates was a third of an I picture's time. */
-            unsigned long long bcost = ~0ull;
-            int bcand = -1, bpred = -1, evcount = 0, highest = 0;
-            const int maxb = __builtin_amdgcn_readfirstlane(M.max_buffers < 2 ? 2 : M.max_buffers);
-            for (int idx = __builtin_amdgcn_readfirstlane(ncand) - 1; idx >= 0; idx--) {
-                const unsigned long long c = md_readlane64(cst, idx);
-                const int ev = __builtin_amdgcn_readlane(evl, idx);
-                if (lane == highest) {
-                    bcand = idx;
-                    if (ev) {
-                        bcost = c;
-                        if (!(ev & 2))
-                            bpred = idx;
-                    }
-                }
-                evcount += ev != 0;
-                if (idx) { /* the first buffer holding the maximum: the buffers' costs read lane by lane (scalar) */
-                    unsigned long long m = 0;
-                    int h = 0;
-#pragma unroll
-                    for (int b = 0; b < MD_MAX_BUF; b++)
-                        if (b < maxb) {
-                            const unsigned long long v = md_readlane64(bcost, b);
-                            if (b == 0 || v > m)
-                                m = v, h = b;
+                MD_TR(26);
+                MD_SUB(9);
+                /* md_fast_loop_buffers (md_logic.h; ProductPerformFastLoop's second loop, :1990-2179) with the buffers in lanes 0..7 instead of LDS: the candidates
+                 * arrive from the last to the first, each goes into the buffer with the highest cost (an unused one first) = the FIRST buffer holding the maximum
+                 * over [0, maxBuffers) - the reference's scan starts at buffer 0, moves on a strictly greater cost and stops at an unused (all-ones) one; its
+                 * do-while looks at buffer 1 even when maxBuffers is 1.  Scalar, the replay of 35 intra candidates was a third of an I picture's time. */
+                unsigned long long bcost = ~0ull;
+                int bcand = -1, bpred = -1, evcount = 0, highest = 0;
+                const int maxb = __builtin_amdgcn_readfirstlane(M.max_buffers < 2 ? 2 : M.max_buffers);
+                for (int idx = __builtin_amdgcn_readfirstlane(ncand) - 1; idx >= 0; idx--) {
+                    const unsigned long long c = md_readlane64(cst, idx);
+                    const int ev = __builtin_amdgcn_readlane(evl, idx);
+                    if (lane == highest) {
+                        bcand = idx;
+                        if (ev) {
+                            bcost = c;
+                            if (!(ev & 2))
+                                bpred = idx;
                         }
-                    highest = h;
-                }
-            }
-            MD_TR(27);
-            MD_SUB(10);
-            if (lane < MD_MAX_BUF) {
-                M.B.fast_cost[lane] = bcost, M.B.full_cost[lane] = ~0ull, M.B.cand[lane] = (int16_t)bcand, M.B.pred[lane] = (int16_t)bpred;
-                M.types[lane] = bcand >= 0 ? M.cand[bcand].type : 0, M.ycbf[lane] = 0, M.full_dist[lane] = 0, M.merge_cost[lane] = M.skip_cost[lane] = 0;
-                M.y_bits[lane] = M.y_dist[lane][0] = M.y_dist[lane][1] = 0;
-            }
-            if (lane == 0)
-                M.B.evaluated_count = evcount;
-            EP_WAVE_SYNC();
-            if (lane == 0) {
-                int bufferTotal = M.buffer_total;
-                bufferTotal = evcount < bufferTotal ? evcount : bufferTotal;
-                const int same = evcount == bufferTotal;
-                M.full_count = md_pre_mode_decision(&M.B, M.types, same ? bufferTotal : M.max_buffers, same, M.best);
-                M.nfull = M.full_count < bufferTotal ? M.full_count : bufferTotal;
-            }
-            MD_TR(28);
-        }
-        __syncthreads();
-        MD_TR(29);
-        MD_PROF(4);
-        /* ---- full loop: a wave per surviving candidate (PerformFullLoop, :4351) ---- */
-        const int nfull = M.nfull;
-        bool split64 = false, fresh64 = false;
-        if constexpr (INTER) {
-            /* a 64x64 unit has four 32x32 transform units per candidate: a wave per (candidate, transform unit) instead of a wave per candidate - with the usual one or
-             * two survivors all four waves work.  The candidates of a 64x64 unit are motion-compensated (no intra candidate at depth 0). */
-            split64 = N == 64 && nfull <= 4 && !M.any_intra;
-            if (split64) {
-                bool sync = false;
-                for (int f = 0; f < nfull; f++) {
-                    const int ci = M.B.cand[M.best[f]], pci = M.B.pred[M.best[f]] < 0 ? ci : M.B.pred[M.best[f]];
-                    if (!(M.V.slot[pci] >= 0 && M.evaluated[pci])) {
-                        sync = true;
-                        if (wave == f)
-                            md_predict_inter_plane(M.V.refs, M.cand[pci], x0, y0, N, 0, lane, M.V.mc[wave], M.V.wpred[f], 0, 1, &M.V.rw, &M.V.rwc);
+                    }
+                    evcount += ev != 0;
+                    if (idx) { /* the first buffer holding the maximum: the buffers' costs read lane by lane (scalar) */
+                        unsigned long long m = 0;
+                        int h = 0;
+    #pragma unroll
+                        for (int b = 0; b < MD_MAX_BUF; b++)
+                            if (b < maxb) {
+                                const unsigned long long v = md_readlane64(bcost, b);
+                                if (b == 0 || v > m)
+                                    m = v, h = b;
+                            }
+                        highest = h;
                     }
                 }
-                if (sync)
-                    __syncthreads();
-                fresh64 = sync;
-                for (int f = 0; f < nfull; f++) {
-                    const int b = M.best[f], ci = M.B.cand[b], pci = M.B.pred[b] < 0 ? ci : M.B.pred[b];
-                    const uint8_t *pred = (M.V.slot[pci] >= 0 && M.evaluated[pci]) ? M.V.cpred[M.V.slot[pci]] : M.V.wpred[f];
-                    const int tu = wave, off = ((tu & 1) << 5) + ((tu >> 1) << 5) * 64;
-                    const MdFl o = md_full_loop_unit<32>(lane, &L.src[st.y * 64 + st.x] + off, 64, pred + off, 64, nullptr, M.tiles[wave], M.qbuf[wave], P.qp, P.slice_type, M.cost,
-                                                         M.cand[ci].type, M.cand[ci].intra_mode, 0, pf, M.rt);
-                    if (lane == 0)
-                        M.fl[b][tu] = o;
+                MD_TR(27);
+                MD_SUB(10);
+                if (lane < MD_MAX_BUF) {
+                    M.B.fast_cost[lane] = bcost, M.B.full_cost[lane] = ~0ull, M.B.cand[lane] = (int16_t)bcand, M.B.pred[lane] = (int16_t)bpred;
+                    M.types[lane] = bcand >= 0 ? M.cand[bcand].type : 0, M.ycbf[lane] = 0, M.full_dist[lane] = 0, M.merge_cost[lane] = M.skip_cost[lane] = 0;
+                    M.y_bits[lane] = M.y_dist[lane][0] = M.y_dist[lane][1] = 0;
+                }
+                if (lane == 0)
+                    M.B.evaluated_count = evcount;
+                EP_WAVE_SYNC();
+                if (lane == 0) {
+                    int bufferTotal = M.buffer_total;
+                    bufferTotal = evcount < bufferTotal ? evcount : bufferTotal;
+                    const int same = evcount == bufferTotal;
+                    M.full_count = md_pre_mode_decision(&M.B, M.types, same ? bufferTotal : M.max_buffers, same, M.best);
+                    M.nfull = M.full_count < bufferTotal ? M.full_count : bufferTotal;
+                }
+                MD_TR(28);
+            }
+            __syncthreads();
+            MD_TR(29);
+            MD_PROF(4);
+            /* ---- full loop: a wave per surviving candidate (PerformFullLoop, :4351) ---- */
+            const int nfull = M.nfull;
+            for (int f = wave; f < nfull; f += 4) {
+                MD_TR(30);
+                const int b = M.best[f], ci = M.B.cand[b];
+                const MdCand cd = M.cand[ci];
+                /* the buffer's luma prediction: the candidate the fast loop predicted there, or - predictionIsReadyLuma == 0 - a fresh one */
+                const bool fresh = ci == M.best_first && cd.type == MD_INTRA && open_loop && M.evaluated[ci];
+                const int pci = (fresh || M.B.pred[b] < 0) ? ci : M.B.pred[b];
+                const MdCand pc = M.cand[pci];
+                uint8_t *pred = M.V.pred[b];
+                int16_t *rc = M.V.recon_coeff[b];
+                if (pc.type != MD_INTER) {
+                    const int mode = pc.intra_mode;
+                    md_intra_block(mode, N, lgN, (!open_loop && md_mode_filtered(mode, lgN)) ? M.reff : M.ref, 1, lane, nullptr, 0, pred);
                     EP_WAVE_SYNC();
                 }
+                MD_TR(31);
+                MD_SUB(12);
+                md_full_loop_cand(lane, N, &L.src[st.y * 64 + st.x], pred, N, rc, M.tiles[wave], M.qbuf[wave], P, M.cost, M.rt, cd.type, cd.intra_mode, pf, M.fl[b]);
+                MD_TR(32);
+                MD_SUB(13);
             }
-        }
-        for (int f = wave; f < nfull && !split64; f += 4) {
-            MD_TR(30);
-            const int b = M.best[f], ci = M.B.cand[b];
-            const MdCand cd = M.cand[ci];
-            /* the buffer's luma prediction: the candidate the fast loop predicted there, or - predictionIsReadyLuma == 0 - a fresh one */
-            const bool fresh = ci == M.best_first && cd.type == MD_INTRA && open_loop && M.evaluated[ci];
-            const int pci = (fresh || M.B.pred[b] < 0) ? ci : M.B.pred[b];
-            const MdCand pc = M.cand[pci];
-            uint8_t *pred;
-            int16_t *rc = nullptr;
-            if constexpr (INTER) {
-                pred = M.V.wpred[wave];
-            } else {
-                pred = M.V.pred[b], rc = M.V.recon_coeff[b];
-            }
-            if (pc.type == MD_INTER) {
-                if constexpr (INTER) {
-                    if (M.V.slot[pci] >= 0 && M.evaluated[pci])
-                        pred = M.V.cpred[M.V.slot[pci]]; /* the fast loop's prediction of this candidate is still there */
+            MD_TR(33);
+            __syncthreads();
+            MD_TR(34);
+            MD_PROF(5);
+            /* ---- wave 0: TuCalcCostLuma + the full cost of every surviving candidate (a lane each), then lane 0: ProductFullModeDecision, CheckHighCostPartition ---- */
+            if (wave == 0) {
+                const bool have = lane < nfull;
+                int b = 0, ctype = 0;
+                uint32_t ycbf = 0;
+                unsigned long long bits = 0, dist[2] = {0, 0}, full = 0;
+                uint64_t mc = 0, sc = 0;
+                if (have) {
+                    const SvtAmdMdPicture &PL = M.pic; /* the rate tables beside the LCU */
+                    b = M.best[lane];
+                    const int ci = M.B.cand[b];
+                    const MdCand c = M.cand[ci];
+                    ctype = c.type;
+                    if (N == 64) {
+                        for (int tu = 0; tu < 4; tu++)
+                            md_tu_calc_cost(PL, M.fl[b][tu], c.type, 64, 32, tu + 1, &ycbf, &bits, dist);
+                    } else {
+                        md_tu_calc_cost(PL, M.fl[b][0], c.type, N, N, 0, &ycbf, &bits, dist);
+                    }
+                    if (M.lcu.chroma_encode_mode == 2 /* CHROMA_MODE_BEST */ || M.lcu.chroma_encode_mode == 1)
+                        bits = md_pf_coeff_bits(pf, P.qp, bits);
+                    if (c.type == MD_INTER)
+                        full = md_inter_full_luma_cost(&PL, &M.S.cu[leaf], &c, N, ycbf, M.fast_rate[ci], (const uint64_t *)dist, bits, &mc, &sc);
+                    else if (islice)
+                        full = md_intra_full_luma_cost_islice(&PL, lgN, ycbf, M.fast_rate[ci], dist[0], bits);
                     else
-                        md_predict_inter_plane(M.V.refs, pc, x0, y0, N, 0, lane, M.V.mc[wave], pred, 0, 1, &M.V.rw, &M.V.rwc);
+                        full = md_intra_full_luma_cost_pslice(&PL, N, ycbf, M.fast_rate[ci], dist[0], bits);
                 }
-            } else {
-                const int mode = pc.intra_mode;
-                md_intra_block(mode, N, lgN, (!open_loop && md_mode_filtered(mode, lgN)) ? M.reff : M.ref, 1, lane, nullptr, 0, pred);
+                /* the reference walks the candidates in order: an intra candidate after an inter one whose root cbf is 0 is not costed at all (full-loop escape, :4450-4460) and
+                 * keeps whatever its buffer held */
+                uint32_t prevRootCbf = 1;
+                unsigned long long bestFullCost = 0xFFFFFFFFull, kept = 0;
+                for (int g = 0; g < nfull; g++) {
+                    const int ty = __shfl(ctype, g);
+                    const uint32_t yc = __shfl(ycbf, g);
+                    const unsigned long long cs = __shfl(full, g);
+                    if (!islice && ty == MD_INTRA && prevRootCbf == 0)
+                        continue;
+                    kept |= 1ull << g;
+                    if (P.full_loop_escape && !islice && ty == MD_INTER && cs < bestFullCost)
+                        prevRootCbf = yc, bestFullCost = cs;
+                }
+                MD_TR(35);
+                MD_SUB(14);
+                if (have && ((kept >> lane) & 1ull)) {
+                    M.ycbf[b] = ycbf, M.full_dist[b] = (uint32_t)dist[0], M.B.full_cost[b] = full;
+                    M.merge_cost[b] = mc, M.skip_cost[b] = sc, M.y_bits[b] = bits, M.y_dist[b][0] = dist[0], M.y_dist[b][1] = dist[1];
+                }
                 EP_WAVE_SYNC();
             }
-            MD_TR(31);
-            MD_SUB(12);
-            md_full_loop_cand(lane, N, &L.src[st.y * 64 + st.x], pred, N, rc, M.tiles[wave], M.qbuf[wave], P, M.cost, M.rt, cd.type, cd.intra_mode, pf, M.fl[b]);
-            MD_TR(32);
-            MD_SUB(13);
-        }
-        if constexpr (INTER) {
-            /* CHROMA_MODE_FULL (PerformFullLoop :4443-4560): the chroma pair of every survivor - ChromaPrediction (the candidate's OWN prediction: the fast loop's when it
-             * evaluated the candidate, a fresh one otherwise), FullLoop_R + CuFullDistortionFastTuMode_R - as tasks (survivor, plane) on the waves the luma units left idle */
-            if (M.lcu.chroma_encode_mode == 1) {
-                if (fresh64) /* every wave is done with the fresh luma predictions in the waves' scratch before a chroma block lands there */
-                    __syncthreads();
-                const int Cn = N >> 1, lgc = lgN - 1, Tc = N == 64 ? 16 : Cn, ntu = N == 64 ? 4 : 1;
-                /* which wave takes which (survivor, plane) task: the waves that carried a luma unit start with 3 units of load, a chroma pair member costs 2 - each task
-                 * goes to the least loaded wave (every wave derives the same table; two survivors: both chroma pairs on the two waves the luma units left idle instead
-                 * of one member behind each luma unit) */
-                unsigned mine = 0;
-                {
-                    int load[4];
-#pragma unroll
-                    for (int w_ = 0; w_ < 4; w_++)
-                        load[w_] = (!split64 && w_ < nfull) ? 3 : 0;
-                    for (int tk = 0; tk < 2 * nfull; tk++) {
-                        int best_w = 0;
-#pragma unroll
-                        for (int w_ = 1; w_ < 4; w_++)
-                            if (load[w_] < load[best_w])
-                                best_w = w_;
-#pragma unroll
-                        for (int w_ = 0; w_ < 4; w_++)
-                            if (w_ == best_w)
-                                load[w_] += 2;
-                        if (best_w == wave)
-                            mine |= 1u << tk;
+            if (t == 0) {
+                int lowest = M.best[0];
+                unsigned long long lowestCost = ~0ull;
+                for (int f = 0; f < M.full_count; f++)
+                    if (M.B.full_cost[M.best[f]] < lowestCost)
+                        lowest = M.best[f], lowestCost = M.B.full_cost[M.best[f]];
+                if (ncand > 0) {
+                    const MdCand c = M.cand[M.B.cand[lowest]];
+                    MdCu &u = M.S.cu[leaf];
+                    M.S.local[leaf].cost = M.B.full_cost[lowest], M.S.local[leaf].full_distortion = M.full_dist[lowest];
+                    u.pred_mode = c.type, u.skip_flag = 0, u.intra_luma_mode = (uint8_t)(c.type == MD_INTRA ? c.intra_mode : 0x1F);
+                    u.ycbf = (uint8_t)(N == 64 ? (M.ycbf[lowest] & 0x1E) : (M.ycbf[lowest] & 1));
+                    u.inter_dir = (uint8_t)(c.type == MD_INTER ? c.dir : 3), u.merge_flag = (uint8_t)(c.type == MD_INTER ? c.merge_flag : 0), u.merge_index = c.merge_index;
+                    u.mv[0].x = u.mv[0].y = u.mv[1].x = u.mv[1].y = 0;
+                    if (c.type == MD_INTER) {
+                        if (c.dir != MD_L1)
+                            u.mv[0] = c.mv[0];
+                        if (c.dir != MD_L0)
+                            u.mv[1] = c.mv[1];
                     }
+                    u.merge_cost = M.merge_cost[lowest], u.skip_cost = M.skip_cost[lowest];
+                    u.y_coeff_bits = M.y_bits[lowest], u.y_dist[0] = M.y_dist[lowest][0], u.y_dist[1] = M.y_dist[lowest][1];
+                    u.fast_luma_rate = M.fast_rate[M.B.cand[lowest]], u.ycbf_mask = M.ycbf[lowest];
                 }
-                for (int tk = 0; tk < 2 * nfull; tk++) {
-                    if (!((mine >> tk) & 1u))
-                        continue;
-                    const int f = tk >> 1, pl = tk & 1, b = M.best[f], ci = M.B.cand[b];
-                    const MdCand cd = M.cand[ci];
-                    const uint8_t *pred;
-                    if (cd.type == MD_INTER && M.V.slot[ci] >= 0 && M.evaluated[ci]) {
-                        pred = M.V.cpred_c[M.V.slot[ci]][pl];
-                    } else {
-                        uint8_t *pw = M.V.wpred_c(wave, pl);
-                        if (cd.type == MD_INTER) {
-                            md_predict_inter_plane(M.V.refs, cd, x0, y0, N, 1 + pl, lane, M.V.mc[wave], pw, 0, 1, &M.V.rw, &M.V.rwc);
-                        } else {
-                            md_intra_block(cd.intra_mode, Cn, lgc, M.V.refc[pl], 0, lane, nullptr, 0, pw);
-                            EP_WAVE_SYNC();
-                        }
-                        pred = pw;
-                    }
-                    for (int tu = 0; tu < ntu; tu++) {
-                        const int ox = ntu == 1 ? 0 : (tu & 1) << 4, oy = ntu == 1 ? 0 : (tu >> 1) << 4;
-                        uint32_t nz;
-                        unsigned long long d[2], bt;
-                        md_chroma_tu(lane, Tc, &M.V.src_c[pl][((st.y >> 1) + oy) * 32 + (st.x >> 1) + ox], pred + oy * Cn + ox, Cn, M.tiles[wave], M.qbuf[wave], P, M.cost, M.rt, cd.type,
-                                     cd.intra_mode, 1 + pl, pf, &nz, d, &bt);
-                        if (lane == 0) {
-                            MdFl o;
-                            o.nz = nz, o.d0 = (uint32_t)d[0], o.d1 = (uint32_t)d[1], o.bits = (uint32_t)bt;
-                            M.V.flc[b][pl][tu] = o;
-                        }
-                    }
+                M.lowest = lowest;
+                M.S.local[leaf].mdc_index = (uint8_t)M.cu_idx;
+                const int exitParent = md_check_high_cost_partition(&P, &M.lcu, &M.S, leaf);
+                M.do_recon = exitParent < 0 && ncand > 0 && !open_loop, M.exited = exitParent >= 0;
+                if (exitParent >= 0) {
+                    M.leaf = exitParent, M.cu_idx = M.S.local[exitParent].mdc_index;
+                    M.S.cu[exitParent].split = 0;
+                    M.last = md_inter_depth_decision(&P, &M.S, exitParent, lcu_x, lcu_y, 1, 0);
+                } else if (open_loop) { /* no reconstruction to wait for: the inter-depth decision follows at once */
+                    M.last = md_inter_depth_decision(&P, &M.S, leaf, lcu_x, lcu_y, 0, md_stop_split(&P, &M.lcu, st.depth, M.S.local[leaf].full_distortion));
                 }
+                if (exitParent >= 0 || open_loop)
+                    M.update = M.S.cu[M.last].split == 0;
+                MD_TR(36);
             }
-        }
-        MD_TR(33);
-        __syncthreads();
-        MD_TR(34);
-        MD_PROF(5);
-        /* ---- wave 0: TuCalcCostLuma + the full cost of every surviving candidate (a lane each), then lane 0: ProductFullModeDecision, CheckHighCostPartition ---- */
-        if (wave == 0) {
-            const bool have = lane < nfull;
-            int b = 0, ctype = 0;
-            uint32_t ycbf = 0;
-            unsigned long long bits = 0, dist[2] = {0, 0}, full = 0;
-            uint64_t mc = 0, sc = 0;
-            if (have) {
-                const SvtAmdMdPicture &PL = M.pic; /* the rate tables beside the LCU */
-                b = M.best[lane];
-                const int ci = M.B.cand[b];
-                const MdCand c = M.cand[ci];
-                ctype = c.type;
-                if (N == 64) {
-                    for (int tu = 0; tu < 4; tu++)
-                        md_tu_calc_cost(PL, M.fl[b][tu], c.type, 64, 32, tu + 1, &ycbf, &bits, dist);
-                } else {
-                    md_tu_calc_cost(PL, M.fl[b][0], c.type, N, N, 0, &ycbf, &bits, dist);
-                }
-                if (M.lcu.chroma_encode_mode == 2 /* CHROMA_MODE_BEST */ || M.lcu.chroma_encode_mode == 1)
-                    bits = md_pf_coeff_bits(pf, P.qp, bits);
-                bool with_chroma = false;
-                if constexpr (INTER) {
-                    if (M.lcu.chroma_encode_mode == 1) { /* InterFullCost / MergeSkipFullCost / IntraFullCostPslice: the chroma loop's sums join the luma ones */
-                        with_chroma = true;
-                        const int ntu = N == 64 ? 4 : 1;
-                        uint32_t cbf[2] = {0, 0};
-                        uint64_t cbits[2] = {0, 0}, cdist[2][2] = {{0, 0}, {0, 0}};
-                        for (int pl = 0; pl < 2; pl++)
-                            for (int tu = 0; tu < ntu; tu++) {
-                                const MdFl o = M.V.flc[b][pl][tu];
-                                cbf[pl] |= (uint32_t)(o.nz != 0) << (ntu == 1 ? 0 : tu + 1);
-                                cbits[pl] += o.bits, cdist[pl][0] += o.d0, cdist[pl][1] += o.d1;
-                            }
-                        const uint64_t yd[2] = {dist[0], dist[1]};
-                        if (c.type == MD_INTER)
-                            full = md_inter_full_cost(&PL, M.V.X.chroma_weight, &M.S.cu[leaf], &c, N, ycbf, cbf, M.fast_rate[ci], yd, cdist, bits, cbits, &mc, &sc);
-                        else
-                            full = md_intra_full_cost_pslice(&PL, M.V.X.chroma_weight, N, ycbf, cbf, M.fast_rate[ci], dist[0], cdist, bits, cbits);
-                    }
-                }
-                if (with_chroma)
-                    ;
-                else if (c.type == MD_INTER)
-                    full = md_inter_full_luma_cost(&PL, &M.S.cu[leaf], &c, N, ycbf, M.fast_rate[ci], (const uint64_t *)dist, bits, &mc, &sc);
-                else if (islice)
-                    full = md_intra_full_luma_cost_islice(&PL, lgN, ycbf, M.fast_rate[ci], dist[0], bits);
-                else
-                    full = md_intra_full_luma_cost_pslice(&PL, N, ycbf, M.fast_rate[ci], dist[0], bits);
-            }
-            /* the reference walks the candidates in order: an intra candidate after an inter one whose root cbf is 0 is not costed at all (full-loop escape, :4450-4460) and
-             * keeps whatever its buffer held */
-            uint32_t prevRootCbf = 1;
-            unsigned long long bestFullCost = 0xFFFFFFFFull, kept = 0;
-            for (int g = 0; g < nfull; g++) {
-                const int ty = __shfl(ctype, g);
-                const uint32_t yc = __shfl(ycbf, g);
-                const unsigned long long cs = __shfl(full, g);
-                if (!islice && ty == MD_INTRA && prevRootCbf == 0)
-                    continue;
-                kept |= 1ull << g;
-                if (P.full_loop_escape && !islice && ty == MD_INTER && cs < bestFullCost)
-                    prevRootCbf = yc, bestFullCost = cs;
-            }
-            MD_TR(35);
-            MD_SUB(14);
-            if (have && ((kept >> lane) & 1ull)) {
-                M.ycbf[b] = ycbf, M.full_dist[b] = (uint32_t)dist[0], M.B.full_cost[b] = full;
-                M.merge_cost[b] = mc, M.skip_cost[b] = sc, M.y_bits[b] = bits, M.y_dist[b][0] = dist[0], M.y_dist[b][1] = dist[1];
-            }
-            EP_WAVE_SYNC();
-        }
-        if (t == 0) {
-            int lowest = M.best[0];
-            unsigned long long lowestCost = ~0ull;
-            for (int f = 0; f < M.full_count; f++)
-                if (M.B.full_cost[M.best[f]] < lowestCost)
-                    lowest = M.best[f], lowestCost = M.B.full_cost[M.best[f]];
-            if (ncand > 0) {
-                const MdCand c = M.cand[M.B.cand[lowest]];
-                MdCu &u = M.S.cu[leaf];
-                M.S.local[leaf].cost = M.B.full_cost[lowest], M.S.local[leaf].full_distortion = M.full_dist[lowest];
-                u.pred_mode = c.type, u.skip_flag = 0, u.intra_luma_mode = (uint8_t)(c.type == MD_INTRA ? c.intra_mode : 0x1F);
-                u.ycbf = (uint8_t)(N == 64 ? (M.ycbf[lowest] & 0x1E) : (M.ycbf[lowest] & 1));
-                u.inter_dir = (uint8_t)(c.type == MD_INTER ? c.dir : 3), u.merge_flag = (uint8_t)(c.type == MD_INTER ? c.merge_flag : 0), u.merge_index = c.merge_index;
-                u.mv[0].x = u.mv[0].y = u.mv[1].x = u.mv[1].y = 0;
-                if (c.type == MD_INTER) {
-                    if (c.dir != MD_L1)
-                        u.mv[0] = c.mv[0];
-                    if (c.dir != MD_L0)
-                        u.mv[1] = c.mv[1];
-                }
-                u.merge_cost = M.merge_cost[lowest], u.skip_cost = M.skip_cost[lowest];
-                u.y_coeff_bits = M.y_bits[lowest], u.y_dist[0] = M.y_dist[lowest][0], u.y_dist[1] = M.y_dist[lowest][1];
-                u.fast_luma_rate = M.fast_rate[M.B.cand[lowest]], u.ycbf_mask = M.ycbf[lowest];
-            }
-            M.lowest = lowest;
-            M.S.local[leaf].mdc_index = (uint8_t)M.cu_idx;
-            const int exitParent = md_check_high_cost_partition(&P, &M.lcu, &M.S, leaf);
-            M.do_recon = exitParent < 0 && ncand > 0 && !open_loop, M.exited = exitParent >= 0;
-            if (exitParent >= 0) {
-                M.leaf = exitParent, M.cu_idx = M.S.local[exitParent].mdc_index;
-                M.S.cu[exitParent].split = 0;
-                M.last = md_inter_depth_decision(&P, &M.S, exitParent, lcu_x, lcu_y, 1, 0);
-            } else if (open_loop) { /* no reconstruction to wait for: the inter-depth decision follows at once */
-                M.last = md_inter_depth_decision(&P, &M.S, leaf, lcu_x, lcu_y, 0, md_stop_split(&P, &M.lcu, st.depth, M.S.local[leaf].full_distortion));
-            }
-            if (exitParent >= 0 || open_loop)
-                M.update = M.S.cu[M.last].split == 0;
-            MD_TR(36);
-        }
-        __syncthreads();
-        MD_TR(37);
-        MD_PROF(6);
-        if constexpr (!INTER) {
+            __syncthreads();
+            MD_TR(37);
+            MD_PROF(6);
             /* ---- wave 0: the winner's reconstruction ---- */
             if (M.do_recon && wave == 0) {
                 const int b = M.lowest;
@@ -2828,14 +2519,12 @@ __device__ __forceinline__ void md_lcu(const MdPictureDev &D, const SvtAmdMdPict
             }
             __syncthreads();
             MD_PROF(7);
-        }
-        /* ---- all lanes: ModeDecisionUpdateNeighborArrays of the unit the decision ended on ---- */
-        if (M.update) {
-            const int last = M.last;
-            const MdStats ls = md_stats(last);
-            const MdCu u = M.S.cu[last];
-            const uint32_t w = (uint32_t)u.pred_mode | ((uint32_t)u.intra_luma_mode << 8) | ((uint32_t)ls.depth << 16) | ((uint32_t)u.skip_flag << 24);
-            if constexpr (!INTER) {
+            /* ---- all lanes: ModeDecisionUpdateNeighborArrays of the unit the decision ended on ---- */
+            if (M.update) {
+                const int last = M.last;
+                const MdStats ls = md_stats(last);
+                const MdCu u = M.S.cu[last];
+                const uint32_t w = (uint32_t)u.pred_mode | ((uint32_t)u.intra_luma_mode << 8) | ((uint32_t)ls.depth << 16) | ((uint32_t)u.skip_flag << 24);
                 if (!open_loop) {
                     const uint8_t *srcp = M.V.best_rec[ls.depth];
                     for (int e = t; e < ls.size * ls.size; e += 256) {
@@ -2843,43 +2532,36 @@ __device__ __forceinline__ void md_lcu(const MdPictureDev &D, const SvtAmdMdPict
                         *L.at(ls.x + x, ls.y + y) = srcp[(ls.y + y) * 64 + ls.x + x];
                     }
                 }
+                const int cells = ls.size >> 2;
+                for (int e = t; e < cells * cells; e += 256)
+                    L.info[((ls.y >> 2) + e / cells + 1) * 36 + (ls.x >> 2) + e % cells + 1] = w;
             }
-            const int cells = ls.size >> 2;
-            for (int e = t; e < cells * cells; e += 256)
-                L.info[((ls.y >> 2) + e / cells + 1) * 36 + (ls.x >> 2) + e % cells + 1] = w;
-            if constexpr (INTER) {
-                const int c8 = ls.size >> 3;
-                MdMvUnit mu;
-                mu.mv[0] = u.mv[0], mu.mv[1] = u.mv[1], mu.dir = u.inter_dir, mu.avail = 0, mu.pad[0] = mu.pad[1] = 0;
-                for (int e = t; e < c8 * c8; e += 256)
-                    M.V.mvu[((ls.y >> 3) + e / c8 + 1) * 18 + (ls.x >> 3) + e % c8 + 1] = mu;
+            MD_TR(38);
+            __syncthreads();
+            MD_TR(39);
+            if (t == 0) {
+                const int cur = M.leaf; /* the unit the loop stands on: the tested one, or the parent a partition exit fell back to */
+                const MdStats cs = md_stats(cur);
+                int cuIdx = M.cu_idx;
+                if (M.S.cu[cur].split)
+                    cuIdx++;
+                else if (lh < 64)
+                    cuIdx++;
+                else
+                    cuIdx += md_next_cu_step(&M.lcu, cuIdx, cs.depth);
+                M.cu_idx = cuIdx;
+                M.done = cuIdx >= M.lcu.leaf_count;
+    #ifdef MD_TRACE
+                g_md_trace_on = D.trace && lcu == D.trace_lcu && cuIdx >= D.trace_unit && cuIdx < D.trace_unit + 2;
+                if (D.trace && lcu == D.trace_lcu)
+                    D.trace[4 * (1 + MD_TRACE_N) + 3] += 0x10000ull + (g_md_trace_on ? 1 : 0) + ((unsigned long long)g_md_trace_n[0] << 32);
+    #endif
             }
+            __syncthreads();
+            MD_PROF(8);
+            if (M.done)
+                break;
         }
-        MD_TR(38);
-        __syncthreads();
-        MD_TR(39);
-        if (t == 0) {
-            const int cur = M.leaf; /* the unit the loop stands on: the tested one, or the parent a partition exit fell back to */
-            const MdStats cs = md_stats(cur);
-            int cuIdx = M.cu_idx;
-            if (M.S.cu[cur].split)
-                cuIdx++;
-            else if (lh < 64)
-                cuIdx++;
-            else
-                cuIdx += md_next_cu_step(&M.lcu, cuIdx, cs.depth);
-            M.cu_idx = cuIdx;
-            M.done = cuIdx >= M.lcu.leaf_count;
-#ifdef MD_TRACE
-            g_md_trace_on = D.trace && lcu == D.trace_lcu && cuIdx >= D.trace_unit && cuIdx < D.trace_unit + 2;
-            if (D.trace && lcu == D.trace_lcu)
-                D.trace[4 * (1 + MD_TRACE_N) + 3] += 0x10000ull + (g_md_trace_on ? 1 : 0) + ((unsigned long long)g_md_trace_n[0] << 32);
-#endif
-        }
-        __syncthreads();
-        MD_PROF(8);
-        if (M.done)
-            break;
     }
     /* ---- the LCU's state leaves LDS: neighbour maps of the picture + the decision record ---- */
     if (!INTER) {
@@ -3150,8 +2832,16 @@ __global__ __launch_bounds__(256) void k_md_picture(const MdPictureDev *__restri
     }
 }
 
-static_assert(sizeof(MdShared<true>) + sizeof(MdPictureDev) + 64 <= 160 * 1024 && sizeof(MdShared<false>) + sizeof(MdPictureDev) + 64 <= 160 * 1024,
-              "the LCU state has to fit the 160 KB of LDS of a CU");
+/* every static __shared__ object k_md_picture holds beside the LCU state: the picture's descriptor (s_D), the ticket (s_ticket), the forward transforms' operands and
+ * their debug switch (md_dct_operands_init), in -DMD_TRACE builds the trace buffers (encdec_device.h); 64 bytes for the objects' alignment */
+#ifdef MD_TRACE
+constexpr size_t MD_LDS_TRACE = sizeof(g_md_trace) + sizeof(g_md_trace_n) + sizeof(g_md_trace_on);
+#else
+constexpr size_t MD_LDS_TRACE = 0;
+#endif
+constexpr size_t MD_LDS_BESIDE = sizeof(MdPictureDev) + sizeof(unsigned) + sizeof(s_dct_op) + sizeof(s_md_force_bfly) + MD_LDS_TRACE + 64;
+static_assert(sizeof(MdShared<true>) + MD_LDS_BESIDE <= 160 * 1024 && sizeof(MdShared<false>) + MD_LDS_BESIDE <= 160 * 1024,
+              "the LCU state and the kernel's other shared objects have to fit the 160 KB of LDS of a CU");
 
 /* ---- host side ------------------------------------------------------------------------------------------------------------- */
 extern "C" int svt_amd_md_picture_supported(const SvtAmdMdPicture *P) { return P ? md_picture_supported(P) : 0; }
