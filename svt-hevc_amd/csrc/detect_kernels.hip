@@ -17,7 +17,7 @@
  * Bound: HBM / latency - 1/4 B/pel (means, the even rows of both planes: half of the 1/2 B/pel chroma), 1/32 B/pel touched lines for the histograms, 256 B per LCU
  * for the detectors.
  */
-#include "svt_amd_internal.h"
+#include "pa_batch.h"
 #include <string.h>
 
 struct ChromaJobDev {
@@ -31,7 +31,6 @@ struct ChromaJobDev {
     int32_t pad;
 };
 static_assert(sizeof(ChromaJobDev) == 64, "ChromaJobDev layout");
-#define CHROMA_TABLE_BYTES (sizeof(ChromaJobDev) * SVT_AMD_MAX_BATCH)
 #define CHROMA_SUMS_BYTES ((size_t)SVT_AMD_MAX_BATCH * 64 * 2 * 8)
 #define CHROMA_STRIPS 8
 
@@ -52,7 +51,6 @@ struct DetectJobDev {
     int32_t logo_cols, logo_rows;  /* the potentialLogoLcu map of the resolution class, in LCUs (Codec/EbSequenceControlSet.c:253-272) */
 };
 static_assert(sizeof(DetectJobDev) == 48, "DetectJobDev layout");
-#define DETECT_TABLE_BYTES (sizeof(DetectJobDev) * SVT_AMD_MAX_BATCH)
 #define DETECT_RED_BYTES (sizeof(DetectReduce) * SVT_AMD_MAX_BATCH)
 #define DETECT_MAX_LCUS 16384
 
@@ -323,16 +321,14 @@ __global__ __launch_bounds__(256) void k_detect_finish(const DetectJobDev *__res
 
 /* ---------------------------------------------------------------- host side ---------------------------------------------------------------- */
 
-static bool chroma_regions_ok(int regions_w, int regions_h) { return regions_w >= 1 && regions_h >= 1 && regions_w * regions_h <= 64; }
-
 extern "C" size_t svt_amd_chroma_stats_bytes(uint16_t luma_width, uint16_t luma_height, int which, int regions_w, int regions_h)
 {
-    const size_t lcus = (size_t)((luma_width + 63) / 64) * (size_t)((luma_height + 63) / 64);
+    const size_t lcus = (size_t)svt_amd_lcu_count(luma_width, luma_height);
     switch (which) {
     case SVT_AMD_CHROMA_MEANS:
         return lcus * sizeof(SvtAmdPaLcuChroma);
     case SVT_AMD_CHROMA_HISTOGRAM:
-        return chroma_regions_ok(regions_w, regions_h) ? (size_t)regions_w * regions_h * 2 * 256 * sizeof(uint32_t) : 0;
+        return svt_amd_regions_ok(regions_w, regions_h) ? (size_t)regions_w * regions_h * 2 * 256 * sizeof(uint32_t) : 0;
     case SVT_AMD_CHROMA_REGION_AVG:
         return 128;
     case SVT_AMD_CHROMA_SUM:
@@ -343,7 +339,7 @@ extern "C" size_t svt_amd_chroma_stats_bytes(uint16_t luma_width, uint16_t luma_
 
 extern "C" size_t svt_amd_picture_detect_bytes(uint16_t luma_width, uint16_t luma_height, int which)
 {
-    const size_t lcus = (size_t)((luma_width + 63) / 64) * (size_t)((luma_height + 63) / 64);
+    const size_t lcus = (size_t)svt_amd_lcu_count(luma_width, luma_height);
     switch (which) {
     case SVT_AMD_DETECT_LCU:
         return lcus * sizeof(SvtAmdPaLcuDetect);
@@ -353,37 +349,30 @@ extern "C" size_t svt_amd_picture_detect_bytes(uint16_t luma_width, uint16_t lum
     return 0;
 }
 
-#define DETECT_BAD(...)                        \
-    do {                                       \
-        svt_amd_set_error(__VA_ARGS__);        \
-        return SVT_AMD_ERR_BAD_PARAM;          \
-    } while (0)
-
 extern "C" int svt_amd_chroma_stats_batch_launch(SvtAmdContext *ctx, const SvtAmdChromaJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
                                                  int regions_w, int regions_h, const SvtAmdChromaArrays *out)
 {
-    if (!ctx || !jobs || !out || num_jobs < 1 || num_jobs > SVT_AMD_MAX_BATCH)
-        DETECT_BAD("svt_amd_chroma_stats_batch_launch: a context, an output table and 1..%d jobs", SVT_AMD_MAX_BATCH);
+    SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
     const int w = luma_width, h = luma_height;
     if (w < 2 || h < 2 || (w & 1) || (h & 1))
-        DETECT_BAD("svt_amd_chroma_stats_batch_launch: job 0: a 4:2:0 picture of %dx%d", w, h);
-    const int wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl;
+        SVT_AMD_BAD("%s: job 0: a 4:2:0 picture of %dx%d", __func__, w, h);
+    const int wl = (w + 63) / 64, lcus = svt_amd_lcu_count(w, h);
     bool any_means = false, any_hist = false;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdChromaJob &j = jobs[i];
         if (!j.want_means && !j.want_histogram)
             continue;
         if (!j.cb || !j.cr)
-            DETECT_BAD("svt_amd_chroma_stats_batch_launch: job %d wants chroma statistics, but has no %s plane", i, j.cb ? "Cr" : "Cb");
+            SVT_AMD_BAD("%s: job %d wants chroma statistics, but has no %s plane", __func__, i, j.cb ? "Cr" : "Cb");
         if (j.pitch < (uint32_t)(w / 2) || j.pitch > 0x7FFFFFFFu)
-            DETECT_BAD("svt_amd_chroma_stats_batch_launch: job %d: a pitch of %u bytes for %d chroma samples a row", i, j.pitch, w / 2);
+            SVT_AMD_BAD("%s: job %d: a pitch of %u bytes for %d chroma samples a row", __func__, i, j.pitch, w / 2);
         if (j.want_means && !out->means)
-            DETECT_BAD("svt_amd_chroma_stats_batch_launch: job %d wants block means, but there is no means array", i);
+            SVT_AMD_BAD("%s: job %d wants block means, but there is no means array", __func__, i);
         if (j.want_histogram && !out->histogram)
-            DETECT_BAD("svt_amd_chroma_stats_batch_launch: job %d wants histograms, but there is no histogram array", i);
-        if (j.want_histogram && (!chroma_regions_ok(regions_w, regions_h) || w / regions_w < 8 || h / regions_h < 8))
-            DETECT_BAD("svt_amd_chroma_stats_batch_launch: job %d: %d x %d regions of a %dx%d picture", i, regions_w, regions_h, w, h);
+            SVT_AMD_BAD("%s: job %d wants histograms, but there is no histogram array", __func__, i);
+        if (j.want_histogram && (!svt_amd_regions_ok(regions_w, regions_h) || w / regions_w < 8 || h / regions_h < 8))
+            SVT_AMD_BAD("%s: job %d: %d x %d regions of a %dx%d picture", __func__, i, regions_w, regions_h, w, h);
         any_means |= j.want_means != 0;
         any_hist |= j.want_histogram != 0;
     }
@@ -391,11 +380,9 @@ extern "C" int svt_amd_chroma_stats_batch_launch(SvtAmdContext *ctx, const SvtAm
         return SVT_AMD_OK;
     const int regions = any_hist ? regions_w * regions_h : 0;
 
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_chroma) /* once per context: the descriptor table and the per-region sums the histogram kernels accumulate into */
-        HIP_TRY(hipMalloc(&ctx->d_chroma, CHROMA_TABLE_BYTES + CHROMA_SUMS_BYTES));
-    ChromaJobDev *d_tab = (ChromaJobDev *)ctx->d_chroma;
-    unsigned long long *d_sums = (unsigned long long *)((uint8_t *)ctx->d_chroma + CHROMA_TABLE_BYTES);
+    ChromaJobDev *d_tab;
+    unsigned long long *d_sums; /* the per-region sums the histogram kernels accumulate into */
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_chroma, sizeof(ChromaJobDev), CHROMA_SUMS_BYTES, (void **)&d_tab, (void **)&d_sums));
     const size_t b_hist = (size_t)regions * 2 * 256 * 4;
     static thread_local ChromaJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
@@ -415,23 +402,13 @@ extern "C" int svt_amd_chroma_stats_batch_launch(SvtAmdContext *ctx, const SvtAm
         }
     }
     /* the table goes up in stream order: a batch queued behind another one on this lane does not overwrite the table the first one still reads */
-    int rc = svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(ChromaJobDev) * (size_t)num_jobs);
-    if (rc)
-        return rc;
+    SVT_AMD_TRY(svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(ChromaJobDev) * (size_t)num_jobs));
     if (any_hist) { /* what the histogram kernels accumulate into: one memset per run of pictures that want them */
         HIP_TRY(hipMemsetAsync(d_sums, 0, (size_t)num_jobs * 128 * 8, st));
-        for (int i = 0; i < num_jobs;) {
-            if (!jobs[i].want_histogram) {
-                i++;
-                continue;
-            }
-            int e = i;
-            while (e < num_jobs && jobs[e].want_histogram)
-                e++;
+        for (int i = 0, e; svt_amd_batch_run(&jobs[0].want_histogram, sizeof(jobs[0]), num_jobs, &i, &e); i = e) {
             HIP_TRY(hipMemsetAsync(out->histogram + (size_t)i * regions * 2 * 256, 0, (size_t)(e - i) * b_hist, st));
             if (out->sum_chroma)
                 HIP_TRY(hipMemsetAsync(out->sum_chroma + (size_t)i * 2, 0, (size_t)(e - i) * 16, st));
-            i = e;
         }
     }
     if (any_means)
@@ -448,30 +425,27 @@ extern "C" int svt_amd_chroma_stats_batch_launch(SvtAmdContext *ctx, const SvtAm
 extern "C" int svt_amd_picture_detect_batch_launch(SvtAmdContext *ctx, const SvtAmdDetectJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
                                                    const SvtAmdDetectArrays *out)
 {
-    if (!ctx || !jobs || !out || num_jobs < 1 || num_jobs > SVT_AMD_MAX_BATCH)
-        DETECT_BAD("svt_amd_picture_detect_batch_launch: a context, an output table and 1..%d jobs", SVT_AMD_MAX_BATCH);
+    SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
     const int w = luma_width, h = luma_height;
     const int wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl;
     if (w < 1 || h < 1 || lcus > DETECT_MAX_LCUS)
-        DETECT_BAD("svt_amd_picture_detect_batch_launch: job 0: a picture of %dx%d (at most %d LCUs)", w, h, DETECT_MAX_LCUS);
+        SVT_AMD_BAD("%s: job 0: a picture of %dx%d (at most %d LCUs)", __func__, w, h, DETECT_MAX_LCUS);
     if (!out->lcu || !out->picture)
-        DETECT_BAD("svt_amd_picture_detect_batch_launch: job 0: there is no %s array", out->lcu ? "picture" : "lcu");
+        SVT_AMD_BAD("%s: job 0: there is no %s array", __func__, out->lcu ? "picture" : "lcu");
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdDetectJob &j = jobs[i];
         if (!j.stats)
-            DETECT_BAD("svt_amd_picture_detect_batch_launch: job %d has no block statistics", i);
+            SVT_AMD_BAD("%s: job %d has no block statistics", __func__, i);
         if (j.want_edge16 && !j.chroma)
-            DETECT_BAD("svt_amd_picture_detect_batch_launch: job %d wants the 16x16 edge map, but has no chroma means", i);
+            SVT_AMD_BAD("%s: job %d wants the 16x16 edge map, but has no chroma means", __func__, i);
         if (j.resolution_class > 3)
-            DETECT_BAD("svt_amd_picture_detect_batch_launch: job %d: resolution class %d", i, j.resolution_class);
+            SVT_AMD_BAD("%s: job %d: resolution class %d", __func__, i, j.resolution_class);
     }
 
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_detect) /* once per context: the descriptor table and the per-picture reduction the per-LCU kernel accumulates into */
-        HIP_TRY(hipMalloc(&ctx->d_detect, DETECT_TABLE_BYTES + DETECT_RED_BYTES));
-    DetectJobDev *d_tab = (DetectJobDev *)ctx->d_detect;
-    DetectReduce *d_red = (DetectReduce *)((uint8_t *)ctx->d_detect + DETECT_TABLE_BYTES);
+    DetectJobDev *d_tab;
+    DetectReduce *d_red; /* the per-picture reduction the per-LCU kernel accumulates into */
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_detect, sizeof(DetectJobDev), DETECT_RED_BYTES, (void **)&d_tab, (void **)&d_red));
     static thread_local DetectJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
     for (int i = 0; i < num_jobs; i++) {
@@ -486,9 +460,7 @@ extern "C" int svt_amd_picture_detect_batch_launch(SvtAmdContext *ctx, const Svt
         d.logo_cols = j.resolution_class == 0 ? 3 : j.resolution_class < 3 ? 7 : 14;
         d.logo_rows = j.resolution_class == 0 ? 2 : j.resolution_class < 3 ? 4 : 8;
     }
-    int rc = svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(DetectJobDev) * (size_t)num_jobs);
-    if (rc)
-        return rc;
+    SVT_AMD_TRY(svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(DetectJobDev) * (size_t)num_jobs));
     /* the stages are ordered on the lane: a batch queued behind this one zeroes the reduction only after this one's finish kernel has read it */
     HIP_TRY(hipMemsetAsync(d_red, 0, sizeof(DetectReduce) * (size_t)num_jobs, st));
     hipLaunchKernelGGL(k_detect_lcu, dim3((unsigned)lcus, (unsigned)num_jobs), dim3(64), 0, st, (const DetectJobDev *)d_tab, w, h, wl, hl);

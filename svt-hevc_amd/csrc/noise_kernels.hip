@@ -17,7 +17,7 @@
  * Traffic: the plane is read once (1 B/pel of it: 1, 1/4 or 1/16 B per luma sample), one byte per evaluated LCU written.  Measured at a third of the copy rate for the
  * full method: bound by load instructions (10 8-byte and 16 byte loads a lane, eight half lines a wave load) and latency, not by HBM.
  */
-#include "svt_amd_internal.h"
+#include "pa_batch.h"
 #include <string.h>
 
 struct NoiseJobDev {
@@ -33,7 +33,6 @@ struct NoiseJobDev {
 };
 static_assert(sizeof(NoiseJobDev) == 64, "NoiseJobDev layout");
 #define NOISE_PARTS 8
-#define NOISE_TABLE_BYTES (sizeof(NoiseJobDev) * SVT_AMD_MAX_BATCH)
 #define NOISE_RED_BYTES ((size_t)SVT_AMD_MAX_BATCH * NOISE_PARTS * 8)
 
 /* (top + bottom + left + right + 4 * centre) >> 3 of four samples: even and odd bytes in 16-bit fields (8 * 255 fits), no carry between fields */
@@ -162,7 +161,7 @@ __global__ __launch_bounds__(64) void k_noise_finish(const NoiseJobDev *__restri
 
 /* ---------------------------------------------------------------- host side ---------------------------------------------------------------- */
 
-static size_t noise_flat_bytes(int w, int h) { return (((size_t)((w + 63) / 64) * (size_t)((h + 63) / 64)) + 63) & ~(size_t)63; }
+static size_t noise_flat_bytes(int w, int h) { return ((size_t)svt_amd_lcu_count(w, h) + 63) & ~(size_t)63; }
 
 extern "C" size_t svt_amd_noise_detect_bytes(uint16_t luma_width, uint16_t luma_height, int which)
 {
@@ -175,48 +174,28 @@ extern "C" size_t svt_amd_noise_detect_bytes(uint16_t luma_width, uint16_t luma_
     return 0;
 }
 
-#define NOISE_BAD(...)                         \
-    do {                                       \
-        svt_amd_set_error(__VA_ARGS__);        \
-        return SVT_AMD_ERR_BAD_PARAM;          \
-    } while (0)
-
 extern "C" int svt_amd_noise_detect_batch_launch(SvtAmdContext *ctx, const SvtAmdNoiseJob *jobs, int num_jobs, const SvtAmdNoiseArrays *out)
 {
-    if (!ctx || !jobs || !out || num_jobs < 1 || num_jobs > SVT_AMD_MAX_BATCH)
-        NOISE_BAD("svt_amd_noise_detect_batch_launch: a context, an output table and 1..%d jobs", SVT_AMD_MAX_BATCH);
+    SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
     if (!out->flat_noise || !out->picture)
-        NOISE_BAD("svt_amd_noise_detect_batch_launch: job 0: there is no %s array", out->flat_noise ? "picture" : "flat_noise");
-    if (jobs[0].cur_slot < 0 || jobs[0].cur_slot >= ctx->num_slots)
-        NOISE_BAD("svt_amd_noise_detect_batch_launch: job 0: bad slot %d", jobs[0].cur_slot);
-    const DevPicture *c0 = &ctx->slots[jobs[0].cur_slot];
-    const int w = c0->width, h = c0->height, wl = (w + 63) / 64;
+        SVT_AMD_BAD("%s: job 0: there is no %s array", __func__, out->flat_noise ? "picture" : "flat_noise");
+    int w = 0, h = 0;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdNoiseJob &j = jobs[i];
-        if (j.cur_slot < 0 || j.cur_slot >= ctx->num_slots || !ctx->slots[j.cur_slot].valid)
-            NOISE_BAD("svt_amd_noise_detect_batch_launch: job %d: slot %d holds no picture", i, j.cur_slot);
-        const DevPicture *c = &ctx->slots[j.cur_slot];
-        if (c->width != w || c->height != h)
-            NOISE_BAD("svt_amd_noise_detect_batch_launch: pictures of different sizes in one batch (job %d: %dx%d, job 0: %dx%d)", i, c->width, c->height, w, h);
+        SVT_AMD_TRY(svt_amd_batch_slot(__func__, ctx, i, j.cur_slot, &w, &h));
         if (j.method != SVT_AMD_NOISE_HALF && j.method != SVT_AMD_NOISE_QUARTER && j.method != SVT_AMD_NOISE_FULL)
-            NOISE_BAD("svt_amd_noise_detect_batch_launch: job %d: noise detection method %d", i, j.method);
+            SVT_AMD_BAD("%s: job %d: noise detection method %d", __func__, i, j.method);
         if (j.noise_detection_th > 1)
-            NOISE_BAD("svt_amd_noise_detect_batch_launch: job %d: noise detection threshold %d", i, j.noise_detection_th);
+            SVT_AMD_BAD("%s: job %d: noise detection threshold %d", __func__, i, j.noise_detection_th);
     }
 
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_noise) /* once per context: the descriptor table and the per-picture partial sums the block kernel accumulates into */
-        HIP_TRY(hipMalloc(&ctx->d_noise, NOISE_TABLE_BYTES + NOISE_RED_BYTES));
-    NoiseJobDev *d_tab = (NoiseJobDev *)ctx->d_noise;
-    unsigned long long *d_red = (unsigned long long *)((uint8_t *)ctx->d_noise + NOISE_TABLE_BYTES);
+    NoiseJobDev *d_tab;
+    unsigned long long *d_red; /* the per-picture partial sums the block kernel accumulates into */
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_noise, sizeof(NoiseJobDev), NOISE_RED_BYTES, (void **)&d_tab, (void **)&d_red));
     const size_t b_flat = noise_flat_bytes(w, h);
     static thread_local NoiseJobDev tab[SVT_AMD_MAX_BATCH];
-    static thread_local uint8_t seen[4096];
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    const bool track = ctx->num_slots <= (int)sizeof(seen);
-    if (track)
-        memset(seen, 0, (size_t)ctx->num_slots);
     int max_blocks = 0;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdNoiseJob &j = jobs[i];
@@ -233,21 +212,15 @@ extern "C" int svt_amd_noise_detect_batch_launch(SvtAmdContext *ctx, const SvtAm
         d.method = j.method;
         const int blocks = (d.w >> 6) * (d.h >> 6);
         max_blocks = blocks > max_blocks ? blocks : max_blocks;
-        if (!(track && seen[j.cur_slot])) { /* the planes may have been built on another lane */
-            HIP_TRY(hipStreamWaitEvent(st, c->ev_ready, 0));
-            if (track)
-                seen[j.cur_slot] = 1;
-        }
+        SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, j.cur_slot));
     }
     /* the table goes up in stream order: a batch queued behind another one on this lane does not overwrite the table the first one still reads */
-    int rc = svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(NoiseJobDev) * (size_t)num_jobs);
-    if (rc)
-        return rc;
+    SVT_AMD_TRY(svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(NoiseJobDev) * (size_t)num_jobs));
     /* the stages are ordered on the lane: a batch queued behind this one zeroes the partial sums only after this one's finish kernel has read them */
     HIP_TRY(hipMemsetAsync(d_red, 0, (size_t)num_jobs * NOISE_PARTS * 8, st));
     HIP_TRY(hipMemsetAsync(out->flat_noise, 0, (size_t)num_jobs * b_flat, st));
     if (max_blocks) /* a decimated picture below 64 samples a side: the reference's loops run zero blocks */
-        hipLaunchKernelGGL(k_noise_blocks, dim3((unsigned)((max_blocks + 3) / 4), (unsigned)num_jobs), dim3(256), 0, st, (const NoiseJobDev *)d_tab, wl);
+        hipLaunchKernelGGL(k_noise_blocks, dim3((unsigned)((max_blocks + 3) / 4), (unsigned)num_jobs), dim3(256), 0, st, (const NoiseJobDev *)d_tab, (w + 63) / 64);
     hipLaunchKernelGGL(k_noise_finish, dim3((unsigned)num_jobs), dim3(64), 0, st, (const NoiseJobDev *)d_tab, h);
     HIP_TRY(hipGetLastError());
     return SVT_AMD_OK;

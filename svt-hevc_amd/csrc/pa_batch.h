@@ -1,0 +1,23 @@
+/*
+ * pa_batch.h - the host half the batched, stream-ordered picture-analysis entries share (side_kernels.hip, where the functions live, detect_kernels.hip,
+ * noise_kernels.hip).  A launcher reads top to bottom: check (svt_amd_batch_header, svt_amd_batch_slot per job, its own checks - all before the
+ * device is touched), svt_amd_batch_begin, fill its *JobDev records and wait on the planes they point into (svt_amd_batch_wait_slot),
+ * svt_amd_upload_descriptors, zero what its kernels accumulate into (svt_amd_batch_run), launch, hipGetLastError.  `entry` is the caller's __func__.
+ */
+#ifndef SVT_AMD_PA_BATCH_H
+#define SVT_AMD_PA_BATCH_H
+#include "svt_amd_internal.h"
+
+/* refuses a call: sets the error text and returns; SVT_AMD_TRY passes on what a callee returned */
+#define SVT_AMD_BAD(...) do { svt_amd_set_error(__VA_ARGS__); return SVT_AMD_ERR_BAD_PARAM; } while (0)
+#define SVT_AMD_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
+
+static inline int svt_amd_lcu_count(int w, int h) { return ((w + 63) / 64) * ((h + 63) / 64); }
+static inline bool svt_amd_regions_ok(int regions_w, int regions_h) { return regions_w >= 1 && regions_h >= 1 && regions_w * regions_h <= 64; }
+int svt_amd_batch_header(const char *entry, const SvtAmdContext *ctx, const void *jobs, const void *out, int num_jobs);
+int svt_amd_batch_slot(const char *entry, const SvtAmdContext *ctx, int job, int slot, int *w, int *h);
+int svt_amd_batch_begin(SvtAmdContext *ctx, void **owned, size_t record_bytes, size_t scratch_bytes, void **d_tab, void **d_scratch);
+int svt_amd_batch_wait_slot(SvtAmdContext *ctx, int slot);
+bool svt_amd_batch_run(const uint8_t *want, size_t stride, int num_jobs, int *begin, int *end);
+
+#endif

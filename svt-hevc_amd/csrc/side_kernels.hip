@@ -12,7 +12,7 @@
  *   k_side_zz           ComputeDecimatedZzSad (Codec/EbMotionEstimationProcess.c:176-300) over (current, previous) 1/16 plane pairs: grid (LCUs / 4, pictures).
  * Bound: HBM - 1 B/pel for k_side_luma (the two separate kernels: 1 + 1), 1/16 B/pel for the histograms, 2/16 B/pel for the zero-motion SAD.
  */
-#include "svt_amd_internal.h"
+#include "pa_batch.h"
 #include <string.h>
 
 /* where the kernels find picture i of a batch; a null pointer = that result is not wanted for the picture (a workgroup-uniform branch) */
@@ -30,7 +30,6 @@ struct SideJobDev {
     int32_t pad[2];
 };
 static_assert(sizeof(SideJobDev) == 96, "SideJobDev layout");
-#define SIDE_TABLE_BYTES (sizeof(SideJobDev) * SVT_AMD_MAX_BATCH)
 #define SIDE_SUMS_BYTES ((size_t)SVT_AMD_MAX_BATCH * 64 * 8)
 #define SIDE_STRIPS 16
 
@@ -223,11 +222,74 @@ __global__ __launch_bounds__(256) void k_side_zz(const SideJobDev *__restrict__ 
     }
 }
 
-static bool side_regions_ok(int regions_w, int regions_h) { return regions_w >= 1 && regions_h >= 1 && regions_w * regions_h <= 64; }
+/* ---- what the four batched picture-analysis entries share on the host (pa_batch.h) ---- */
+
+int svt_amd_batch_header(const char *entry, const SvtAmdContext *ctx, const void *jobs, const void *out, int num_jobs)
+{
+    if (!ctx || !jobs || !out || num_jobs < 1 || num_jobs > SVT_AMD_MAX_BATCH)
+        SVT_AMD_BAD("%s: a context, an output table and 1..%d jobs", entry, SVT_AMD_MAX_BATCH);
+    return SVT_AMD_OK;
+}
+
+/* one job's picture slot: job 0 gives the batch its size (*w, *h), every job - job 0 included - has to hold a picture of that size */
+int svt_amd_batch_slot(const char *entry, const SvtAmdContext *ctx, int job, int slot, int *w, int *h)
+{
+    const DevPicture *c = slot >= 0 && slot < ctx->num_slots ? &ctx->slots[slot] : nullptr;
+    if (job == 0) {
+        if (!c)
+            SVT_AMD_BAD("%s: job 0: bad slot %d", entry, slot);
+        *w = c->width, *h = c->height;
+    }
+    if (!c || !c->valid)
+        SVT_AMD_BAD("%s: job %d: slot %d holds no picture", entry, job, slot);
+    if (c->width != *w || c->height != *h)
+        SVT_AMD_BAD("%s: pictures of different sizes in one batch (job %d: %dx%d, job 0: %dx%d)", entry, job, c->width, c->height, *w, *h);
+    return SVT_AMD_OK;
+}
+
+static thread_local uint8_t seen[4096]; /* the slots this call has waited on; a context of more slots waits once per use instead */
+
+/* the first device call of a launcher.  The entry's descriptor table (SVT_AMD_MAX_BATCH records) and, behind it, the scratch its kernels accumulate into are
+ * one allocation the context owns (*owned: the entry's member of the context), made at the entry's first call and freed by svt_amd_context_destroy. */
+int svt_amd_batch_begin(SvtAmdContext *ctx, void **owned, size_t record_bytes, size_t scratch_bytes, void **d_tab, void **d_scratch)
+{
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!*owned)
+        HIP_TRY(hipMalloc(owned, record_bytes * SVT_AMD_MAX_BATCH + scratch_bytes));
+    *d_tab = *owned;
+    *d_scratch = (uint8_t *)*owned + record_bytes * SVT_AMD_MAX_BATCH;
+    if (ctx->num_slots <= (int)sizeof(seen))
+        memset(seen, 0, (size_t)ctx->num_slots);
+    return SVT_AMD_OK;
+}
+
+/* the planes of a slot may have been built on another lane: the launch waits on ev_ready of every slot it reads, once per slot and call */
+int svt_amd_batch_wait_slot(SvtAmdContext *ctx, int slot)
+{
+    uint8_t untracked = 0, *s = ctx->num_slots <= (int)sizeof(seen) ? &seen[slot] : &untracked;
+    if (!*s)
+        HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), ctx->slots[slot].ev_ready, 0));
+    *s = 1;
+    return SVT_AMD_OK;
+}
+
+/* the next run [*begin, *end) of jobs whose `want` byte (`stride` bytes from one job to the next) is set, from *begin on: one memset clears an output array
+ * for a whole run.  for (int i = 0, e; svt_amd_batch_run(&jobs[0].want_x, sizeof(jobs[0]), n, &i, &e); i = e) ... */
+bool svt_amd_batch_run(const uint8_t *want, size_t stride, int num_jobs, int *begin, int *end)
+{
+    int i = *begin;
+    while (i < num_jobs && !want[(size_t)i * stride])
+        i++;
+    int e = i;
+    while (e < num_jobs && want[(size_t)e * stride])
+        e++;
+    *begin = i, *end = e;
+    return i < num_jobs;
+}
 
 extern "C" size_t svt_amd_side_stats_bytes(uint16_t luma_width, uint16_t luma_height, int which, int regions_w, int regions_h)
 {
-    const size_t lcus = (size_t)((luma_width + 63) / 64) * (size_t)((luma_height + 63) / 64);
+    const size_t lcus = (size_t)svt_amd_lcu_count(luma_width, luma_height);
     switch (which) {
     case SVT_AMD_SIDE_BLOCK_STATS:
         return lcus * sizeof(SvtAmdPaLcuStats);
@@ -236,7 +298,7 @@ extern "C" size_t svt_amd_side_stats_bytes(uint16_t luma_width, uint16_t luma_he
     case SVT_AMD_SIDE_ZZ:
         return lcus * sizeof(SvtAmdZzLcu);
     case SVT_AMD_SIDE_HISTOGRAM:
-        return side_regions_ok(regions_w, regions_h) ? (size_t)regions_w * regions_h * 256 * sizeof(uint32_t) : 0;
+        return svt_amd_regions_ok(regions_w, regions_h) ? (size_t)regions_w * regions_h * 256 * sizeof(uint32_t) : 0;
     case SVT_AMD_SIDE_REGION_AVG:
         return 64;
     case SVT_AMD_SIDE_SUM_LUMA:
@@ -245,67 +307,46 @@ extern "C" size_t svt_amd_side_stats_bytes(uint16_t luma_width, uint16_t luma_he
     return 0;
 }
 
-#define SIDE_BAD(...)                          \
-    do {                                       \
-        svt_amd_set_error(__VA_ARGS__);        \
-        return SVT_AMD_ERR_BAD_PARAM;          \
-    } while (0)
-
 extern "C" int svt_amd_side_stats_batch_launch(SvtAmdContext *ctx, const SvtAmdSideJob *jobs, int num_jobs, int regions_w, int regions_h,
                                                const SvtAmdSideArrays *out)
 {
-    if (!ctx || !jobs || !out || num_jobs < 1 || num_jobs > SVT_AMD_MAX_BATCH)
-        SIDE_BAD("svt_amd_side_stats_batch_launch: a context, an output table and 1..%d jobs", SVT_AMD_MAX_BATCH);
+    SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
-    if (jobs[0].cur_slot < 0 || jobs[0].cur_slot >= ctx->num_slots)
-        SIDE_BAD("svt_amd_side_stats_batch_launch: job 0: bad slot %d", jobs[0].cur_slot);
-    const DevPicture *c0 = &ctx->slots[jobs[0].cur_slot];
-    const int w = c0->width, h = c0->height, wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl;
+    int w = 0, h = 0;
     bool any_luma = false, any_hist = false, any_zz = false;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdSideJob &j = jobs[i];
-        if (j.cur_slot < 0 || j.cur_slot >= ctx->num_slots || !ctx->slots[j.cur_slot].valid)
-            SIDE_BAD("svt_amd_side_stats_batch_launch: job %d: slot %d holds no picture", i, j.cur_slot);
-        const DevPicture *c = &ctx->slots[j.cur_slot];
-        if (c->width != w || c->height != h)
-            SIDE_BAD("svt_amd_side_stats_batch_launch: pictures of different sizes in one batch (job %d: %dx%d, job 0: %dx%d)", i, c->width, c->height, w, h);
+        SVT_AMD_TRY(svt_amd_batch_slot(__func__, ctx, i, j.cur_slot, &w, &h));
         if (j.prev_slot >= 0) {
             if (j.prev_slot >= ctx->num_slots || !ctx->slots[j.prev_slot].valid)
-                SIDE_BAD("svt_amd_side_stats_batch_launch: job %d: previous slot %d holds no picture", i, j.prev_slot);
+                SVT_AMD_BAD("%s: job %d: previous slot %d holds no picture", __func__, i, j.prev_slot);
             if (ctx->slots[j.prev_slot].width != w || ctx->slots[j.prev_slot].height != h)
-                SIDE_BAD("svt_amd_side_stats_batch_launch: job %d: previous slot %d holds a picture of another size", i, j.prev_slot);
+                SVT_AMD_BAD("%s: job %d: previous slot %d holds a picture of another size", __func__, i, j.prev_slot);
             if (!out->zz)
-                SIDE_BAD("svt_amd_side_stats_batch_launch: job %d wants the zero-motion SAD, but there is no zz array", i);
+                SVT_AMD_BAD("%s: job %d wants the zero-motion SAD, but there is no zz array", __func__, i);
             any_zz = true;
         }
         if (j.want_block_stats && !out->block_stats)
-            SIDE_BAD("svt_amd_side_stats_batch_launch: job %d wants block statistics, but there is no block_stats array", i);
+            SVT_AMD_BAD("%s: job %d wants block statistics, but there is no block_stats array", __func__, i);
         if (j.want_ac_energy && !out->ac_energy)
-            SIDE_BAD("svt_amd_side_stats_batch_launch: job %d wants AC energies, but there is no ac_energy array", i);
+            SVT_AMD_BAD("%s: job %d wants AC energies, but there is no ac_energy array", __func__, i);
         if (j.want_histogram && !out->histogram)
-            SIDE_BAD("svt_amd_side_stats_batch_launch: job %d wants histograms, but there is no histogram array", i);
+            SVT_AMD_BAD("%s: job %d wants histograms, but there is no histogram array", __func__, i);
         any_luma |= j.want_block_stats || j.want_ac_energy;
         any_hist |= j.want_histogram != 0;
     }
-    if (any_hist && (!side_regions_ok(regions_w, regions_h) || w / 4 < regions_w || h / 4 < regions_h))
-        SIDE_BAD("svt_amd_side_stats_batch_launch: %d x %d regions of a %dx%d picture", regions_w, regions_h, w, h);
+    if (any_hist && (!svt_amd_regions_ok(regions_w, regions_h) || w / 4 < regions_w || h / 4 < regions_h))
+        SVT_AMD_BAD("%s: %d x %d regions of a %dx%d picture", __func__, regions_w, regions_h, w, h);
     if (!any_luma && !any_hist && !any_zz)
         return SVT_AMD_OK;
-    const int regions = any_hist ? regions_w * regions_h : 0;
+    const int wl = (w + 63) / 64, lcus = svt_amd_lcu_count(w, h), regions = any_hist ? regions_w * regions_h : 0;
 
-    HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_side) { /* once per context: the descriptor table and the per-region sums the histogram kernels accumulate into */
-        HIP_TRY(hipMalloc(&ctx->d_side, SIDE_TABLE_BYTES + SIDE_SUMS_BYTES));
-    }
-    SideJobDev *d_tab = (SideJobDev *)ctx->d_side;
-    unsigned long long *d_sums = (unsigned long long *)((uint8_t *)ctx->d_side + SIDE_TABLE_BYTES);
+    SideJobDev *d_tab;
+    unsigned long long *d_sums; /* the per-region sums the histogram kernels accumulate into */
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_side, sizeof(SideJobDev), SIDE_SUMS_BYTES, (void **)&d_tab, (void **)&d_sums));
     const size_t b_stats = (size_t)lcus * sizeof(SvtAmdPaLcuStats), b_hist = (size_t)regions * 256 * 4;
     static thread_local SideJobDev tab[SVT_AMD_MAX_BATCH];
-    static thread_local uint8_t seen[4096];
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    const bool track = ctx->num_slots <= (int)sizeof(seen);
-    if (track)
-        memset(seen, 0, (size_t)ctx->num_slots);
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdSideJob &j = jobs[i];
         const DevPicture *c = &ctx->slots[j.cur_slot], *p = j.prev_slot >= 0 ? &ctx->slots[j.prev_slot] : nullptr;
@@ -324,34 +365,20 @@ extern "C" int svt_amd_side_stats_batch_launch(SvtAmdContext *ctx, const SvtAmdS
             d.region_avg = out->region_average ? out->region_average + (size_t)i * 64 : nullptr;
             d.total = out->sum_luma ? (unsigned long long *)out->sum_luma + i : nullptr;
         }
-        /* the planes may have been built on another lane: the current AND the previous slot (once per slot and call) */
-        const int both[2] = {j.cur_slot, j.prev_slot};
-        for (int k = 0; k < 2; k++)
-            if (both[k] >= 0 && !(track && seen[both[k]])) {
-                HIP_TRY(hipStreamWaitEvent(st, ctx->slots[both[k]].ev_ready, 0));
-                if (track)
-                    seen[both[k]] = 1;
-            }
+        /* the planes may have been built on another lane: the current AND the previous slot */
+        SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, j.cur_slot));
+        if (p)
+            SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, j.prev_slot));
     }
     /* the table goes up in stream order (a copy kernel from a pinned ring): a batch queued behind another one on this lane does not overwrite the
      * table the first one still reads */
-    int rc = svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(SideJobDev) * (size_t)num_jobs);
-    if (rc)
-        return rc;
+    SVT_AMD_TRY(svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(SideJobDev) * (size_t)num_jobs));
     if (any_hist) { /* what the histogram kernels accumulate into: one memset per run of pictures that want them */
         HIP_TRY(hipMemsetAsync(d_sums, 0, (size_t)num_jobs * 64 * 8, st));
-        for (int i = 0; i < num_jobs;) {
-            if (!jobs[i].want_histogram) {
-                i++;
-                continue;
-            }
-            int e = i;
-            while (e < num_jobs && jobs[e].want_histogram)
-                e++;
+        for (int i = 0, e; svt_amd_batch_run(&jobs[0].want_histogram, sizeof(jobs[0]), num_jobs, &i, &e); i = e) {
             HIP_TRY(hipMemsetAsync(out->histogram + (size_t)i * regions * 256, 0, (size_t)(e - i) * b_hist, st));
             if (out->sum_luma)
                 HIP_TRY(hipMemsetAsync(out->sum_luma + i, 0, (size_t)(e - i) * 8, st));
-            i = e;
         }
     }
     if (any_luma)

@@ -6,13 +6,12 @@ import ctypes as C
 import numpy as np
 
 import svtlib as S
+from pa_batch_util import BAD_PARAM, SENTINEL, DeviceBuffer  # noqa: F401 (the two constants are used through this module)
 
 vp = C.c_void_p
 BLOCK_STATS, AC_ENERGY, ZZ_SAD, HISTOGRAM, REGION_AVG, SUM_LUMA = range(6)
 KINDS = ("block_stats", "ac_energy", "zz", "histogram", "region_average", "sum_luma")
 ZZ_DTYPE = np.dtype([("sad", "<u4"), ("zz_cost", "u1"), ("non_moving_index", "u1"), ("pad", "u1", 2)])
-BAD_PARAM = -1                     # SVT_AMD_ERR_BAD_PARAM
-SENTINEL = 0xA5                    # what the result arrays hold before a batch runs
 NOT_COMPUTED = 100000000           # the AC energy of an incomplete LCU
 
 
@@ -26,6 +25,7 @@ class SideArrays(C.Structure):
 
 
 def declare(lib):
+    lib.svt_amd_last_error.restype = C.c_char_p
     lib.svt_amd_side_stats_batch_launch.restype = C.c_int
     lib.svt_amd_side_stats_batch_launch.argtypes = [vp, C.POINTER(SideJob), C.c_int, C.c_int, C.c_int, C.POINTER(SideArrays)]
     lib.svt_amd_side_stats_bytes.restype = C.c_size_t
@@ -59,38 +59,29 @@ class DeviceArrays:
     """the six device arrays of an n-picture batch, filled with SENTINEL"""
 
     def __init__(self, lib, ctx, n, w, h, rw=4, rh=4, absent=()):
-        self.lib, self.ctx, self.n, self.w, self.h, self.rw, self.rh = lib, ctx, n, w, h, rw, rh
+        self.n, self.rw, self.rh = n, rw, rh
         self.sizes = numpy_sizes(w, h, rw, rh)
-        self.ptr = [vp() for _ in KINDS]
-        for k, b in enumerate(self.sizes):
-            if KINDS[k] in absent:
-                continue
-            assert lib.svt_amd_device_alloc(ctx, n * b, C.byref(self.ptr[k])) == 0, lib.svt_amd_last_error()
-        self.fill()
+        self.buf = [None if KINDS[k] in absent else DeviceBuffer(lib, ctx, n * b) for k, b in enumerate(self.sizes)]
+        self.ptr = [b.ptr if b else vp() for b in self.buf]
 
     def fill(self):
-        for k, b in enumerate(self.sizes):
-            if self.ptr[k]:
-                poison = np.full(self.n * b, SENTINEL, np.uint8)
-                assert self.lib.svt_amd_device_upload(self.ctx, self.ptr[k], poison.ctypes.data, poison.size) == 0, self.lib.svt_amd_last_error()
+        for b in filter(None, self.buf):
+            b.fill()
 
     def table(self):
         return SideArrays(*[p.value for p in self.ptr])
 
     def raw(self, k):
-        out = np.zeros((self.n, self.sizes[k]), np.uint8)
-        assert self.lib.svt_amd_device_download(self.ctx, out.ctypes.data, self.ptr[k], out.size) == 0, self.lib.svt_amd_last_error()
-        return out
+        return self.buf[k].get().reshape(self.n, -1)
 
     def download(self):
         """blocking copies (they wait for the context's stream): the arrays as numpy, picture first"""
-        return views([self.raw(k) if self.ptr[k] else None for k in range(6)], self.n, self.rw, self.rh)
+        return views([self.raw(k) if self.buf[k] else None for k in range(6)], self.n, self.rw, self.rh)
 
     def free(self):
-        for p in self.ptr:
-            if p:
-                self.lib.svt_amd_device_free(self.ctx, p)
-        self.ptr = [vp() for _ in KINDS]
+        for b in filter(None, self.buf):
+            b.free()
+        self.buf, self.ptr = [None] * 6, [vp() for _ in KINDS]
 
 
 def views(raw, n, rw, rh):

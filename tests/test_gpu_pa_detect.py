@@ -13,13 +13,12 @@ import pa_detect_pictures as P
 import sidelib as L
 import svtlib as S
 from gpu_util import upload
+from pa_batch_util import SENTINEL, DeviceBuffer, is_sentinel as _sentinel, make_context, ok as _ok, refused as _refused
 from test_oracle_pa import oracle_picture as pa_oracle
 from test_pa_detect_cpu import CASES, load_case
 
 pytestmark = pytest.mark.gpu
-vp = C.c_void_p
-SENTINEL = L.SENTINEL
-BAD_PARAM = L.BAD_PARAM
+CHROMA, DETECT = "svt_amd_chroma_stats_batch_launch", "svt_amd_picture_detect_batch_launch"
 KINDS4 = ("objects", "noise", "motion", "static")
 
 
@@ -28,42 +27,8 @@ def lib(product):
     return N.declare(L.declare(product))
 
 
-def _ok(lib, rc):
-    assert rc == 0, lib.svt_amd_last_error()
-
-
 def _context(lib, w, h, slots):
-    ctx = vp()
-    _ok(lib, lib.svt_amd_context_create(0, max(w, 64), max(h, 64), slots, C.byref(ctx)))
-    return ctx
-
-
-class Buf:
-    """device memory filled with SENTINEL"""
-
-    def __init__(self, lib, ctx, nbytes):
-        self.lib, self.ctx, self.n, self.ptr = lib, ctx, nbytes, vp()
-        _ok(lib, lib.svt_amd_device_alloc(ctx, nbytes, C.byref(self.ptr)))
-        self.fill()
-
-    def fill(self):
-        poison = np.full(self.n, SENTINEL, np.uint8)
-        _ok(self.lib, self.lib.svt_amd_device_upload(self.ctx, self.ptr, poison.ctypes.data, self.n))
-
-    def at(self, offset):
-        return self.ptr.value + offset
-
-    def put(self, array, offset=0):
-        """stream-ordered upload on the context's lane; the caller keeps `array` alive until the lane is synchronised"""
-        _ok(self.lib, self.lib.svt_amd_device_upload_async(self.ctx, vp(self.at(offset)), array.ctypes.data, array.nbytes))
-
-    def get(self):
-        out = np.zeros(self.n, np.uint8)
-        _ok(self.lib, self.lib.svt_amd_device_download(self.ctx, out.ctypes.data, self.ptr, self.n))    # waits for the context's stream
-        return out
-
-    def free(self):
-        self.lib.svt_amd_device_free(self.ctx, self.ptr)
+    return make_context(lib, max(w, 64), max(h, 64), slots)
 
 
 class Batch:
@@ -74,7 +39,7 @@ class Batch:
         self.lib, self.ctx, self.n, self.w, self.h, self.rw, self.rh = lib, ctx, n, w, h, rw, rh
         self.nl, self.plane = S.lcu_count(w, h), (w // 2) * (h // 2)
         self.size = dict(zip(self.NAMES, [self.nl * 256] + N.chroma_sizes(w, h, rw, rh) + N.detect_sizes(w, h) + [2 * self.plane]))
-        self.buf = {k: Buf(lib, ctx, n * b) for k, b in self.size.items()}
+        self.buf = {k: DeviceBuffer(lib, ctx, n * b) for k, b in self.size.items()}
         self.keep = []
 
     def put_chroma(self, i, cb, cr):
@@ -132,10 +97,6 @@ class Batch:
     def free(self):
         for b in self.buf.values():
             b.free()
-
-
-def _sentinel(a):
-    return bool((np.ascontiguousarray(a).view(np.uint8) == SENTINEL).all())
 
 
 def _three_calls(lib, ctx, batch, frames, edges, cls):
@@ -412,8 +373,8 @@ def test_refused_batches_name_the_job_and_queue_nothing(lib):
         batch = Batch(lib, ctx, n, w, h)
         outputs = ("means", "histogram", "region_average", "sum_chroma", "lcu", "picture")
 
-        def refused(rc, job):
-            assert rc == BAD_PARAM
+        def refused(rc, job, entry):
+            _refused(lib, rc, entry, job)
             assert ("job %d" % job).encode() in lib.svt_amd_last_error(), lib.svt_amd_last_error()
 
         everything, detect_all = [(1, 1)] * n, [(1, 0, 1)] * n
@@ -421,39 +382,41 @@ def test_refused_batches_name_the_job_and_queue_nothing(lib):
         jobs = batch.chroma_jobs(everything)
         jobs[2].cr = None
         t = batch.chroma_table()
-        refused(lib.svt_amd_chroma_stats_batch_launch(ctx, jobs, n, w, h, 4, 4, C.byref(t)), 2)
+        refused(lib.svt_amd_chroma_stats_batch_launch(ctx, jobs, n, w, h, 4, 4, C.byref(t)), 2, CHROMA)
         t = batch.chroma_table()
         t.means = None
-        refused(batch.chroma([(0, 1), (1, 1), (1, 1)], t), 1)
+        refused(batch.chroma([(0, 1), (1, 1), (1, 1)], t), 1, CHROMA)
         t = batch.chroma_table()
         t.histogram = None
-        refused(batch.chroma(everything, t), 0)
+        refused(batch.chroma(everything, t), 0, CHROMA)
         jobs = batch.detect_jobs(detect_all)
         jobs[1].stats = None
         t = batch.detect_table()
-        refused(lib.svt_amd_picture_detect_batch_launch(ctx, jobs, n, w, h, C.byref(t)), 1)
+        refused(lib.svt_amd_picture_detect_batch_launch(ctx, jobs, n, w, h, C.byref(t)), 1, DETECT)
         for missing in ("lcu", "picture"):
             t = batch.detect_table()
             setattr(t, missing, None)
-            refused(batch.detect(detect_all, t), 0)
+            refused(batch.detect(detect_all, t), 0, DETECT)
         # the 16x16 edge map wanted without chroma means
-        refused(batch.detect([(1, 0, 1), (0, 0, 0), (1, 0, 0)]), 2)
-        refused(batch.detect([(0, 0, 1), (0, 4, 1), (0, 0, 1)]), 1)              # no such resolution class
+        refused(batch.detect([(1, 0, 1), (0, 0, 0), (1, 0, 0)]), 2, DETECT)
+        refused(batch.detect([(0, 0, 1), (0, 4, 1), (0, 0, 1)]), 1, DETECT)              # no such resolution class
         # regions that do not fit: more than 64, none, regions below 8 luma samples
         for rw, rh in ((9, 8), (0, 4), (4, 0), (64, 1), (1, 31)):
             jobs = batch.chroma_jobs([(1, 0), (1, 1), (1, 1)])
             t = batch.chroma_table()
-            refused(lib.svt_amd_chroma_stats_batch_launch(ctx, jobs, n, w, h, rw, rh, C.byref(t)), 1)
+            refused(lib.svt_amd_chroma_stats_batch_launch(ctx, jobs, n, w, h, rw, rh, C.byref(t)), 1, CHROMA)
         jobs = batch.chroma_jobs(everything)
         jobs[1].pitch = w // 2 - 1
         t = batch.chroma_table()
-        refused(lib.svt_amd_chroma_stats_batch_launch(ctx, jobs, n, w, h, 4, 4, C.byref(t)), 1)
+        refused(lib.svt_amd_chroma_stats_batch_launch(ctx, jobs, n, w, h, 4, 4, C.byref(t)), 1, CHROMA)
         # 0 and 257 jobs
         big_c, big_d = (N.ChromaJob * 257)(), (N.DetectJob * 257)()
         tc, td = batch.chroma_table(), batch.detect_table()
         for count in (0, 257):
-            assert lib.svt_amd_chroma_stats_batch_launch(ctx, big_c, count, w, h, 4, 4, C.byref(tc)) == BAD_PARAM and b"jobs" in lib.svt_amd_last_error()
-            assert lib.svt_amd_picture_detect_batch_launch(ctx, big_d, count, w, h, C.byref(td)) == BAD_PARAM and b"jobs" in lib.svt_amd_last_error()
+            _refused(lib, lib.svt_amd_chroma_stats_batch_launch(ctx, big_c, count, w, h, 4, 4, C.byref(tc)), CHROMA, count)
+            assert b"jobs" in lib.svt_amd_last_error()
+            _refused(lib, lib.svt_amd_picture_detect_batch_launch(ctx, big_d, count, w, h, C.byref(td)), DETECT, count)
+            assert b"jobs" in lib.svt_amd_last_error()
         _ok(lib, lib.svt_amd_synchronize(ctx))
         assert batch.untouched(outputs), "a refused batch wrote"
         # ... and a following complete batch on the same context is right

@@ -11,12 +11,12 @@ import pa_noise_numpy as N
 import pa_noise_pictures as P
 import svtlib as S
 from gpu_util import upload
+from pa_batch_util import SENTINEL, DeviceBuffer, make_context as _context, ok as _ok, refused as _refused
 from test_pa_noise_cpu import CASES, load_case
 
 pytestmark = pytest.mark.gpu
 vp = C.c_void_p
-SENTINEL = 0xA5
-BAD_PARAM = -1
+ENTRY = "svt_amd_noise_detect_batch_launch"
 METHODS = (P.HALF, P.QUARTER, P.FULL)
 
 
@@ -25,34 +25,15 @@ def lib(product):
     return N.declare(product)
 
 
-def _ok(lib, rc):
-    assert rc == 0, lib.svt_amd_last_error()
-
-
-def _context(lib, w, h, slots):
-    ctx = vp()
-    _ok(lib, lib.svt_amd_context_create(0, w, h, slots, C.byref(ctx)))
-    return ctx
-
-
 class Arrays:
     """the two device arrays, with room for `room` pictures, filled with SENTINEL"""
 
     def __init__(self, lib, ctx, room, w, h):
-        self.lib, self.ctx, self.room = lib, ctx, room
-        self.size = N.sizes(w, h)
-        self.ptr = [vp(), vp()]
-        for p, b in zip(self.ptr, self.size):
-            _ok(lib, lib.svt_amd_device_alloc(ctx, room * b, C.byref(p)))
-        self.fill()
-
-    def fill(self):
-        for p, b in zip(self.ptr, self.size):
-            poison = np.full(self.room * b, SENTINEL, np.uint8)
-            _ok(self.lib, self.lib.svt_amd_device_upload(self.ctx, p, poison.ctypes.data, poison.size))
+        self.lib, self.ctx, self.size = lib, ctx, N.sizes(w, h)
+        self.buf = [DeviceBuffer(lib, ctx, room * b) for b in self.size]
 
     def table(self):
-        return N.NoiseArrays(self.ptr[0].value, self.ptr[1].value)
+        return N.NoiseArrays(self.buf[0].ptr.value, self.buf[1].ptr.value)
 
     def launch(self, specs, ctx=None, table=None):
         """specs: (slot, method, threshold) per picture; -> the return code"""
@@ -63,9 +44,8 @@ class Arrays:
     def download(self, n, ctx=None):
         """waits for the context's stream -> (flat [n][bytes], picture records [n]); everything beyond picture n must still be the sentinel"""
         raw = []
-        for p, b in zip(self.ptr, self.size):
-            out = np.zeros(self.room * b, np.uint8)
-            _ok(self.lib, self.lib.svt_amd_device_download(ctx or self.ctx, out.ctypes.data, p, out.size))
+        for buf, b in zip(self.buf, self.size):
+            out = buf.get(ctx)
             assert (out[n * b:] == SENTINEL).all(), "the batch wrote beyond its %d pictures" % n
             raw.append(out[:n * b])
         return raw[0].reshape(n, self.size[0]), raw[1].view(N.PIC_DTYPE).reshape(n)
@@ -76,8 +56,8 @@ class Arrays:
         return flat.size == 0 and pic.size == 0
 
     def free(self):
-        for p in self.ptr:
-            self.lib.svt_amd_device_free(self.ctx, p)
+        for buf in self.buf:
+            buf.free()
 
 
 def _assert_equals_checker(flat, pic, i, luma, method, th, what):
@@ -279,7 +259,7 @@ def test_refused_batches_name_the_job_and_queue_nothing(lib):
         upload(lib, ctx, 2, P.picture(200, 136, P.spec(802, 10)))               # slot 2: a picture of another size; slot 3: none
 
         def refused(rc, job):
-            assert rc == BAD_PARAM
+            _refused(lib, rc, ENTRY, job)
             assert ("job %d" % job).encode() in lib.svt_amd_last_error(), lib.svt_amd_last_error()
 
         good = [(0, P.FULL, 0), (1, P.HALF, 1), (0, P.QUARTER, 1)]
@@ -299,7 +279,8 @@ def test_refused_batches_name_the_job_and_queue_nothing(lib):
         big = (N.NoiseJob * 257)()
         t = arrays.table()
         for count in (0, 257):
-            assert lib.svt_amd_noise_detect_batch_launch(ctx, big, count, C.byref(t)) == BAD_PARAM and b"jobs" in lib.svt_amd_last_error()
+            _refused(lib, lib.svt_amd_noise_detect_batch_launch(ctx, big, count, C.byref(t)), ENTRY, count)
+            assert b"jobs" in lib.svt_amd_last_error()
         _ok(lib, lib.svt_amd_synchronize(ctx))
         assert arrays.untouched(), "a refused batch wrote"
         # ... and a following complete batch on the same context is right

@@ -11,6 +11,7 @@ import pytest
 import sidelib as L
 import svtlib as S
 from gpu_util import default_params, upload
+from pa_batch_util import is_sentinel as _sentinel, make_context as _context, ok as _ok, refused as _refused
 from test_oracle_pa import CASES, oracle_picture as pa_oracle
 from test_oracle_sbo import oracle_picture as sbo_oracle
 from test_oracle_zz import oracle_zz
@@ -23,16 +24,6 @@ KINDS4 = ("objects", "noise", "motion", "static")
 @pytest.fixture(scope="module")
 def lib(product):
     return L.declare(product)
-
-
-def _ok(lib, rc):
-    assert rc == 0, lib.svt_amd_last_error()
-
-
-def _context(lib, w, h, slots):
-    ctx = vp()
-    _ok(lib, lib.svt_amd_context_create(0, w, h, slots, C.byref(ctx)))
-    return ctx
 
 
 def _mixed_frames(n, w, h, seed):
@@ -156,10 +147,6 @@ def test_batch_equals_the_blocking_entries_byte_for_byte(lib, w, h, rw, rh):
 
 # ---- 5. selection and the parameter checks ---------------------------------------------------------------------------------------------------
 
-def _sentinel(a):
-    return bool((np.ascontiguousarray(a).view(np.uint8) == L.SENTINEL).all())
-
-
 def test_selection_per_picture_and_refused_batches_queue_nothing(lib):
     w, h, n = 832, 480, 6
     frames = _mixed_frames(n, w, h, 11)
@@ -198,8 +185,7 @@ def test_selection_per_picture_and_refused_batches_queue_nothing(lib):
             t = arrays.table()
             if missing:
                 setattr(t, missing, None)
-            assert L.launch(lib, ctx, L.make_jobs(spec), t, rw, rh) == L.BAD_PARAM, (spec, missing)
-            assert lib.svt_amd_last_error()
+            _refused(lib, L.launch(lib, ctx, L.make_jobs(spec), t, rw, rh), "svt_amd_side_stats_batch_launch", (spec, missing))
 
         for missing in ("block_stats", "ac_energy", "zz", "histogram"):
             refused(everything, missing)

@@ -12,10 +12,10 @@ import pytest
 import pa_detect_numpy as N
 import pa_detect_pictures as P
 import svtlib as S
+from pa_batch_util import refused
 from test_oracle_pa import oracle_picture as pa_oracle
 
 CASES = sorted(os.path.basename(p)[9:-4] for p in glob.glob(os.path.join(S.GOLDEN_DIR, "padetect_*.npz")))
-BAD_PARAM = -1
 
 
 def load_case(name):
@@ -75,14 +75,14 @@ def test_bad_parameters_are_refused_without_a_device(lib):
     cj, dj = (N.ChromaJob * 1)(), (N.DetectJob * 1)()
     ca, da = N.ChromaArrays(), N.DetectArrays()
     fake = C.create_string_buffer(4096)          # never read: the job count is checked first
-    assert lib.svt_amd_chroma_stats_batch_launch(None, cj, 1, 416, 240, 4, 4, C.byref(ca)) == BAD_PARAM
-    assert lib.svt_amd_picture_detect_batch_launch(None, dj, 1, 416, 240, C.byref(da)) == BAD_PARAM
+    refused(lib, lib.svt_amd_chroma_stats_batch_launch(None, cj, 1, 416, 240, 4, 4, C.byref(ca)), "svt_amd_chroma_stats_batch_launch")
+    refused(lib, lib.svt_amd_picture_detect_batch_launch(None, dj, 1, 416, 240, C.byref(da)), "svt_amd_picture_detect_batch_launch")
     for n in (0, -1, 257, 1 << 20):
-        assert lib.svt_amd_chroma_stats_batch_launch(fake, cj, n, 416, 240, 4, 4, C.byref(ca)) == BAD_PARAM, n
-        assert lib.svt_amd_picture_detect_batch_launch(fake, dj, n, 416, 240, C.byref(da)) == BAD_PARAM, n
+        refused(lib, lib.svt_amd_chroma_stats_batch_launch(fake, cj, n, 416, 240, 4, 4, C.byref(ca)), "svt_amd_chroma_stats_batch_launch", n)
+        refused(lib, lib.svt_amd_picture_detect_batch_launch(fake, dj, n, 416, 240, C.byref(da)), "svt_amd_picture_detect_batch_launch", n)
         assert b"1..256 jobs" in lib.svt_amd_last_error()
-    assert lib.svt_amd_chroma_stats_batch_launch(fake, None, 1, 416, 240, 4, 4, C.byref(ca)) == BAD_PARAM
-    assert lib.svt_amd_picture_detect_batch_launch(fake, dj, 1, 416, 240, None) == BAD_PARAM
+    refused(lib, lib.svt_amd_chroma_stats_batch_launch(fake, None, 1, 416, 240, 4, 4, C.byref(ca)), "svt_amd_chroma_stats_batch_launch")
+    refused(lib, lib.svt_amd_picture_detect_batch_launch(fake, dj, 1, 416, 240, None), "svt_amd_picture_detect_batch_launch")
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -13,9 +13,9 @@ import pytest
 import pa_noise_numpy as N
 import pa_noise_pictures as P
 import svtlib as S
+from pa_batch_util import refused
 
 CASES = sorted(os.path.basename(p)[8:-4] for p in glob.glob(os.path.join(S.GOLDEN_DIR, "panoise_*.npz")))
-BAD_PARAM = -1
 
 
 def load_case(name):
@@ -71,12 +71,12 @@ def test_bytes_per_picture_are_the_documented_sizes(lib, w, h, lcus):
 def test_bad_parameters_are_refused_without_a_device(lib):
     jobs, arrays = (N.NoiseJob * 1)(), N.NoiseArrays()
     fake = C.create_string_buffer(4096)          # never read: the job count is checked first
-    assert lib.svt_amd_noise_detect_batch_launch(None, jobs, 1, C.byref(arrays)) == BAD_PARAM
+    refused(lib, lib.svt_amd_noise_detect_batch_launch(None, jobs, 1, C.byref(arrays)), "svt_amd_noise_detect_batch_launch")
     for n in (0, -1, 257, 1 << 20):
-        assert lib.svt_amd_noise_detect_batch_launch(fake, jobs, n, C.byref(arrays)) == BAD_PARAM, n
+        refused(lib, lib.svt_amd_noise_detect_batch_launch(fake, jobs, n, C.byref(arrays)), "svt_amd_noise_detect_batch_launch", n)
         assert b"1..256 jobs" in lib.svt_amd_last_error()
-    assert lib.svt_amd_noise_detect_batch_launch(fake, None, 1, C.byref(arrays)) == BAD_PARAM
-    assert lib.svt_amd_noise_detect_batch_launch(fake, jobs, 1, None) == BAD_PARAM
+    refused(lib, lib.svt_amd_noise_detect_batch_launch(fake, None, 1, C.byref(arrays)), "svt_amd_noise_detect_batch_launch")
+    refused(lib, lib.svt_amd_noise_detect_batch_launch(fake, jobs, 1, None), "svt_amd_noise_detect_batch_launch")
 
 
 @pytest.mark.parametrize("name", CASES)

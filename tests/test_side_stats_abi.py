@@ -7,6 +7,7 @@ import subprocess
 import pytest
 
 import sidelib as L
+from pa_batch_util import refused
 import svtlib as S
 
 
@@ -38,12 +39,12 @@ def test_structure_layouts(tmp_path):
 def test_bad_parameters_are_refused_without_a_device(lib):
     jobs = L.make_jobs([(0, -1, 1, 1, 1)])
     table = L.SideArrays()
-    assert lib.svt_amd_side_stats_batch_launch(None, jobs, 1, 4, 4, C.byref(table)) == L.BAD_PARAM
+    refused(lib, lib.svt_amd_side_stats_batch_launch(None, jobs, 1, 4, 4, C.byref(table)), "svt_amd_side_stats_batch_launch")
     fake = C.create_string_buffer(4096)          # never read: the job count is checked first
     for n in (0, -1, 257, 1 << 20):
-        assert lib.svt_amd_side_stats_batch_launch(fake, jobs, n, 4, 4, C.byref(table)) == L.BAD_PARAM, n
-    assert lib.svt_amd_side_stats_batch_launch(fake, None, 1, 4, 4, C.byref(table)) == L.BAD_PARAM
-    assert lib.svt_amd_side_stats_batch_launch(fake, jobs, 1, 4, 4, None) == L.BAD_PARAM
+        refused(lib, lib.svt_amd_side_stats_batch_launch(fake, jobs, n, 4, 4, C.byref(table)), "svt_amd_side_stats_batch_launch", n)
+    refused(lib, lib.svt_amd_side_stats_batch_launch(fake, None, 1, 4, 4, C.byref(table)), "svt_amd_side_stats_batch_launch")
+    refused(lib, lib.svt_amd_side_stats_batch_launch(fake, jobs, 1, 4, 4, None), "svt_amd_side_stats_batch_launch")
 
 
 @pytest.mark.parametrize("w,h", [(416, 240), (1920, 1080), (3840, 2160)])
