@@ -611,6 +611,125 @@ SVT_AMD_API int svt_amd_noise_detect_batch_launch(SvtAmdContext *ctx, const SvtA
 /* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
 SVT_AMD_API size_t svt_amd_noise_detect_bytes(uint16_t luma_width, uint16_t luma_height, int which);
 
+/*
+ * Batched source-based operations: what SourceBasedOperationsKernel (Codec/EbSourceBasedOperationsProcess.c:1397) derives, per LCU and per picture, from the
+ * records of the stages before it - and the two steps in front of it that feed it (EbHevcUpdateBeaInfoOverTime, DeriveSimilarCollocatedFlag) - for up to 256
+ * pictures of ONE geometry per call, stream-ordered on the context's lane like svt_amd_picture_detect_batch_launch: the call never blocks and never copies to
+ * the host.  Pure integer logic on records that already lie in HBM; no plane is read.  A batch of one picture is the single-picture form.
+ * Job (all pointers DEVICE memory):
+ *   stats           required: SvtAmdPaLcuStats[lcus] of the picture (svt_amd_side_stats_batch_launch)
+ *   ref_stats       or NULL: the same array of the list-0 PA reference picture - the reference object's yMean[lcu] / variance[lcu] are that picture's 64x64
+ *                   values (Codec/EbPictureAnalysisProcess.c:4323-4324).  NULL: both similarity flags are 0 (I pictures)
+ *   chroma, detect, histogram   required: SvtAmdPaLcuChroma[lcus], SvtAmdPaLcuDetect[lcus] and the luma histogram [regions_w][regions_h][256] as
+ *                   svt_amd_chroma_stats / picture_detect / side_stats _batch_launch left them
+ *   zz[17], zz_count 0..17   SvtAmdZzLcu[lcus] of the picture itself (entry 0) and of the following pictures of the look-ahead window, in window order.  The window
+ *                   is MIN(2 * period + 1, framesInSw, lookAheadDistance) pictures and ends in front of an I or end-of-sequence picture
+ *                   (Codec/EbInitialRateControlProcess.c:534-553): that rule is the caller's, who passes fewer entries.  zz_count 0: no look-ahead, every
+ *                   zz_cost / non_moving_index is 0xFF (EbHevcInitZzCostInfo, :573)
+ *   me, ois         SvtAmdMeLcuResult[lcus] / SvtAmdOisLcuResult[lcus], or NULL: the records resident in picture slot cur_slot (the call waits, on the device,
+ *                   for the launches that wrote them; the slot has to hold complete records of a picture of the batch's size; a later ME / OIS launch into
+ *                   that slot from ANOTHER lane is the caller's to order behind this call, svt_amd_lane_event_record / _wait).  Read for P / B pictures and with
+ *                   want_qpm only; an I picture without want_qpm ignores me, ois and cur_slot
+ *   slice_type      0 I, 1 P, 2 B; temporal_layer_index 0..5; is_used_as_reference; resolution_class 0..3 (SequenceControlSet_t.inputResolution);
+ *                   skip_ois_8x8, cu8x8_mode (PictureParentControlSet_t.skipOis8x8 / cu8x8Mode); want_qpm: improveSharpness || bitRateReduction ||
+ *                   depthMode == PICT_LCU_SWITCH_DEPTH_MODE (:1585)
+ * The rules, restated as the reference has them (nothing is repaired); "complete" is lcuParams->isCompleteLcu, unit validity lcuParams->rasterScanCuValidity
+ * (Codec/EbSequenceControlSet.c:206, :277):
+ *   zz_cost, non_moving_index   EbHevcUpdateBeaInfoOverTime (Codec/EbInitialRateControlProcess.c:519): the sum over the zz_count records / zz_count, (EB_U8).  Every
+ *                   rule below reads these averaged values.
+ *   similar_colocated(_all_layers)   DeriveSimilarCollocatedFlag (Codec/EbMotionEstimationProcess.c:462): |mean - refMean| < 10 and (|var * 100 / MAX(refVar, 1) -
+ *                   100| < 10 or |var - refVar| < 10); similar_colocated only with is_used_as_reference.
+ *   grass, skin, high_luma, high_chroma   GrassSkinLcu (:427): bit i is 16x16 unit i (raster), valid units only.  The 8x8 children carry their unit's flags
+ *                   (:493-499), the 32x32 and 64x64 flags are the OR over their units (:501-517), so the masks carry everything.  In the reference the
+ *                   parent flags are NEVER CLEARED: cuStatArray[parent] keeps a 1 for the life of the PCS pool object.  The device gives the per-picture value;
+ *                   that stickiness lives in the caller's object (parent |= OR of the masks).  grass_percentage: GrassSkinPicture (:527).
+ *   cmplx_contrast  SpatialHighContrastClassifier (:768), TemporalHighContrastClassifier (:741), PopulateFromCurrentLcuToNeighborLcus (:804).
+ *                   lcuCmplxContrastArray is ORDER-DEPENDENT like isolated_high_intensity above: every LCU clears its own flag when the raster loop reaches it
+ *                   (:1439) and a triggering LCU never marks itself, so the flag of n is 1 exactly when a triggering complete LCU m > n is one of n's eight
+ *                   neighbours and the populate condition of that direction (:815-851) holds.
+ *   dark_background_light_foreground, intra_coded_block_probability   LumaContrastDetectorLcu (:364) / Picture (:409): incomplete LCUs count in the moving /
+ *                   non-moving means.
+ *   failing_motion, uncovered_area   FailingMotionLcu (:169), DetectUncoveredLcu (:228): the (EB_S32) casts and the division (:211-212, :278-279) as written; the
+ *                   OIS distortion is bits 0-19 of candidate[k][0].
+ *   high_dark_area_density, high_dark_low_light_area_density, black_area_percentage   DeriveHighDarkAreaDensityFlag (:684): 32-bit sums and products as written.
+ *   isolated_non_homogeneous   DetermineIsolatedNonHomogeneousRegionInPicture (:536): only the four diagonal neighbours are counted homogeneous (lcuVer != 0 &&
+ *                   lcuHor != 0, :584); the flat-neighbour test is > 1 (:569).
+ *   percentage_of_edge_in_light_background   DetermineMorePotentialAuraAreas (:639) with isEdgeLcu as Codec/EbSequenceControlSet.c:210 derives it.  A neighbour index
+ *                   outside the picture's LCU array (the reference reads past it when a last-column LCU carries edge_block_num, which the detectors never set
+ *                   there) counts as 0.
+ *   complete_lcu_count, non_moving_index_average, zz_cost_average, low_motion_content   DerivePictureActivityStatistics (:81).  With no complete LCU the reference
+ *                   leaves stale averages; the device writes 0 with complete_lcu_count 0.
+ *   complex_lcu     DeriveBlockinessPresentFlag (:958) with IsSpatiallyComplexArea (:860), after the averages above: 0 / 1 / 2.  The neighbour tests compare signed:
+ *                   in a picture below 64 samples a side the reference's unsigned forms (:922-939) read outside its arrays.
+ *   cmplx_status    ComplexityClassifier32x32 (:120): 0 (CMPLX_LOW) / 4 (CMPLX_NOISE).
+ *   intra_/inter_complexity_*, processed_leaf_count   with want_qpm: QpmGatherStatistics (:999) and the picture part (:1585-1660): the 8x8 units use their own OIS
+ *                   distortion under cu8x8_mode 0 when its validDistortion bit (20) is set and fall back to the parent 16x16 (0 when that is not valid
+ *                   either); depth 3 stays at its start values (min 0xFFFFFFFF, everything else 0) under skip_ois_8x8 (totDepths 3).  All zero without want_qpm.
+ * Left to the host: CalculateAcEnergy (:302) exists as svt_amd_side_stats_batch_launch's ac_energy; SetDefaultDeltaQpRange (:609) is three table reads;
+ * StationaryEdgeOverUpdateOverTimeLcu (:1142) walks the control sets of the look-ahead window.
+ * Two stages in stream order: per LCU (a wave per LCU: a lane per 16x16 unit, a lane per 8x8 / 16x16 / 32x32 / 64x64 unit for the QPM statistics, lane shuffles),
+ * the LCU's record and its partial sums stored - not added - into context-owned scratch; then a workgroup per picture that reduces the partials in LDS and runs
+ * the passes that need the reduced values or the 3x3 neighbourhood.  The arrays are DEVICE memory, both required, picture i of the batch at i times
+ * svt_amd_source_ops_bytes(...) bytes of each.  Everything is checked before anything is queued: a NULL required pointer, zz_count above 17 (or a NULL entry below
+ * it), a layer above 5, a slice type above 2, a class above 3, a P / B picture or want_qpm whose ME / OIS records are neither given nor complete in a slot of the
+ * batch's size, bad regions, a picture of more than 16384 LCUs or of more LCUs than the context was made for return SVT_AMD_ERR_BAD_PARAM
+ * (svt_amd_last_error names the job) and queue nothing.
+ */
+typedef struct SvtAmdSboJob {
+    const SvtAmdPaLcuStats   *stats;        /* required */
+    const SvtAmdPaLcuStats   *ref_stats;    /* or NULL  */
+    const SvtAmdPaLcuChroma  *chroma;       /* required */
+    const SvtAmdPaLcuDetect  *detect;       /* required */
+    const uint32_t           *histogram;    /* required: luma [regions_w][regions_h][256] */
+    const SvtAmdZzLcu        *zz[17];       /* [0] the picture itself, then the window; entries from zz_count on are not read */
+    const SvtAmdMeLcuResult  *me;           /* or NULL: cur_slot's */
+    const SvtAmdOisLcuResult *ois;          /* or NULL: cur_slot's */
+    int32_t cur_slot;
+    uint8_t zz_count, slice_type, temporal_layer_index, is_used_as_reference;
+    uint8_t resolution_class, skip_ois_8x8, cu8x8_mode, want_qpm;
+    uint8_t pad[4];
+} SvtAmdSboJob;                             /* 208 bytes */
+typedef struct SvtAmdSboLcu {
+    uint16_t grass, skin, high_luma, high_chroma; /* bit i: cuStatArray[RASTER_SCAN_TO_MD_SCAN[5 + i]].grassArea / skinArea / highLuma / highChroma (:480-491) */
+    uint8_t  zz_cost, non_moving_index;     /* zzCostArray / nonMovingIndexArray after EbHevcUpdateBeaInfoOverTime                          */
+    uint8_t  similar_colocated;             /* similarColocatedLcuArray                                                                     */
+    uint8_t  similar_colocated_all_layers;  /* similarColocatedLcuArrayAllLayers                                                            */
+    uint8_t  failing_motion;                /* failingMotionLcuFlag (:220, :1484)                                                           */
+    uint8_t  uncovered_area;                /* uncoveredAreaLcuFlag (:292, :1494)                                                           */
+    uint8_t  cmplx_contrast;                /* lcuCmplxContrastArray after the whole raster loop (:1439, :1514)                             */
+    uint8_t  isolated_non_homogeneous;      /* lcuIsolatedNonHomogeneousAreaArray (:551, :597)                                              */
+    uint8_t  cmplx_status;                  /* cmplxStatusLcu: 0 / 4 (:135, :160)                                                           */
+    uint8_t  complex_lcu;                   /* complexLcuArray: 0 / 1 / 2 (:967-993)                                                        */
+    uint8_t  pad[6];                        /* 0 */
+} SvtAmdSboLcu;                             /* 24 bytes */
+typedef struct SvtAmdSboPic {
+    uint32_t complete_lcu_count;            /* completeLcuCount (:91)                     */
+    uint32_t zz_cost_average;               /* zzCostAverage (:110)                       */
+    uint16_t non_moving_index_average;      /* nonMovingIndexAverage (:109)               */
+    uint8_t  low_motion_content;            /* lowMotionContentFlag (:112)                */
+    uint8_t  dark_background_light_foreground; /* darkBackGroundlightForeGround (:416)    */
+    uint8_t  intra_coded_block_probability; /* intraCodedBlockProbability (:420-423)      */
+    uint8_t  grass_percentage;              /* grassPercentageInPicture (:530)            */
+    uint8_t  percentage_of_edge_in_light_background; /* percentageOfEdgeinLightBackground (:677) */
+    uint8_t  high_dark_area_density;        /* highDarkAreaDensityFlag (:704)             */
+    uint8_t  high_dark_low_light_area_density; /* highDarkLowLightAreaDensityFlag (:726)  */
+    uint8_t  black_area_percentage;         /* blackAreaPercentage (:724)                 */
+    uint8_t  pad[6];                        /* 0 */
+    uint32_t intra_complexity_min[4], intra_complexity_max[4], intra_complexity_accum[4], intra_complexity_avg[4]; /* by cuDepth (Codec/EbPictureControlSet.h:566-569) */
+    uint32_t inter_complexity_min[4], inter_complexity_max[4], inter_complexity_accum[4], inter_complexity_avg[4]; /* (:570-573) */
+    uint32_t processed_leaf_count[4];       /* processedleafCount (:574) */
+} SvtAmdSboPic;                             /* 168 bytes */
+typedef struct SvtAmdSboArrays {            /* DEVICE pointers, picture i of the batch at index i; both required */
+    SvtAmdSboLcu *lcu;                      /* [n][lcus] */
+    SvtAmdSboPic *picture;                  /* [n]       */
+} SvtAmdSboArrays;
+SVT_AMD_API int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmdSboJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
+                                                int regions_w, int regions_h, const SvtAmdSboArrays *out);
+#define SVT_AMD_SBO_LCU     0
+#define SVT_AMD_SBO_PICTURE 1
+/* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_source_ops_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+
 
 /* Device-side timing of the launches issued between begin/end on the context's
  * own stream (HIP events); used for roofline.achieved in bench.py. */

@@ -123,6 +123,8 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
         (void)hipFree(ctx->d_detect);
     if (ctx->d_noise)
         (void)hipFree(ctx->d_noise);
+    if (ctx->d_sbo)
+        (void)hipFree(ctx->d_sbo);
     if (ctx->d_dbg)
         (void)hipFree(ctx->d_dbg);
     for (int i = 0; i < ctx->cap_stamps; i++) {
