@@ -279,7 +279,8 @@ SVT_AMD_API int svt_amd_zz_sad_picture(SvtAmdContext *ctx, int cur_slot, int pre
  * queued on ONE stream ("lane") and overlapped with the other lanes' copies and kernels.  A lane is a context forked from
  * the one that owns the picture slots (svt_amd_context_fork): all lanes see the same slots, each has its own stream,
  * descriptors, timers and pinned result buffers.  The owning context is itself a lane.  Calls on one lane are serialised by
- * the caller; different lanes may be driven from different threads.
+ * the caller; different lanes may be driven from different threads.  Destroy every lane before the owner: a lane's destructor waits for
+ * the lane's work and then visits the owner's slots (it takes back the completion markers its ME / OIS launches lent them).
  * A context - the owner or a lane - takes its stream at its first stream-ordered call (a launch, an asynchronous copy or upload, a
  * lane event, a timer), not when it is made: an owner that only allocates (svt_amd_device_alloc, svt_amd_host_alloc), copies blocking
  * (svt_amd_device_upload / _download / _copy) and forks holds none, and svt_amd_synchronize of it returns at once.  Streams beyond the
@@ -2045,6 +2046,9 @@ SVT_AMD_API int svt_amd_debug_me_kernel_lds_bytes(const SvtAmdMeParams *params, 
 /* measurement: what the context's device makes of that kernel at 256 threads and that job's pool: resident workgroups per CU
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor) and the kernel's private segment in bytes per lane (localSizeBytes of hipFuncGetAttributes: 0 = no scratch frame) */
 SVT_AMD_API int svt_amd_debug_me_kernel_occupancy(SvtAmdContext *ctx, const SvtAmdMeParams *params, int phase, int *workgroups_per_cu, int *private_bytes);
+/* measurement: the completion markers this context (lane) has recorded behind its ME / OIS launches since it was made - one per launch, however many pictures the
+ * launch holds - and the waits on other lanes' markers it has issued as a consumer of records left in the slots (me == NULL / ois == NULL) */
+SVT_AMD_API int svt_amd_debug_launch_markers(SvtAmdContext *ctx, unsigned long long *records, unsigned long long *waits);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,13 @@ static void plane_destroy(DevPlane *p)
     memset(p, 0, sizeof(*p));
 }
 
+static inline void slot_mark_lock(DevPicture *s)
+{
+    while (__atomic_exchange_n(&s->mark_lock, 1, __ATOMIC_ACQUIRE))
+        ;
+}
+static inline void slot_mark_unlock(DevPicture *s) { __atomic_store_n(&s->mark_lock, 0, __ATOMIC_RELEASE); }
+
 extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
 {
     if (!ctx)
@@ -56,6 +63,20 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
     (void)hipSetDevice(ctx->device);
     (void)svt_amd_ctx_sync(ctx);
     (void)svt_amd_comm_destroy(ctx);
+    /* the slots outlive a lane: whatever this context's launches wrote is finished (the synchronisation above), so a slot that still refers to one of its
+     * markers has nothing to wait for - and must not keep an event that is destroyed below */
+    for (int i = 0; ctx->slots && i < ctx->num_slots; i++) {
+        DevPicture *s = &ctx->slots[i];
+        slot_mark_lock(s);
+        if (s->ev_me.lane == ctx)
+            s->ev_me = LaunchMark{nullptr, nullptr};
+        if (s->ev_ois.lane == ctx)
+            s->ev_ois = LaunchMark{nullptr, nullptr};
+        slot_mark_unlock(s);
+    }
+    for (int i = 0; i < 16; i++)
+        if (ctx->ev_launch[i])
+            (void)hipEventDestroy(ctx->ev_launch[i]);
     for (int i = 0; !ctx->parent && ctx->slots && i < ctx->num_slots; i++) {
         DevPicture *s = &ctx->slots[i];
         plane_destroy(&s->full);
@@ -78,10 +99,6 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
             (void)hipHostFree(s->h_staging);
         if (s->ev_ready)
             (void)hipEventDestroy(s->ev_ready);
-        if (s->ev_me)
-            (void)hipEventDestroy(s->ev_me);
-        if (s->ev_ois)
-            (void)hipEventDestroy(s->ev_ois);
         if (s->ev_md_read)
             (void)hipEventDestroy(s->ev_md_read);
     }
@@ -147,6 +164,8 @@ static int context_common_create(SvtAmdContext *ctx)
     HIP_TRY(hipEventCreate(&ctx->ev_begin));
     HIP_TRY(hipEventCreate(&ctx->ev_end));
     HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming | hipEventBlockingSync)); /* waited on for milliseconds by several host threads: they sleep */
+    for (int i = 0; i < 16; i++)
+        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_launch[i], hipEventDisableTiming));
     const int nlcu = ((ctx->max_w + 63) / 64) * ((ctx->max_h + 63) / 64);
     if (hipMalloc((void **)&ctx->d_me_scratch, (size_t)nlcu * sizeof(SvtAmdMeLcuResult)) != hipSuccess ||
         hipMalloc(&ctx->d_prep_jobs, 128 * SVT_AMD_MAX_BATCH) != hipSuccess ||
@@ -317,8 +336,7 @@ extern "C" int svt_amd_context_create(int device_ordinal, uint16_t max_luma_widt
             break;
         }
         s->staging_bytes = (size_t)w * h;
-        if (hipEventCreateWithFlags(&s->ev_ready, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s->ev_me, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&s->ev_ois, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s->ev_md_read, hipEventDisableTiming) != hipSuccess) {
+        if (hipEventCreateWithFlags(&s->ev_ready, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s->ev_md_read, hipEventDisableTiming) != hipSuccess) {
             svt_amd_set_error("hipEventCreate (slot %d) failed", i);
             rc = SVT_AMD_ERR_DEVICE;
             break;
@@ -730,6 +748,51 @@ static void slot_records_reset(DevPicture *s)
     memset(s->me_cov, 0, sizeof(s->me_cov));
     s->me_cov_count = 0;
     __atomic_store_n(&s->me_cov_lock, 0, __ATOMIC_RELEASE);
+    slot_mark_lock(s); /* no consumer is let at those records (me_lcus / ois_lcus are 0), so there is no launch to order one behind */
+    s->ev_me = s->ev_ois = LaunchMark{nullptr, nullptr};
+    slot_mark_unlock(s);
+}
+/* The completion marker of a launch: the next entry of the lane's ring, recorded ONCE at the current end of the lane's stream - behind the kernels of the
+ * launch - and lent to every slot whose records those kernels write (the invariant that makes a stale reference harmless: SvtAmdContext::ev_launch). */
+static int svt_amd_launch_mark_record(SvtAmdContext *ctx, LaunchMark *mark)
+{
+    hipEvent_t ev = ctx->ev_launch[ctx->launch_next];
+    HIP_TRY(hipEventRecord(ev, svt_amd_ctx_stream(ctx)));
+    ctx->launch_next = (ctx->launch_next + 1) & 15;
+    ctx->mark_records++;
+    *mark = LaunchMark{ev, ctx};
+    return SVT_AMD_OK;
+}
+static void slot_mark_set(DevPicture *s, int which, const LaunchMark &mark)
+{
+    slot_mark_lock(s);
+    (which ? s->ev_ois : s->ev_me) = mark;
+    slot_mark_unlock(s);
+}
+int svt_amd_records_wait(SvtAmdContext *ctx, DevPicture *s, int which, hipEvent_t *seen, int *nseen, int cap)
+{
+    /* the wait is issued under the slot's lock: the producing lane cannot clear the reference and destroy its ring (svt_amd_context_destroy) in between */
+    slot_mark_lock(s);
+    const LaunchMark m = which ? s->ev_ois : s->ev_me;
+    bool wait = m.ev && m.lane != ctx;
+    for (int i = 0; wait && seen && i < *nseen; i++)
+        wait = seen[i] != m.ev;
+    const hipError_t e = wait ? hipStreamWaitEvent(svt_amd_ctx_stream(ctx), m.ev, 0) : hipSuccess;
+    slot_mark_unlock(s);
+    HIP_TRY(e);
+    if (wait) {
+        ctx->mark_waits++;
+        if (seen && *nseen < cap)
+            seen[(*nseen)++] = m.ev;
+    }
+    return SVT_AMD_OK;
+}
+extern "C" int svt_amd_debug_launch_markers(SvtAmdContext *ctx, unsigned long long *records, unsigned long long *waits)
+{
+    if (!ctx || !records || !waits)
+        return SVT_AMD_ERR_BAD_PARAM;
+    *records = ctx->mark_records, *waits = ctx->mark_waits;
+    return SVT_AMD_OK;
 }
 /* Before a kernel of this lane writes the slot's record buffers: a mode-decision kernel of another lane may still be reading the previous picture's records in place
  * (svt_amd_md_encode_picture_inter with me == NULL / ois == NULL records ev_md_read behind its launch). */
@@ -742,7 +805,7 @@ static int slot_records_before_write(SvtAmdContext *ctx, DevPicture *s)
     return SVT_AMD_OK;
 }
 /* [lcu_begin, lcu_end): the LCUs the launch wrote.  The slot counts as holding the picture's records only when the launches since the last upload cover all of it. */
-static int me_records_written(SvtAmdContext *ctx, int slot, const SvtAmdMeParams *p, uint32_t lcu_begin, uint32_t lcu_end)
+static int me_records_written(SvtAmdContext *ctx, int slot, const SvtAmdMeParams *p, uint32_t lcu_begin, uint32_t lcu_end, const LaunchMark &mark)
 {
     DevPicture *s = &ctx->slots[slot];
     const uint32_t n = ((p->luma_width + 63u) / 64u) * ((p->luma_height + 63u) / 64u);
@@ -754,14 +817,14 @@ static int me_records_written(SvtAmdContext *ctx, int slot, const SvtAmdMeParams
             s->me_cov[i >> 6] |= 1ull << (i & 63), s->me_cov_count++;
     covered = s->me_cov_count;
     __atomic_store_n(&s->me_cov_lock, 0, __ATOMIC_RELEASE);
-    HIP_TRY(hipEventRecord(s->ev_me, svt_amd_ctx_stream(ctx)));
+    slot_mark_set(s, 0, mark);
     __atomic_store_n(&s->me_lcus, covered >= n ? n : 0u, __ATOMIC_RELEASE);
     return SVT_AMD_OK;
 }
-static int ois_records_written(SvtAmdContext *ctx, int slot, const SvtAmdOisParams *p)
+static int ois_records_written(SvtAmdContext *ctx, int slot, const SvtAmdOisParams *p, const LaunchMark &mark)
 {
     DevPicture *s = &ctx->slots[slot];
-    HIP_TRY(hipEventRecord(s->ev_ois, svt_amd_ctx_stream(ctx)));
+    slot_mark_set(s, 1, mark);
     __atomic_store_n(&s->ois_lcus, ((p->luma_width + 63u) / 64u) * ((p->luma_height + 63u) / 64u), __ATOMIC_RELEASE);
     return SVT_AMD_OK;
 }
@@ -803,8 +866,9 @@ extern "C" int svt_amd_me_picture_range_launch(SvtAmdContext *ctx, const SvtAmdM
     if ((rc = slot_records_before_write(ctx, &ctx->slots[cur_slot])) != 0)
         return rc;
     rc = svt_amd_launch_me_batch(ctx, &job, 1, job.lcu_count);
-    if (rc == SVT_AMD_OK)
-        rc = me_records_written(ctx, cur_slot, params, lcu_begin, lcu_end);
+    LaunchMark mark;
+    if (rc == SVT_AMD_OK && (rc = svt_amd_launch_mark_record(ctx, &mark)) == SVT_AMD_OK)
+        rc = me_records_written(ctx, cur_slot, params, lcu_begin, lcu_end, mark);
     return rc;
 }
 
@@ -834,8 +898,11 @@ extern "C" int svt_amd_me_batch_launch(SvtAmdContext *ctx, const SvtAmdMeJob *jo
             rc = slot_records_before_write(ctx, &ctx->slots[jobs[i].cur_slot]);
         if (rc == SVT_AMD_OK)
             rc = e == hipSuccess ? svt_amd_launch_me_batch(ctx, dj, num_jobs, max_lcus) : SVT_AMD_ERR_DEVICE;
+        LaunchMark mark; /* every slot of the batch is written by the same kernels: one marker behind them serves all */
+        if (rc == SVT_AMD_OK)
+            rc = svt_amd_launch_mark_record(ctx, &mark);
         for (int i = 0; i < num_jobs && rc == SVT_AMD_OK; i++)
-            rc = me_records_written(ctx, jobs[i].cur_slot, &jobs[i].params, 0, (uint32_t)dj[i].lcu_count);
+            rc = me_records_written(ctx, jobs[i].cur_slot, &jobs[i].params, 0, (uint32_t)dj[i].lcu_count, mark);
     }
     free(dj);
     return rc;
@@ -1143,8 +1210,9 @@ static int ois_launch(SvtAmdContext *ctx, const SvtAmdOisParams *params, int cur
         return rc;
     rc = svt_amd_launch_ois_batch(ctx, &j, 1, j.nlcu);
     const int rc2 = svt_amd_stamp_end(ctx);
-    if (!rc && !rc2)
-        return ois_records_written(ctx, cur_slot, params);
+    LaunchMark mark;
+    if (!rc && !rc2 && !(rc = svt_amd_launch_mark_record(ctx, &mark)))
+        return ois_records_written(ctx, cur_slot, params, mark);
     return rc ? rc : rc2;
 }
 
@@ -1169,8 +1237,11 @@ extern "C" int svt_amd_ois_batch_launch(SvtAmdContext *ctx, const SvtAmdOisJob *
         return rc;
     rc = svt_amd_launch_ois_batch(ctx, host, num_jobs, max_lcus);
     const int rc2 = svt_amd_stamp_end(ctx);
+    LaunchMark mark; /* one marker behind the launch for all of its slots, as in svt_amd_me_batch_launch */
+    if (!rc && !rc2)
+        rc = svt_amd_launch_mark_record(ctx, &mark);
     for (int i = 0; i < num_jobs && !rc && !rc2; i++)
-        rc = ois_records_written(ctx, jobs[i].cur_slot, &jobs[i].params);
+        rc = ois_records_written(ctx, jobs[i].cur_slot, &jobs[i].params, mark);
     return rc ? rc : rc2;
 }
 

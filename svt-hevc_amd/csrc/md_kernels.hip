@@ -3187,7 +3187,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
             return SVT_AMD_ERR_BAD_PARAM;
         }
     }
-    hipEvent_t ev_wait[2] = {nullptr, nullptr}; /* records read where another lane's kernels leave them: this lane's stream orders itself behind those kernels */
+    DevPicture *rec_slot[2] = {nullptr, nullptr}; /* records read where another lane's kernels leave them: this lane's stream orders itself behind those kernels */
     const SvtAmdMeLcuResult *d_me_slot = nullptr;
     if (X && !me) {
         SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
@@ -3197,7 +3197,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
             return SVT_AMD_ERR_BAD_PARAM;
         }
         d_me_slot = root->slots[me_slot].d_me_out;
-        ev_wait[0] = root->slots[me_slot].ev_me;
+        rec_slot[0] = &root->slots[me_slot];
     }
     const SvtAmdOisLcuResult *d_ois_slot = nullptr;
     if (!ois) {
@@ -3208,7 +3208,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
             return SVT_AMD_ERR_BAD_PARAM;
         }
         d_ois_slot = root->slots[ois_slot].d_ois_out;
-        ev_wait[1] = root->slots[ois_slot].ev_ois;
+        rec_slot[1] = &root->slots[ois_slot];
     }
     if (pic->md_rect_n) { /* a rank's rectangle (svt_amd_encdec_picture_set_rect): its borders must be tile borders - an LCU never waits for one outside */
         const SvtAmdRect &r = pic->md_rect;
@@ -3231,9 +3231,9 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     if ((rc = md_state(pic, &m)) != 0)
         return rc;
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    for (hipEvent_t ev : ev_wait)
-        if (ev)
-            HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+    for (int k = 0; k < 2; k++)
+        if (rec_slot[k] && (rc = svt_amd_records_wait(ctx, rec_slot[k], k, nullptr, nullptr, 0)) != 0)
+            return rc;
     /* debug (SVT_AMD_MD_TIMING): host clock around the call's three parts, with a stream synchronisation after each - one line per call on stderr */
     static const bool timing = getenv("SVT_AMD_MD_TIMING") != nullptr;
     const auto t_call = std::chrono::steady_clock::now();

@@ -451,6 +451,8 @@ extern "C" int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmdS
     SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_sbo, sizeof(SboJobDev), pic_scratch * SVT_AMD_MAX_BATCH, (void **)&d_tab, (void **)&d_scratch));
     static thread_local SboJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
+    hipEvent_t waited[32]; /* the producing launches this call has ordered itself behind: one wait each, however many slots they wrote */
+    int nwaited = 0;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdSboJob &j = jobs[i];
         SboJobDev &d = tab[i];
@@ -464,11 +466,11 @@ extern "C" int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmdS
                 DevPicture *c = &ctx->slots[j.cur_slot];
                 SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, j.cur_slot));
                 if (!j.me) {
-                    HIP_TRY(hipStreamWaitEvent(st, c->ev_me, 0));
+                    SVT_AMD_TRY(svt_amd_records_wait(ctx, c, 0, waited, &nwaited, 32));
                     d.me = c->d_me_out;
                 }
                 if (!j.ois) {
-                    HIP_TRY(hipStreamWaitEvent(st, c->ev_ois, 0));
+                    SVT_AMD_TRY(svt_amd_records_wait(ctx, c, 1, waited, &nwaited, 32));
                     d.ois = c->d_ois_out;
                 }
             }

@@ -1,0 +1,278 @@
+"""-m gpu: the completion markers of the ME / OIS launches (svt-hevc_amd/csrc/svt_amd_internal.h: SvtAmdContext::ev_launch, DevPicture::ev_me / ev_ois).  A launch
+records ONE marker behind its kernels, whatever the number of pictures, and lends it to every slot it wrote; a consumer that reads the records where they lie
+(svt_amd_source_ops_batch_launch with me = ois = NULL) waits once per distinct producing launch of another lane and not at all for its own lane.  The counters of
+svt_amd_debug_launch_markers are the deterministic part; the byte comparisons against the same chain on one lane with a synchronisation after every call are
+detectors of chance for a missing wait (the producing lane is kept busy by a 16-picture 640x384 ME batch in front, the slots hold other pictures' records
+before).  Pictures are one and two LCUs; the controls are those of the recorded 1080p pictures (tests/golden/me_p_1920x1080_m9.npz, ois_ip_1920x1080_m9.npz)."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import sbo_records as R
+import svtlib as S
+from golden_util import load_case
+from gpu_util import upload
+from pa_batch_util import BAD_PARAM, DeviceBuffer, ok
+from test_gpu_source_ops import Pictures, Results, launch
+
+pytestmark = pytest.mark.gpu
+
+vp, ull = C.c_void_p, C.c_ulonglong
+N = 5                                  # pictures of a small batch: slots 0 .. 4, picture i searched in the picture of slot i + 1 (slot 5: a reference only)
+BUSY, BUSY_W, BUSY_H = 16, 640, 384    # the batch that keeps the producing lane busy: slots 8 .. 23, references 9 .. 24
+SLOTS = 8 + BUSY + 1
+SIZES = [(64, 64), (128, 64)]
+JOB = R.job(R.P, 0, 1, 1, qpm=1)       # a P picture with the QPM sums: every LCU's ME and OIS records are read
+
+
+@pytest.fixture(scope="module")
+def lib(product):
+    R.declare(product)
+    product.svt_amd_debug_launch_markers.restype = C.c_int
+    product.svt_amd_debug_launch_markers.argtypes = [vp, C.POINTER(ull), C.POINTER(ull)]
+    return product
+
+
+def markers(lib, ctx):
+    """(completion records, waits on other lanes' records) the context has issued since it was made"""
+    r, w = ull(), ull()
+    ok(lib, lib.svt_amd_debug_launch_markers(ctx, C.byref(r), C.byref(w)))
+    return r.value, w.value
+
+
+def controls(w, h):
+    p = S.params_from_record(load_case("p_1920x1080_m9")["params"][0])
+    op = S.ois_params_from_record(np.load(os.path.join(S.GOLDEN_DIR, "ois_ip_1920x1080_m9.npz"))["params"][1])
+    assert p.num_lists == 1 and not op.slice_is_intra
+    p.luma_width, p.luma_height, op.luma_width, op.luma_height = w, h, w, h
+    return p, op
+
+
+def me_jobs(p, slots):
+    jobs = (S.MeJob * len(slots))()
+    for k, s in enumerate(slots):
+        jobs[k].params, jobs[k].cur_slot = p, s
+        jobs[k].ref_slot[0] = jobs[k].ref_slot[1] = s + 1
+    return jobs
+
+
+def ois_jobs(op, slots):
+    jobs = (S.OisJob * len(slots))()
+    for k, s in enumerate(slots):
+        jobs[k].params, jobs[k].cur_slot = op, s
+    return jobs
+
+
+class World:
+    """one root with two lanes; the busy batch's pictures uploaded once; per picture size the seeded side records of the N jobs on the device and the bytes the
+    chain gives on the root alone with a synchronisation after every call (computed once, never written again)"""
+
+    def __init__(self, lib):
+        self.lib, self.root, self.a, self.b = lib, vp(), vp(), vp()
+        ok(lib, lib.svt_amd_context_create(0, BUSY_W, BUSY_H, SLOTS, C.byref(self.root)))
+        ok(lib, lib.svt_amd_context_fork(self.root, C.byref(self.a)))
+        ok(lib, lib.svt_amd_context_fork(self.root, C.byref(self.b)))
+        for t in range(BUSY + 1):
+            upload(lib, self.root, 8 + t, S.gen_luma("motion", BUSY_W, BUSY_H, t, 11))
+        self.busy_p = controls(BUSY_W, BUSY_H)[0]
+        self.pics, self.want, self.frames, self.outs = {}, {}, {}, []
+        ok(lib, lib.svt_amd_synchronize(self.root))
+
+    def side(self, w, h):
+        if (w, h) not in self.pics:
+            recs = [R.make_inputs(w, h, 1, 1, 43, i, JOB) for i in range(N)]
+            self.pics[w, h] = Pictures(self.lib, self.root, w, h, 1, 1, recs, [JOB] * N)
+            ok(self.lib, self.lib.svt_amd_synchronize(self.root))
+            self.frames[w, h] = [S.gen_luma("noise" if t & 1 else "motion", w, h, t, 7) for t in range(N + 1)]
+        return self.pics[w, h]
+
+    def fill(self, ctx, w, h, stale):
+        """pictures into slots 0 .. N through `ctx`; stale: other pictures, and their ME / OIS records left in the slots"""
+        self.side(w, h)
+        for s in range(N + 1):
+            upload(self.lib, ctx, s, S.gen_luma("motion", w, h, s, 99) if stale else self.frames[w, h][s])
+        if stale:
+            p, op = controls(w, h)
+            ok(self.lib, self.lib.svt_amd_me_batch_launch(ctx, me_jobs(p, range(N)), N))
+            ok(self.lib, self.lib.svt_amd_ois_batch_launch(ctx, ois_jobs(op, range(N)), N))
+        ok(self.lib, self.lib.svt_amd_synchronize(ctx))
+
+    def consume(self, ctx, w, h, slots, me_from_slot=True, ois_from_slot=True, expect=0):
+        """source-based operations of the pictures in `slots` on `ctx`, records read in the slots -> (return code, the two result arrays' bytes)"""
+        pics = self.side(w, h)
+        jobs = (R.SboJob * len(slots))()
+        for k, s in enumerate(slots):
+            jobs[k] = pics.job(s, (s, me_from_slot, ois_from_slot))
+        out = Results(self.lib, self.root, len(slots), w, h)
+        self.outs.append(out)
+        t = out.table()
+        rc = launch(self.lib, ctx, jobs, len(slots), w, h, 1, 1, t)
+        if rc != expect or rc:
+            return rc, None
+        return rc, (out.lcu.get(ctx).tobytes(), out.pic.get(ctx).tobytes())   # blocking downloads on the consumer's lane
+
+    def reference(self, w, h):
+        """the chain on the root alone, a synchronisation after every call"""
+        if (w, h) not in self.want:
+            lib, root = self.lib, self.root
+            p, op = controls(w, h)
+            self.fill(root, w, h, stale=False)
+            ok(lib, lib.svt_amd_me_batch_launch(root, me_jobs(p, range(N)), N))
+            ok(lib, lib.svt_amd_synchronize(root))
+            ok(lib, lib.svt_amd_ois_batch_launch(root, ois_jobs(op, range(N)), N))
+            ok(lib, lib.svt_amd_synchronize(root))
+            rc, got = self.consume(root, w, h, range(N))
+            ok(lib, rc)
+            rc, first = self.consume(root, w, h, [0], ois_from_slot=False)
+            ok(lib, rc)
+            # other pictures leave other records, or the comparisons below could not tell a stale slot from a written one
+            self.fill(root, w, h, stale=True)
+            rc, other = self.consume(root, w, h, range(N))
+            ok(lib, rc)
+            assert other != got
+            self.want[w, h] = dict(all=got, first=first)
+        return self.want[w, h]
+
+    def busy(self, lane):
+        ok(self.lib, self.lib.svt_amd_me_batch_launch(lane, me_jobs(self.busy_p, range(8, 8 + BUSY)), BUSY))
+
+    def close(self):
+        for c in (self.a, self.b, self.root):
+            ok(self.lib, self.lib.svt_amd_synchronize(c))
+        for out in self.outs:
+            out.free()
+        for pics in self.pics.values():
+            pics.free()
+        for c in (self.a, self.b, self.root):
+            self.lib.svt_amd_context_destroy(c)
+
+
+@pytest.fixture(scope="module")
+def world(lib):
+    w = World(lib)
+    yield w
+    w.close()
+
+
+def test_one_record_per_launch(lib, world):
+    """ME and OIS batch launches of 1, 2 and 5 pictures raise `records` by one each; so do the single-picture entries"""
+    w, h = SIZES[1]
+    p, op = controls(w, h)
+    world.fill(world.a, w, h, stale=False)
+    a = world.a
+    for n in (1, 2, 5):
+        r0 = markers(lib, a)[0]
+        ok(lib, lib.svt_amd_me_batch_launch(a, me_jobs(p, range(n)), n))
+        r1 = markers(lib, a)[0]
+        ok(lib, lib.svt_amd_ois_batch_launch(a, ois_jobs(op, range(n)), n))
+        r2 = markers(lib, a)[0]
+        assert (r1 - r0, r2 - r1) == (1, 1), n
+    refs = (C.c_int * 2)(1, 1)
+    r0 = markers(lib, a)[0]
+    ok(lib, lib.svt_amd_me_picture_launch(a, C.byref(p), 0, refs))
+    r1 = markers(lib, a)[0]
+    ok(lib, lib.svt_amd_me_picture_range_launch(a, C.byref(p), 0, refs, 1, 2))
+    r2 = markers(lib, a)[0]
+    ok(lib, lib.svt_amd_ois_picture_launch(a, C.byref(op), 0))
+    r3 = markers(lib, a)[0]
+    assert (r1 - r0, r2 - r1, r3 - r2) == (1, 1, 1)
+    assert markers(lib, world.b)[0] == 0                                                # a lane that launched nothing has recorded nothing
+    ok(lib, lib.svt_amd_synchronize(a))
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+@pytest.mark.parametrize("me_launches,consumer,waits", [(1, "b", 2), (2, "b", 3), (1, "a", 0)])
+def test_consumer_waits_once_per_producing_launch(lib, world, w, h, me_launches, consumer, waits):
+    """ME + OIS of five pictures on lane A behind a long batch, the source-based operations on lane B (or on A itself) with the records read in the slots"""
+    want = world.reference(w, h)["all"]
+    p, op = controls(w, h)
+    world.fill(world.root, w, h, stale=True)
+    world.fill(world.a, w, h, stale=False)
+    world.busy(world.a)
+    if me_launches == 1:
+        ok(lib, lib.svt_amd_me_batch_launch(world.a, me_jobs(p, range(N)), N))
+    else:
+        ok(lib, lib.svt_amd_me_batch_launch(world.a, me_jobs(p, range(3)), 3))
+        ok(lib, lib.svt_amd_me_batch_launch(world.a, me_jobs(p, range(3, N)), N - 3))
+    ok(lib, lib.svt_amd_ois_batch_launch(world.a, ois_jobs(op, range(N)), N))
+    lane = world.b if consumer == "b" else world.a
+    w0 = markers(lib, lane)[1]
+    rc, got = world.consume(lane, w, h, range(N))
+    ok(lib, rc)
+    assert markers(lib, lane)[1] - w0 == waits
+    assert got == want
+    ok(lib, lib.svt_amd_synchronize(world.a))
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+def test_producing_lane_destroyed_first(lib, world, w, h):
+    """the slots outlive the lane whose marker they borrowed: the consumer on the root finds nothing to wait for, and the records"""
+    want = world.reference(w, h)["all"]
+    p, op = controls(w, h)
+    world.fill(world.root, w, h, stale=True)
+    lane = vp()
+    ok(lib, lib.svt_amd_context_fork(world.root, C.byref(lane)))
+    world.fill(lane, w, h, stale=False)
+    ok(lib, lib.svt_amd_me_batch_launch(lane, me_jobs(p, range(N)), N))
+    ok(lib, lib.svt_amd_ois_batch_launch(lane, ois_jobs(op, range(N)), N))
+    ok(lib, lib.svt_amd_synchronize(lane))
+    lib.svt_amd_context_destroy(lane)
+    w0 = markers(lib, world.root)[1]
+    rc, got = world.consume(world.root, w, h, range(N))
+    ok(lib, rc)
+    assert markers(lib, world.root)[1] == w0
+    assert got == want
+
+
+@pytest.mark.parametrize("w,h", SIZES)
+def test_ring_wrap_leaves_a_stale_reference_safe(lib, world, w, h):
+    """40 single-picture ME launches on lane A, the first into slot 0, the others into slots 1 and 2 in turn: the ring of 16 markers has come round twice when
+    lane B reads slot 0's records - it waits once, on an entry lane A has re-recorded later in its stream, and reads the right records"""
+    want = world.reference(w, h)["first"]
+    p, _ = controls(w, h)
+    world.fill(world.root, w, h, stale=True)
+    world.fill(world.a, w, h, stale=False)
+    world.busy(world.a)
+    r0 = markers(lib, world.a)[0]
+    for k in range(40):
+        s = 0 if k == 0 else 1 + (k & 1)
+        ok(lib, lib.svt_amd_me_picture_launch(world.a, C.byref(p), s, (C.c_int * 2)(s + 1, s + 1)))
+    assert markers(lib, world.a)[0] - r0 == 40
+    w0 = markers(lib, world.b)[1]
+    rc, got = world.consume(world.b, w, h, [0], ois_from_slot=False)
+    ok(lib, rc)
+    assert markers(lib, world.b)[1] - w0 == 1
+    assert got == want
+    ok(lib, lib.svt_amd_synchronize(world.a))
+
+
+def test_upload_into_a_slot_clears_its_references(lib, world):
+    """after svt_amd_picture_upload_device_batch into a slot its records are the previous picture's: a consumer of them is refused, and waits for nothing"""
+    w, h = SIZES[0]
+    p, op = controls(w, h)
+    world.fill(world.a, w, h, stale=False)
+    ok(lib, lib.svt_amd_me_batch_launch(world.a, me_jobs(p, range(N)), N))
+    ok(lib, lib.svt_amd_ois_batch_launch(world.a, ois_jobs(op, range(N)), N))
+    w0 = markers(lib, world.b)[1]
+    rc, got = world.consume(world.b, w, h, [0, 1])
+    ok(lib, rc)
+    assert markers(lib, world.b)[1] - w0 == 2
+    luma = DeviceBuffer(lib, world.root, w * h)
+    try:
+        frame = np.ascontiguousarray(world.frames[w, h][0])
+        luma.put(frame)
+        ok(lib, lib.svt_amd_synchronize(world.root))
+        ok(lib, lib.svt_amd_picture_upload_device_batch(world.a, 1, (C.c_int * 1)(0), (vp * 1)(luma.ptr.value), w, w, h))
+        w0 = markers(lib, world.b)[1]
+        rc, _ = world.consume(world.b, w, h, [0, 1], expect=BAD_PARAM)
+        assert rc == BAD_PARAM and lib.svt_amd_last_error().startswith(R.ENTRY.encode() + b": job 0: slot 0 holds no complete ME records"), lib.svt_amd_last_error()
+        assert markers(lib, world.b)[1] == w0
+        rc, again = world.consume(world.b, w, h, [1])                  # the neighbour's records and reference are untouched
+        ok(lib, rc)
+        assert markers(lib, world.b)[1] - w0 == 2
+        assert again[0] == got[0][S.lcu_count(w, h) * R.SBO_LCU_DTYPE.itemsize:] and again[1] == got[1][R.SBO_PIC_DTYPE.itemsize:]
+        ok(lib, lib.svt_amd_synchronize(world.a))
+    finally:
+        luma.free()
