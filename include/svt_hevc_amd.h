@@ -2047,7 +2047,9 @@ SVT_AMD_API int svt_amd_debug_me_kernel_lds_bytes(const SvtAmdMeParams *params, 
  * (hipOccupancyMaxActiveBlocksPerMultiprocessor) and the kernel's private segment in bytes per lane (localSizeBytes of hipFuncGetAttributes: 0 = no scratch frame) */
 SVT_AMD_API int svt_amd_debug_me_kernel_occupancy(SvtAmdContext *ctx, const SvtAmdMeParams *params, int phase, int *workgroups_per_cu, int *private_bytes);
 /* measurement: the completion markers this context (lane) has recorded behind its ME / OIS launches since it was made - one per launch, however many pictures the
- * launch holds - and the waits on other lanes' markers it has issued as a consumer of records left in the slots (me == NULL / ois == NULL) */
+ * launch holds; the marker behind a kernel that READ a slot's records in place is not counted - and every wait on another lane's marker it has issued: as a consumer
+ * of records left in the slots (me == NULL / ois == NULL, an OIS launch reading the slot's ME records), as the next marker of a chain (a band of a picture whose
+ * other bands another lane wrote, a second reader of one slot), and as a launch into a slot whose records another lane is still reading */
 SVT_AMD_API int svt_amd_debug_launch_markers(SvtAmdContext *ctx, unsigned long long *records, unsigned long long *waits);
 
 #ifdef __cplusplus

@@ -49,13 +49,6 @@ static void plane_destroy(DevPlane *p)
     memset(p, 0, sizeof(*p));
 }
 
-static inline void slot_mark_lock(DevPicture *s)
-{
-    while (__atomic_exchange_n(&s->mark_lock, 1, __ATOMIC_ACQUIRE))
-        ;
-}
-static inline void slot_mark_unlock(DevPicture *s) { __atomic_store_n(&s->mark_lock, 0, __ATOMIC_RELEASE); }
-
 extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
 {
     if (!ctx)
@@ -65,15 +58,8 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
     (void)svt_amd_comm_destroy(ctx);
     /* the slots outlive a lane: whatever this context's launches wrote is finished (the synchronisation above), so a slot that still refers to one of its
      * markers has nothing to wait for - and must not keep an event that is destroyed below */
-    for (int i = 0; ctx->slots && i < ctx->num_slots; i++) {
-        DevPicture *s = &ctx->slots[i];
-        slot_mark_lock(s);
-        if (s->ev_me.lane == ctx)
-            s->ev_me = LaunchMark{nullptr, nullptr};
-        if (s->ev_ois.lane == ctx)
-            s->ev_ois = LaunchMark{nullptr, nullptr};
-        slot_mark_unlock(s);
-    }
+    for (int i = 0; ctx->slots && i < ctx->num_slots; i++)
+        slot_forget_lane(&ctx->slots[i].rec, ctx);
     for (int i = 0; i < 16; i++)
         if (ctx->ev_launch[i])
             (void)hipEventDestroy(ctx->ev_launch[i]);
@@ -99,8 +85,6 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
             (void)hipHostFree(s->h_staging);
         if (s->ev_ready)
             (void)hipEventDestroy(s->ev_ready);
-        if (s->ev_md_read)
-            (void)hipEventDestroy(s->ev_md_read);
     }
     if (!ctx->parent)
         free(ctx->slots);
@@ -166,7 +150,7 @@ static int context_common_create(SvtAmdContext *ctx)
     HIP_TRY(hipEventCreateWithFlags(&ctx->ev_done, hipEventDisableTiming | hipEventBlockingSync)); /* waited on for milliseconds by several host threads: they sleep */
     for (int i = 0; i < 16; i++)
         HIP_TRY(hipEventCreateWithFlags(&ctx->ev_launch[i], hipEventDisableTiming));
-    const int nlcu = ((ctx->max_w + 63) / 64) * ((ctx->max_h + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(ctx->max_w, ctx->max_h);
     if (hipMalloc((void **)&ctx->d_me_scratch, (size_t)nlcu * sizeof(SvtAmdMeLcuResult)) != hipSuccess ||
         hipMalloc(&ctx->d_prep_jobs, 128 * SVT_AMD_MAX_BATCH) != hipSuccess ||
         hipMalloc(&ctx->d_pack_src, sizeof(PackSrc) * SVT_AMD_MAX_BATCH) != hipSuccess ||
@@ -315,7 +299,7 @@ extern "C" int svt_amd_context_create(int device_ordinal, uint16_t max_luma_widt
     ctx->num_slots = num_picture_slots;
     ctx->slots = (DevPicture *)calloc((size_t)num_picture_slots, sizeof(DevPicture));
     int rc = ctx->slots ? SVT_AMD_OK : SVT_AMD_ERR_RESOURCES;
-    const int nlcu = ((max_luma_width + 63) / 64) * ((max_luma_height + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(max_luma_width, max_luma_height);
     if (rc == SVT_AMD_OK)
         rc = context_common_create(ctx);
     for (int i = 0; rc == SVT_AMD_OK && i < num_picture_slots; i++) {
@@ -336,7 +320,7 @@ extern "C" int svt_amd_context_create(int device_ordinal, uint16_t max_luma_widt
             break;
         }
         s->staging_bytes = (size_t)w * h;
-        if (hipEventCreateWithFlags(&s->ev_ready, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&s->ev_md_read, hipEventDisableTiming) != hipSuccess) {
+        if (hipEventCreateWithFlags(&s->ev_ready, hipEventDisableTiming) != hipSuccess) {
             svt_amd_set_error("hipEventCreate (slot %d) failed", i);
             rc = SVT_AMD_ERR_DEVICE;
             break;
@@ -591,7 +575,6 @@ extern "C" int svt_amd_host_free(SvtAmdContext *ctx, void *h_ptr)
 
 /* ---- pictures ---------------------------------------------------------- */
 
-static void slot_records_reset(DevPicture *s);
 static int check_slot(SvtAmdContext *ctx, int slot)
 {
     if (!ctx || slot < 0 || slot >= ctx->num_slots) {
@@ -630,7 +613,7 @@ extern "C" int svt_amd_picture_upload_device(SvtAmdContext *ctx, int slot, const
         return rc;
     if ((rc = svt_amd_launch_prep(ctx, s, (const uint8_t *)d_luma, stride)) != 0)
         return rc;
-    slot_records_reset(s); /* the records in the slot's buffers are the previous picture's */
+    slot_records_forget(&s->rec); /* the records in the slot's buffers are the previous picture's */
     s->valid = 1;
     return SVT_AMD_OK;
 }
@@ -657,7 +640,7 @@ extern "C" int svt_amd_picture_upload_device_batch(SvtAmdContext *ctx, int num, 
     if (rc)
         return rc;
     for (int i = 0; i < num; i++)
-        slot_records_reset(pics[i]), pics[i]->valid = 1;
+        slot_records_forget(&pics[i]->rec), pics[i]->valid = 1;
     return SVT_AMD_OK;
 }
 
@@ -737,95 +720,80 @@ static int validate_me(SvtAmdContext *ctx, const SvtAmdMeParams *p, int cur_slot
     return SVT_AMD_OK;
 }
 
-/* the slot's motion-estimation / open-loop intra search records are (being) written by kernels on this lane's stream: consumers on other lanes order themselves behind */
-/* A new picture enters the slot: whatever records the buffers hold belong to the previous one (every upload path calls this where it sets `valid`). */
-static void slot_records_reset(DevPicture *s)
+/* The completion marker of a launch: the next entry of the lane's ring (SvtAmdContext::ev_launch), recorded ONCE at the end of the lane's stream - behind the
+ * launch's kernels - and lent to every slot whose records they write or read in place.  A launch passes one `mark` ({nullptr, nullptr} at first) through all of
+ * its slots: the first records it.  Where the slot holds a marker of `kind` that still matters (slot_chain_behind) the lane's stream waits on that one first -
+ * behind the launch's kernels, so only the marker is ordered - and the new marker stands for both.  Wait, record and hand-over are one critical section of the
+ * slot: of two lanes one chains behind the other.  kind == SLOT_ME: the launch wrote LCUs [begin, end) of a picture of n; SLOT_OIS: all n. */
+static int slot_mark_lend(SvtAmdContext *ctx, DevPicture *s, int kind, LaunchMark *mark, uint32_t n, uint32_t begin, uint32_t end)
 {
-    __atomic_store_n(&s->me_lcus, 0u, __ATOMIC_RELEASE);
-    __atomic_store_n(&s->ois_lcus, 0u, __ATOMIC_RELEASE);
-    while (__atomic_exchange_n(&s->me_cov_lock, 1, __ATOMIC_ACQUIRE))
-        ;
-    memset(s->me_cov, 0, sizeof(s->me_cov));
-    s->me_cov_count = 0;
-    __atomic_store_n(&s->me_cov_lock, 0, __ATOMIC_RELEASE);
-    slot_mark_lock(s); /* no consumer is let at those records (me_lcus / ois_lcus are 0), so there is no launch to order one behind */
-    s->ev_me = s->ev_ois = LaunchMark{nullptr, nullptr};
-    slot_mark_unlock(s);
-}
-/* The completion marker of a launch: the next entry of the lane's ring, recorded ONCE at the current end of the lane's stream - behind the kernels of the
- * launch - and lent to every slot whose records those kernels write (the invariant that makes a stale reference harmless: SvtAmdContext::ev_launch). */
-static int svt_amd_launch_mark_record(SvtAmdContext *ctx, LaunchMark *mark)
-{
-    hipEvent_t ev = ctx->ev_launch[ctx->launch_next];
-    HIP_TRY(hipEventRecord(ev, svt_amd_ctx_stream(ctx)));
-    ctx->launch_next = (ctx->launch_next + 1) & 15;
-    ctx->mark_records++;
-    *mark = LaunchMark{ev, ctx};
+    SlotRecords *r = &s->rec;
+    slot_lock(r);
+    const hipEvent_t behind = slot_chain_behind(r, kind, ctx, begin == 0 && end >= n);
+    hipError_t e = behind ? hipStreamWaitEvent(svt_amd_ctx_stream(ctx), behind, 0) : hipSuccess;
+    if (e == hipSuccess && !mark->ev) {
+        const hipEvent_t ev = ctx->ev_launch[ctx->launch_next];
+        if ((e = hipEventRecord(ev, svt_amd_ctx_stream(ctx))) == hipSuccess) {
+            ctx->launch_next = (ctx->launch_next + 1) & 15;
+            ctx->mark_records += kind != SLOT_READ; /* the counter is of producing launches */
+            *mark = LaunchMark{ev, ctx};
+        }
+    }
+    if (e == hipSuccess) {
+        r->mark[kind] = *mark;
+        if (kind == SLOT_ME)
+            slot_me_cover(r, n, begin, end);
+        else if (kind == SLOT_OIS)
+            r->ois_lcus = n;
+    }
+    slot_unlock(r);
+    HIP_TRY(e);
+    ctx->mark_waits += behind != nullptr;
     return SVT_AMD_OK;
 }
-static void slot_mark_set(DevPicture *s, int which, const LaunchMark &mark)
+/* The stream of `ctx` waits for the slot's marker of `kind` unless that is null or the lane's own: before it reads the records (SLOT_ME / SLOT_OIS) or writes
+ * them (SLOT_READ; the marker is spent then).  The wait is issued under the slot's lock: the lane that lent the marker cannot clear the reference and destroy
+ * its ring (svt_amd_context_destroy) in between. */
+int svt_amd_records_wait(SvtAmdContext *ctx, DevPicture *s, int kind, hipEvent_t *seen, int *nseen, int cap)
 {
-    slot_mark_lock(s);
-    (which ? s->ev_ois : s->ev_me) = mark;
-    slot_mark_unlock(s);
-}
-int svt_amd_records_wait(SvtAmdContext *ctx, DevPicture *s, int which, hipEvent_t *seen, int *nseen, int cap)
-{
-    /* the wait is issued under the slot's lock: the producing lane cannot clear the reference and destroy its ring (svt_amd_context_destroy) in between */
-    slot_mark_lock(s);
-    const LaunchMark m = which ? s->ev_ois : s->ev_me;
-    bool wait = m.ev && m.lane != ctx;
+    slot_lock(&s->rec);
+    const hipEvent_t ev = slot_wait_for(&s->rec, kind, ctx);
+    bool wait = ev != nullptr;
     for (int i = 0; wait && seen && i < *nseen; i++)
-        wait = seen[i] != m.ev;
-    const hipError_t e = wait ? hipStreamWaitEvent(svt_amd_ctx_stream(ctx), m.ev, 0) : hipSuccess;
-    slot_mark_unlock(s);
+        wait = seen[i] != ev;
+    const hipError_t e = wait ? hipStreamWaitEvent(svt_amd_ctx_stream(ctx), ev, 0) : hipSuccess;
+    if (ev && kind == SLOT_READ && e == hipSuccess)
+        s->rec.mark[SLOT_READ] = LaunchMark{nullptr, nullptr};
+    slot_unlock(&s->rec);
     HIP_TRY(e);
     if (wait) {
         ctx->mark_waits++;
         if (seen && *nseen < cap)
-            seen[(*nseen)++] = m.ev;
+            seen[(*nseen)++] = ev;
     }
     return SVT_AMD_OK;
+}
+/* Before a kernel of this lane writes the slot's record buffers: a kernel of another lane may still be reading the previous picture's records in place */
+static int slot_records_before_write(SvtAmdContext *ctx, DevPicture *s) { return svt_amd_records_wait(ctx, s, SLOT_READ, nullptr, nullptr, 0); }
+int svt_amd_records_read_mark(SvtAmdContext *ctx, SvtAmdContext *root, int slot)
+{
+    LaunchMark mark{nullptr, nullptr};
+    return slot_mark_lend(ctx, &root->slots[slot], SLOT_READ, &mark, 0, 0, 0);
+}
+const void *svt_amd_slot_records(SvtAmdContext *root, int slot, int which, int w, int h)
+{
+    if (slot < 0 || slot >= root->num_slots)
+        return nullptr;
+    DevPicture *s = &root->slots[slot];
+    if (!s->valid || s->width != w || s->height != h || slot_lcus(&s->rec, which) != (uint32_t)svt_amd_lcu_count(w, h))
+        return nullptr;
+    return which ? (const void *)s->d_ois_out : (const void *)s->d_me_out;
 }
 extern "C" int svt_amd_debug_launch_markers(SvtAmdContext *ctx, unsigned long long *records, unsigned long long *waits)
 {
     if (!ctx || !records || !waits)
         return SVT_AMD_ERR_BAD_PARAM;
     *records = ctx->mark_records, *waits = ctx->mark_waits;
-    return SVT_AMD_OK;
-}
-/* Before a kernel of this lane writes the slot's record buffers: a mode-decision kernel of another lane may still be reading the previous picture's records in place
- * (svt_amd_md_encode_picture_inter with me == NULL / ois == NULL records ev_md_read behind its launch). */
-static int slot_records_before_write(SvtAmdContext *ctx, DevPicture *s)
-{
-    if (__atomic_load_n(&s->md_read_pending, __ATOMIC_ACQUIRE)) {
-        HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), s->ev_md_read, 0));
-        __atomic_store_n(&s->md_read_pending, 0, __ATOMIC_RELEASE);
-    }
-    return SVT_AMD_OK;
-}
-/* [lcu_begin, lcu_end): the LCUs the launch wrote.  The slot counts as holding the picture's records only when the launches since the last upload cover all of it. */
-static int me_records_written(SvtAmdContext *ctx, int slot, const SvtAmdMeParams *p, uint32_t lcu_begin, uint32_t lcu_end, const LaunchMark &mark)
-{
-    DevPicture *s = &ctx->slots[slot];
-    const uint32_t n = ((p->luma_width + 63u) / 64u) * ((p->luma_height + 63u) / 64u);
-    uint32_t covered;
-    while (__atomic_exchange_n(&s->me_cov_lock, 1, __ATOMIC_ACQUIRE)) /* (two lanes may launch bands of one slot side by side) */
-        ;
-    for (uint32_t i = lcu_begin; i < lcu_end && i < n && i < 64u * 128u; i++)
-        if (!((s->me_cov[i >> 6] >> (i & 63)) & 1ull))
-            s->me_cov[i >> 6] |= 1ull << (i & 63), s->me_cov_count++;
-    covered = s->me_cov_count;
-    __atomic_store_n(&s->me_cov_lock, 0, __ATOMIC_RELEASE);
-    slot_mark_set(s, 0, mark);
-    __atomic_store_n(&s->me_lcus, covered >= n ? n : 0u, __ATOMIC_RELEASE);
-    return SVT_AMD_OK;
-}
-static int ois_records_written(SvtAmdContext *ctx, int slot, const SvtAmdOisParams *p, const LaunchMark &mark)
-{
-    DevPicture *s = &ctx->slots[slot];
-    slot_mark_set(s, 1, mark);
-    __atomic_store_n(&s->ois_lcus, ((p->luma_width + 63u) / 64u) * ((p->luma_height + 63u) / 64u), __ATOMIC_RELEASE);
     return SVT_AMD_OK;
 }
 
@@ -835,7 +803,7 @@ static int make_job(SvtAmdContext *ctx, const SvtAmdMeParams *params, int cur_sl
     int rc = validate_me(ctx, params, cur_slot, ref_slot);
     if (rc)
         return rc;
-    const uint32_t nlcu = ((params->luma_width + 63u) / 64u) * ((params->luma_height + 63u) / 64u);
+    const uint32_t nlcu = svt_amd_lcu_count(params->luma_width, params->luma_height);
     if (lcu_begin >= lcu_end || lcu_end > nlcu) {
         svt_amd_set_error("motion estimation: bad LCU range [%u,%u) of %u", lcu_begin, lcu_end, nlcu);
         return SVT_AMD_ERR_BAD_PARAM;
@@ -865,10 +833,9 @@ extern "C" int svt_amd_me_picture_range_launch(SvtAmdContext *ctx, const SvtAmdM
     HIP_TRY(hipSetDevice(ctx->device));
     if ((rc = slot_records_before_write(ctx, &ctx->slots[cur_slot])) != 0)
         return rc;
-    rc = svt_amd_launch_me_batch(ctx, &job, 1, job.lcu_count);
-    LaunchMark mark;
-    if (rc == SVT_AMD_OK && (rc = svt_amd_launch_mark_record(ctx, &mark)) == SVT_AMD_OK)
-        rc = me_records_written(ctx, cur_slot, params, lcu_begin, lcu_end, mark);
+    LaunchMark mark{nullptr, nullptr};
+    if ((rc = svt_amd_launch_me_batch(ctx, &job, 1, job.lcu_count)) == SVT_AMD_OK)
+        rc = slot_mark_lend(ctx, &ctx->slots[cur_slot], SLOT_ME, &mark, (uint32_t)svt_amd_lcu_count(params->luma_width, params->luma_height), lcu_begin, lcu_end);
     return rc;
 }
 
@@ -884,7 +851,7 @@ extern "C" int svt_amd_me_batch_launch(SvtAmdContext *ctx, const SvtAmdMeJob *jo
     int rc = SVT_AMD_OK, max_lcus = 0;
     for (int i = 0; i < num_jobs && rc == SVT_AMD_OK; i++) {
         const SvtAmdMeParams *p = &jobs[i].params;
-        const uint32_t nlcu = ((p->luma_width + 63u) / 64u) * ((p->luma_height + 63u) / 64u);
+        const uint32_t nlcu = svt_amd_lcu_count(p->luma_width, p->luma_height);
         rc = make_job(ctx, p, jobs[i].cur_slot, jobs[i].ref_slot, 0, nlcu, &dj[i]);
         if (rc == SVT_AMD_OK)
             max_lcus = dj[i].lcu_count > max_lcus ? dj[i].lcu_count : max_lcus;
@@ -898,11 +865,9 @@ extern "C" int svt_amd_me_batch_launch(SvtAmdContext *ctx, const SvtAmdMeJob *jo
             rc = slot_records_before_write(ctx, &ctx->slots[jobs[i].cur_slot]);
         if (rc == SVT_AMD_OK)
             rc = e == hipSuccess ? svt_amd_launch_me_batch(ctx, dj, num_jobs, max_lcus) : SVT_AMD_ERR_DEVICE;
-        LaunchMark mark; /* every slot of the batch is written by the same kernels: one marker behind them serves all */
-        if (rc == SVT_AMD_OK)
-            rc = svt_amd_launch_mark_record(ctx, &mark);
+        LaunchMark mark{nullptr, nullptr}; /* every slot of the batch is written by the same kernels: one marker behind them serves all */
         for (int i = 0; i < num_jobs && rc == SVT_AMD_OK; i++)
-            rc = me_records_written(ctx, jobs[i].cur_slot, &jobs[i].params, 0, (uint32_t)dj[i].lcu_count, mark);
+            rc = slot_mark_lend(ctx, &ctx->slots[jobs[i].cur_slot], SLOT_ME, &mark, (uint32_t)dj[i].lcu_count, 0, (uint32_t)dj[i].lcu_count);
     }
     free(dj);
     return rc;
@@ -951,11 +916,12 @@ extern "C" int svt_amd_me_picture_launch(SvtAmdContext *ctx, const SvtAmdMeParam
 {
     if (!params)
         return SVT_AMD_ERR_BAD_PARAM;
-    const uint32_t nlcu = ((params->luma_width + 63u) / 64u) * ((params->luma_height + 63u) / 64u);
+    const uint32_t nlcu = svt_amd_lcu_count(params->luma_width, params->luma_height);
     return svt_amd_me_picture_range_launch(ctx, params, cur_slot, ref_slot, 0, nlcu);
 }
 
-extern "C" int svt_amd_me_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtAmdMeLcuResult *out)
+/* the slot's ME (which == 0) / OIS records into host memory on the context's stream; sync: the host waits (else complete after svt_amd_synchronize; pinned memory) */
+static int records_fetch(SvtAmdContext *ctx, int cur_slot, int which, void *out, bool sync)
 {
     int rc = check_slot(ctx, cur_slot);
     if (rc)
@@ -964,40 +930,16 @@ extern "C" int svt_amd_me_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtAmd
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     DevPicture *c = &ctx->slots[cur_slot];
-    const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(out, c->d_me_out, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyDeviceToHost,
-                           svt_amd_ctx_stream(ctx)));
-    HIP_TRY(svt_amd_ctx_sync(ctx));
+    const size_t bytes = (size_t)svt_amd_lcu_count(c->width, c->height) * (which ? sizeof(SvtAmdOisLcuResult) : sizeof(SvtAmdMeLcuResult));
+    HIP_TRY(hipMemcpyAsync(out, which ? (const void *)c->d_ois_out : (const void *)c->d_me_out, bytes, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+    if (sync)
+        HIP_TRY(svt_amd_ctx_sync(ctx));
     return SVT_AMD_OK;
 }
-
-/* stream-ordered copy of the slot's ME / OIS records into (pinned) host memory; complete after svt_amd_synchronize */
-extern "C" int svt_amd_me_picture_fetch_async(SvtAmdContext *ctx, int cur_slot, SvtAmdMeLcuResult *out)
-{
-    int rc = check_slot(ctx, cur_slot);
-    if (rc)
-        return rc;
-    if (!out)
-        return SVT_AMD_ERR_BAD_PARAM;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevPicture *c = &ctx->slots[cur_slot];
-    const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(out, c->d_me_out, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
-    return SVT_AMD_OK;
-}
-extern "C" int svt_amd_ois_picture_fetch_async(SvtAmdContext *ctx, int cur_slot, SvtAmdOisLcuResult *out)
-{
-    int rc = check_slot(ctx, cur_slot);
-    if (rc)
-        return rc;
-    if (!out)
-        return SVT_AMD_ERR_BAD_PARAM;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevPicture *c = &ctx->slots[cur_slot];
-    const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(out, c->d_ois_out, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
-    return SVT_AMD_OK;
-}
+extern "C" int svt_amd_me_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtAmdMeLcuResult *out) { return records_fetch(ctx, cur_slot, 0, out, true); }
+extern "C" int svt_amd_me_picture_fetch_async(SvtAmdContext *ctx, int cur_slot, SvtAmdMeLcuResult *out) { return records_fetch(ctx, cur_slot, 0, out, false); }
+extern "C" int svt_amd_ois_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtAmdOisLcuResult *out) { return records_fetch(ctx, cur_slot, 1, out, true); }
+extern "C" int svt_amd_ois_picture_fetch_async(SvtAmdContext *ctx, int cur_slot, SvtAmdOisLcuResult *out) { return records_fetch(ctx, cur_slot, 1, out, false); }
 
 /* Cross-lane ordering for hosts that build their own pipelines (bench.py: copy-in lane -> compute lane -> copy-out lane): lane
  * `lane` records its event `index` at the current end of its stream; svt_amd_lane_event_wait makes another lane's stream wait for
@@ -1101,7 +1043,7 @@ extern "C" int svt_amd_me_picture_fetch_compact_async(SvtAmdContext *ctx, int cu
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     DevPicture *c = &ctx->slots[cur_slot];
-    const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(c->width, c->height);
     uint8_t *d = nullptr;
     if ((rc = slot_pack_buffer(ctx, c, pack_me_bytes(nlcu) + (size_t)nlcu * sizeof(SvtAmdOisLcuResult), &d)) != 0)
         return rc;
@@ -1121,7 +1063,7 @@ extern "C" int svt_amd_ois_picture_fetch_compact_async(SvtAmdContext *ctx, int c
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     DevPicture *c = &ctx->slots[cur_slot];
-    const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(c->width, c->height);
     uint8_t *d = nullptr;
     if ((rc = slot_pack_buffer(ctx, c, pack_me_bytes(nlcu) + (size_t)nlcu * sizeof(SvtAmdOisLcuResult), &d)) != 0)
         return rc;
@@ -1146,7 +1088,7 @@ extern "C" int svt_amd_records_pack_batch_async(SvtAmdContext *ctx, const int *s
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     const DevPicture *c0 = &ctx->slots[slots[0]];
-    const int nlcu = ((c0->width + 63) / 64) * ((c0->height + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(c0->width, c0->height);
     static thread_local PackSrc tab[SVT_AMD_MAX_BATCH];
     for (int i = 0; i < n; i++) {
         if ((rc = check_slot(ctx, slots[i])) != 0)
@@ -1205,14 +1147,17 @@ static int ois_launch(SvtAmdContext *ctx, const SvtAmdOisParams *params, int cur
     HIP_TRY(hipSetDevice(ctx->device));
     OisJobDev j;
     make_ois_job(ctx, params, cur_slot, d_me, &j);
-    int rc = slot_records_before_write(ctx, &ctx->slots[cur_slot]);
+    DevPicture *c = &ctx->slots[cur_slot];
+    int rc = slot_records_before_write(ctx, c);
+    if (!rc && d_me == c->d_me_out && !params->slice_is_intra) /* a P / B picture's search reads the slot's ME records: another lane may have left them */
+        rc = svt_amd_records_wait(ctx, c, SLOT_ME, nullptr, nullptr, 0);
     if (rc || (rc = svt_amd_stamp_begin(ctx, KC_OIS)) != 0)
         return rc;
     rc = svt_amd_launch_ois_batch(ctx, &j, 1, j.nlcu);
     const int rc2 = svt_amd_stamp_end(ctx);
-    LaunchMark mark;
-    if (!rc && !rc2 && !(rc = svt_amd_launch_mark_record(ctx, &mark)))
-        return ois_records_written(ctx, cur_slot, params, mark);
+    LaunchMark mark{nullptr, nullptr};
+    if (!rc && !rc2)
+        rc = slot_mark_lend(ctx, c, SLOT_OIS, &mark, (uint32_t)j.nlcu, 0, (uint32_t)j.nlcu);
     return rc ? rc : rc2;
 }
 
@@ -1231,17 +1176,20 @@ extern "C" int svt_amd_ois_batch_launch(SvtAmdContext *ctx, const SvtAmdOisJob *
     }
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = SVT_AMD_OK;
-    for (int i = 0; i < num_jobs && !rc; i++)
-        rc = slot_records_before_write(ctx, &ctx->slots[jobs[i].cur_slot]);
+    hipEvent_t waited[32]; /* the ME launches of other lanes whose records the P / B pictures' searches read: one wait each */
+    int nwaited = 0;
+    for (int i = 0; i < num_jobs && !rc; i++) {
+        DevPicture *c = &ctx->slots[jobs[i].cur_slot];
+        if ((rc = slot_records_before_write(ctx, c)) == 0 && !jobs[i].params.slice_is_intra)
+            rc = svt_amd_records_wait(ctx, c, SLOT_ME, waited, &nwaited, 32);
+    }
     if (rc || (rc = svt_amd_stamp_begin(ctx, KC_OIS)) != 0)
         return rc;
     rc = svt_amd_launch_ois_batch(ctx, host, num_jobs, max_lcus);
     const int rc2 = svt_amd_stamp_end(ctx);
-    LaunchMark mark; /* one marker behind the launch for all of its slots, as in svt_amd_me_batch_launch */
-    if (!rc && !rc2)
-        rc = svt_amd_launch_mark_record(ctx, &mark);
+    LaunchMark mark{nullptr, nullptr}; /* one marker behind the launch for all of its slots, as in svt_amd_me_batch_launch */
     for (int i = 0; i < num_jobs && !rc && !rc2; i++)
-        rc = ois_records_written(ctx, jobs[i].cur_slot, &jobs[i].params, mark);
+        rc = slot_mark_lend(ctx, &ctx->slots[jobs[i].cur_slot], SLOT_OIS, &mark, (uint32_t)host[i].nlcu, 0, (uint32_t)host[i].nlcu);
     return rc ? rc : rc2;
 }
 
@@ -1251,21 +1199,6 @@ extern "C" int svt_amd_ois_picture_launch(SvtAmdContext *ctx, const SvtAmdOisPar
     if (rc)
         return rc;
     return ois_launch(ctx, params, cur_slot, ctx->slots[cur_slot].d_me_out);
-}
-
-extern "C" int svt_amd_ois_picture_fetch(SvtAmdContext *ctx, int cur_slot, SvtAmdOisLcuResult *out)
-{
-    int rc = check_slot(ctx, cur_slot);
-    if (rc)
-        return rc;
-    if (!out)
-        return SVT_AMD_ERR_BAD_PARAM;
-    HIP_TRY(hipSetDevice(ctx->device));
-    DevPicture *c = &ctx->slots[cur_slot];
-    const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
-    HIP_TRY(hipMemcpyAsync(out, c->d_ois_out, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
-    HIP_TRY(svt_amd_ctx_sync(ctx));
-    return SVT_AMD_OK;
 }
 
 extern "C" int svt_amd_ois_picture(SvtAmdContext *ctx, const SvtAmdOisParams *params, int cur_slot,
@@ -1279,7 +1212,7 @@ extern "C" int svt_amd_ois_picture(SvtAmdContext *ctx, const SvtAmdOisParams *pa
     const SvtAmdMeLcuResult *d_me = ctx->slots[cur_slot].d_me_out;
     if (me) {
         HIP_TRY(hipSetDevice(ctx->device));
-        const int nlcu = ((params->luma_width + 63) / 64) * ((params->luma_height + 63) / 64);
+        const int nlcu = svt_amd_lcu_count(params->luma_width, params->luma_height);
         HIP_TRY(hipMemcpyAsync(ctx->d_me_scratch, me, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
         HIP_TRY(svt_amd_ctx_sync(ctx)); /* `me` may be freed by the caller on return of a later call */
         d_me = ctx->d_me_scratch;
@@ -1320,7 +1253,7 @@ extern "C" int svt_amd_picture_upload_async(SvtAmdContext *ctx, int slot, const 
     if ((rc = svt_amd_launch_prep(ctx, s, s->d_staging, width)) != 0)
         return rc;
     HIP_TRY(hipEventRecord(s->ev_ready, svt_amd_ctx_stream(ctx)));
-    slot_records_reset(s); /* the records in the slot's buffers are the previous picture's */
+    slot_records_forget(&s->rec); /* the records in the slot's buffers are the previous picture's */
     s->valid = 1;
     return SVT_AMD_OK;
 }
@@ -1351,14 +1284,14 @@ extern "C" int svt_amd_frontend_submit(SvtAmdContext *ctx, const SvtAmdFrontendJ
         return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     DevPicture *c = &ctx->slots[job->cur_slot];
-    const int nlcu = ((ctx->max_w + 63) / 64) * ((ctx->max_h + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(ctx->max_w, ctx->max_h);
     if (!ctx->h_me)
         HIP_TRY(hipHostMalloc((void **)&ctx->h_me, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipHostMallocDefault));
     if (!ctx->h_ois)
         HIP_TRY(hipHostMalloc((void **)&ctx->h_ois, (size_t)nlcu * sizeof(SvtAmdOisLcuResult), hipHostMallocDefault));
     /* pictures may have been prepared on another lane's stream */
     HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), c->ev_ready, 0));
-    const int pn = ((c->width + 63) / 64) * ((c->height + 63) / 64);
+    const int pn = svt_amd_lcu_count(c->width, c->height);
     if (job->has_me) {
         for (int l = 0; l < job->me.num_lists && l < 2; l++) {
             if ((rc = check_slot(ctx, job->ref_slot[l])) != 0)
@@ -1421,7 +1354,7 @@ extern "C" int svt_amd_frontend_warmup(SvtAmdContext *ctx)
     if (!ctx)
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    const int nlcu = ((ctx->max_w + 63) / 64) * ((ctx->max_h + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(ctx->max_w, ctx->max_h);
     if (!ctx->h_me)
         HIP_TRY(hipHostMalloc((void **)&ctx->h_me, (size_t)nlcu * sizeof(SvtAmdMeLcuResult), hipHostMallocDefault));
     if (!ctx->h_ois)
@@ -1493,7 +1426,7 @@ extern "C" int svt_amd_zz_sad_picture(SvtAmdContext *ctx, int cur_slot, int prev
         return SVT_AMD_ERR_BAD_PARAM;
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    const int nlcu = ((c->width + 63) / 64) * ((c->height + 63) / 64);
+    const int nlcu = svt_amd_lcu_count(c->width, c->height);
     /* results are small (8 B / LCU): reuse the head of the ME scratch buffer */
     SvtAmdZzLcu *d_out = (SvtAmdZzLcu *)ctx->d_me_scratch;
     if ((rc = svt_amd_launch_zz_sad(ctx, c, p, d_out)) != 0)

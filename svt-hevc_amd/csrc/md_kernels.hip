@@ -3188,26 +3188,21 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
         }
     }
     DevPicture *rec_slot[2] = {nullptr, nullptr}; /* records read where another lane's kernels leave them: this lane's stream orders itself behind those kernels */
+    SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
     const SvtAmdMeLcuResult *d_me_slot = nullptr;
     if (X && !me) {
-        SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
-        if (me_slot < 0 || me_slot >= root->num_slots || !root->slots[me_slot].d_me_out || !root->slots[me_slot].valid || __atomic_load_n(&root->slots[me_slot].me_lcus, __ATOMIC_ACQUIRE) != (uint32_t)n ||
-            root->slots[me_slot].width != pic->d.width || root->slots[me_slot].height != pic->d.height) {
+        if (!(d_me_slot = (const SvtAmdMeLcuResult *)svt_amd_slot_records(root, me_slot, 0, pic->d.width, pic->d.height))) {
             svt_amd_set_error("svt_amd_md_encode_picture_inter: slot %d does not hold the motion-estimation records of a %u x %u picture (none launched for the slot's current picture, or only a part of it)", me_slot, pic->d.width, pic->d.height);
             return SVT_AMD_ERR_BAD_PARAM;
         }
-        d_me_slot = root->slots[me_slot].d_me_out;
         rec_slot[0] = &root->slots[me_slot];
     }
     const SvtAmdOisLcuResult *d_ois_slot = nullptr;
     if (!ois) {
-        SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
-        if (ois_slot < 0 || ois_slot >= root->num_slots || !root->slots[ois_slot].d_ois_out || !root->slots[ois_slot].valid || __atomic_load_n(&root->slots[ois_slot].ois_lcus, __ATOMIC_ACQUIRE) != (uint32_t)n ||
-            root->slots[ois_slot].width != pic->d.width || root->slots[ois_slot].height != pic->d.height) {
+        if (!(d_ois_slot = (const SvtAmdOisLcuResult *)svt_amd_slot_records(root, ois_slot, 1, pic->d.width, pic->d.height))) {
             svt_amd_set_error("svt_amd_md_encode_picture: slot %d does not hold the open-loop intra search records of a %u x %u picture", ois_slot, pic->d.width, pic->d.height);
             return SVT_AMD_ERR_BAD_PARAM;
         }
-        d_ois_slot = root->slots[ois_slot].d_ois_out;
         rec_slot[1] = &root->slots[ois_slot];
     }
     if (pic->md_rect_n) { /* a rank's rectangle (svt_amd_encdec_picture_set_rect): its borders must be tile borders - an LCU never waits for one outside */
@@ -3432,15 +3427,11 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     HIP_TRY(hipEventRecord(m->ev_k2, st));
     if ((rc = ep_picture_written(ctx, pic)) != 0)
         return rc;
-    {   /* records read in place: the next motion-estimation / open-loop intra launch INTO those slots orders itself behind this kernel (context.hip slot_records_before_write) */
-        SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
-        const int rs[2] = {d_me_slot ? me_slot : -1, d_ois_slot ? ois_slot : -1};
-        for (int k = 0; k < 2; k++)
-            if (rs[k] >= 0 && !(k == 1 && rs[1] == rs[0])) {
-                HIP_TRY(hipEventRecord(root->slots[rs[k]].ev_md_read, st));
-                __atomic_store_n(&root->slots[rs[k]].md_read_pending, 1, __ATOMIC_RELEASE);
-            }
-    }
+    /* records read in place: the next motion-estimation / open-loop intra launch INTO those slots orders itself behind this kernel */
+    if (rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, me_slot)) != 0)
+        return rc;
+    if (rec_slot[1] && rec_slot[1] != rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, ois_slot)) != 0)
+        return rc;
     if (timing) {
         HIP_TRY(hipStreamSynchronize(st));
         t_kernel = std::chrono::steady_clock::now();

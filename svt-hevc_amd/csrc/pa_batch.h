@@ -12,7 +12,6 @@
 #define SVT_AMD_BAD(...) do { svt_amd_set_error(__VA_ARGS__); return SVT_AMD_ERR_BAD_PARAM; } while (0)
 #define SVT_AMD_TRY(expr) do { const int rc_ = (expr); if (rc_) return rc_; } while (0)
 
-static inline int svt_amd_lcu_count(int w, int h) { return ((w + 63) / 64) * ((h + 63) / 64); }
 static inline bool svt_amd_regions_ok(int regions_w, int regions_h) { return regions_w >= 1 && regions_h >= 1 && regions_w * regions_h <= 64; }
 int svt_amd_batch_header(const char *entry, const SvtAmdContext *ctx, const void *jobs, const void *out, int num_jobs);
 int svt_amd_batch_slot(const char *entry, const SvtAmdContext *ctx, int job, int slot, int *w, int *h);

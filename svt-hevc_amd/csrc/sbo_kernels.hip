@@ -438,9 +438,9 @@ extern "C" int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmdS
                 SVT_AMD_BAD("%s: job %d reads the %s records of slot %d, which holds no picture", __func__, i, j.me ? "OIS" : "ME", j.cur_slot);
             if (c->width != w || c->height != h)
                 SVT_AMD_BAD("%s: job %d: slot %d holds a picture of %dx%d, the batch is %dx%d", __func__, i, j.cur_slot, c->width, c->height, w, h);
-            if (!j.me && __atomic_load_n(&c->me_lcus, __ATOMIC_ACQUIRE) != (uint32_t)lcus)
+            if (!j.me && !svt_amd_slot_records(ctx, j.cur_slot, 0, w, h))
                 SVT_AMD_BAD("%s: job %d: slot %d holds no complete ME records", __func__, i, j.cur_slot);
-            if (!j.ois && __atomic_load_n(&c->ois_lcus, __ATOMIC_ACQUIRE) != (uint32_t)lcus)
+            if (!j.ois && !svt_amd_slot_records(ctx, j.cur_slot, 1, w, h))
                 SVT_AMD_BAD("%s: job %d: slot %d holds no complete OIS records", __func__, i, j.cur_slot);
         }
     }

@@ -15,6 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/svt_hevc_amd.h"
+#include "slot_records.h"
+
+static inline int svt_amd_lcu_count(int w, int h) { return ((w + 63) / 64) * ((h + 63) / 64); }
 
 struct DevPlane {
     uint8_t *origin;   /* device pointer to sample (0,0) */
@@ -24,13 +27,6 @@ struct DevPlane {
     size_t   alloc_bytes;
     int32_t  lead_rows; /* rows above y = -pad kept as guard */
     int32_t  lead_cols; /* bytes left of x = 0 in each row   */
-};
-
-/* Where a slot's ME / OIS records come from: the completion marker of the launch that last wrote them, borrowed from the ring of the lane that recorded it
- * (SvtAmdContext::ev_launch).  ev == nullptr: nothing to wait for (no launch since the last upload, or the producing lane is finished and gone). */
-struct LaunchMark {
-    hipEvent_t ev;
-    struct SvtAmdContext *lane;
 };
 
 struct DevPicture {
@@ -44,19 +40,7 @@ struct DevPicture {
     uint8_t *d_pack;               /* compact wire form of this slot's ME + OIS records (svt_amd_*_fetch_compact_async) */
     size_t pack_bytes;
     hipEvent_t ev_ready;           /* recorded after the planes of this slot were built: lanes on other streams wait on it */
-    LaunchMark ev_me, ev_ois;      /* recorded behind the kernels that wrote d_me_out / d_ois_out: a consumer on another lane's stream (the mode decision reading the
-                                    * records where they are) waits on them through svt_amd_records_wait.  Borrowed, not owned: one launch hands the same marker to
-                                    * every slot it wrote.  Lanes run on different host threads: read and written under mark_lock only */
-    int mark_lock;
-    uint32_t me_lcus, ois_lcus;    /* LCUs of the picture whose records the buffers hold (0: none yet, or only a part of the picture: every upload into the slot resets
-                                    * them; read / written across host threads with acquire / release) */
-    /* which LCUs of the slot's CURRENT picture the range launches since the last upload have covered - a bit per LCU (8K: 8,160), so bands may arrive in any order and
-     * from several lanes (me_cov_lock); me_lcus is set when every LCU is covered */
-    uint64_t me_cov[128];
-    uint32_t me_cov_count;
-    int me_cov_lock;
-    hipEvent_t ev_md_read;         /* recorded behind a mode-decision kernel that reads d_me_out / d_ois_out in place: the next ME / OIS launch INTO the slot waits for it */
-    int md_read_pending;
+    SlotRecords rec;               /* which picture's ME / OIS records the buffers hold and who is ordered behind whom: slot_records.h, through context.hip only */
     uint16_t width, height;
     int      valid;
 };
@@ -126,10 +110,11 @@ struct SvtAmdContext {
     uint8_t *h_desc_ring;          /* pinned ring of launch descriptors (svt_amd_upload_descriptors) */
     hipEvent_t ev_desc[8];
     int desc_next;
-    /* Completion markers of this lane's ME / OIS launches (svt_amd_launch_mark_record): one record per launch, lent to every slot the launch wrote.
+    /* Completion markers of this lane's ME / OIS launches and of its kernels that read a slot's records in place (slot_mark_lend): one record per launch, lent to
+     * every slot the launch wrote.
      * INVARIANT: an entry is only ever re-recorded by this lane, later in this lane's stream order.  A waiter holding a reference from before the ring came
      * round (16 launches ago) therefore waits for a LATER point of the stream that wrote its records: longer than needed, never too little.  The ring lives
-     * as long as the lane: svt_amd_context_destroy clears every slot reference to it, behind the lane's synchronisation, before it destroys the events. */
+     * as long as the lane: svt_amd_context_destroy clears every slot reference to it, of all three kinds, behind the lane's synchronisation, before it destroys the events. */
     hipEvent_t ev_launch[16];
     int launch_next;
     unsigned long long mark_records, mark_waits; /* svt_amd_debug_launch_markers */
@@ -154,11 +139,15 @@ int svt_amd_ctx_scratch(SvtAmdContext *ctx, size_t bytes, uint8_t **out);
 /* context.hip: the device's view of a range inside a svt_amd_host_register'ed buffer, or nullptr */
 const void *svt_amd_registered_device_ptr(const void *h_ptr, size_t bytes);
 
-/* context.hip: the consumer side of DevPicture::ev_me (which == 0) / ev_ois (which == 1): the stream of `ctx` orders itself behind the launch that wrote the
- * slot's records.  No wait where that launch ran on this very lane (stream order holds already) or where there is nothing to wait for.  A batched consumer
- * passes `seen` (room for `cap` events) / `nseen`, zeroed once per call: a marker it has already waited on in this call is skipped, so a batch costs one wait
- * per distinct producing launch.  seen == nullptr: no memory. */
+/* context.hip: what a consumer of the records resident in a slot goes through (the mode decision, the source-based operations), in this order.
+ * svt_amd_slot_records: the device pointer of the slot's ME (which == 0) / OIS (which == 1) records, or nullptr unless the slot is in range, holds a picture of
+ * w x h and complete records of it.  It sets no error text: the caller refuses in its own words.
+ * svt_amd_records_wait: the stream of `ctx` orders itself behind the launch that wrote them (no wait where that ran on this very lane, or where there is nothing
+ * to wait for).  A batched consumer passes `seen` (room for `cap` events) / `nseen`, zeroed once per call: one wait per distinct producing launch.
+ * svt_amd_records_read_mark: behind the kernel that read them in place - the next ME / OIS launch INTO the slot from another lane orders itself behind it. */
+const void *svt_amd_slot_records(SvtAmdContext *root, int slot, int which, int w, int h);
 int svt_amd_records_wait(SvtAmdContext *ctx, DevPicture *s, int which, hipEvent_t *seen, int *nseen, int cap);
+int svt_amd_records_read_mark(SvtAmdContext *ctx, SvtAmdContext *root, int slot);
 
 void svt_amd_set_error(const char *fmt, ...);
 

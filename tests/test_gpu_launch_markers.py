@@ -1,4 +1,4 @@
-"""-m gpu: the completion markers of the ME / OIS launches (svt-hevc_amd/csrc/svt_amd_internal.h: SvtAmdContext::ev_launch, DevPicture::ev_me / ev_ois).  A launch
+"""-m gpu: the completion markers of the ME / OIS launches (svt-hevc_amd/csrc/svt_amd_internal.h: SvtAmdContext::ev_launch, DevPicture::rec).  A launch
 records ONE marker behind its kernels, whatever the number of pictures, and lends it to every slot it wrote; a consumer that reads the records where they lie
 (svt_amd_source_ops_batch_launch with me = ois = NULL) waits once per distinct producing launch of another lane and not at all for its own lane.  The counters of
 svt_amd_debug_launch_markers are the deterministic part; the byte comparisons against the same chain on one lane with a synchronisation after every call are
@@ -127,12 +127,20 @@ class World:
             ok(lib, rc)
             rc, first = self.consume(root, w, h, [0], ois_from_slot=False)
             ok(lib, rc)
+            upload(lib, root, 0, self.frames[w, h][0])                 # slot 0 once more, its ME records an LCU a launch as the two-lane tests write them
+            for b in range(S.lcu_count(w, h)):
+                ok(lib, lib.svt_amd_me_picture_range_launch(root, C.byref(p), 0, (C.c_int * 2)(1, 1), b, b + 1))
+                ok(lib, lib.svt_amd_synchronize(root))
+            ok(lib, lib.svt_amd_ois_picture_launch(root, C.byref(op), 0))
+            ok(lib, lib.svt_amd_synchronize(root))
+            rc, bands = self.consume(root, w, h, [0])
+            ok(lib, rc)
             # other pictures leave other records, or the comparisons below could not tell a stale slot from a written one
             self.fill(root, w, h, stale=True)
             rc, other = self.consume(root, w, h, range(N))
             ok(lib, rc)
             assert other != got
-            self.want[w, h] = dict(all=got, first=first)
+            self.want[w, h] = dict(all=got, first=first, bands=bands)
         return self.want[w, h]
 
     def busy(self, lane):
@@ -276,3 +284,111 @@ def test_upload_into_a_slot_clears_its_references(lib, world):
         ok(lib, lib.svt_amd_synchronize(world.a))
     finally:
         luma.free()
+
+
+# ---- bands of one picture from two lanes: the marker chain (svt-hevc_amd/csrc/slot_records.h: slot_chain_behind) ----
+# 128x64: two LCUs, the smallest picture that has two bands; 192x64: three.  A band is one LCU.  The lane of band k is lanes[k]; lane A's first launch sits behind
+# the busy batch, so a consumer that is ordered behind the last band's lane only reads LCUs lane A has not written yet.
+BAND_SIZES = [(128, 64), (192, 64)]
+A_FIRST = {(128, 64): "ab", (192, 64): "aba"}
+B_FIRST = {(128, 64): "ba", (192, 64): "baa"}   # lane B's band first, lane A's behind the busy batch complete the picture
+
+
+def band(lib, ctx, p, b, slot=0):
+    ok(lib, lib.svt_amd_me_picture_range_launch(ctx, C.byref(p), slot, (C.c_int * 2)(slot + 1, slot + 1), b, b + 1))
+
+
+def launch_bands(lib, world, w, h, lanes):
+    """fresh pictures over stale records, then band k of slot 0 on lanes[k] -> the lane of the last band.  Asserts per launch: one record on the launching lane and
+    none on the other; one wait (the chain) where the slot's marker is the other lane's, i.e. where the previous band was the other lane's, else none."""
+    p, _ = controls(w, h)
+    world.fill(world.root, w, h, stale=True)
+    world.fill(world.a, w, h, stale=False)
+    world.busy(world.a)
+    ctx = dict(a=world.a, b=world.b)
+    for b, name in enumerate(lanes):
+        before = {k: markers(lib, c) for k, c in ctx.items()}
+        band(lib, ctx[name], p, b)
+        other = "b" if name == "a" else "a"
+        r, wt = markers(lib, ctx[name])
+        assert (r - before[name][0], wt - before[name][1]) == (1, int(b > 0 and lanes[b - 1] != name)), (b, lanes)
+        assert markers(lib, ctx[other]) == before[other], (b, lanes)
+    return ctx[lanes[-1]], ctx["b" if lanes[-1] == "a" else "a"]
+
+
+@pytest.mark.parametrize("w,h", BAND_SIZES)
+@pytest.mark.parametrize("lanes", [A_FIRST, B_FIRST], ids=["a_first", "b_first"])
+def test_bands_from_two_lanes_chain_their_markers(lib, world, w, h, lanes):
+    """the lane of the last band holds the order of all of them: OIS and the consumer there wait for nothing, a consumer on the other lane once per kind of record"""
+    want = world.reference(w, h)["bands"]
+    _, op = controls(w, h)
+    last, other = launch_bands(lib, world, w, h, lanes[w, h])
+    r0, w0 = markers(lib, last)
+    ok(lib, lib.svt_amd_ois_picture_launch(last, C.byref(op), 0))      # a P picture: it reads the slot's ME records, whose marker is this lane's own
+    assert markers(lib, last) == (r0 + 1, w0)
+    rc, got = world.consume(last, w, h, [0])
+    ok(lib, rc)
+    assert markers(lib, last) == (r0 + 1, w0)
+    assert got == want
+    w0 = markers(lib, other)[1]
+    rc, got = world.consume(other, w, h, [0])
+    ok(lib, rc)
+    assert markers(lib, other)[1] - w0 == 2                             # the ME and the OIS records both carry the last lane's markers
+    assert got == want
+    for c in (world.a, world.b):
+        ok(lib, lib.svt_amd_synchronize(c))
+
+
+@pytest.mark.parametrize("w,h", BAND_SIZES)
+def test_ois_on_the_other_lane_waits_for_the_me_marker(lib, world, w, h):
+    """all bands chained onto lane A; the P picture's OIS on lane B reads them: one wait at that launch, then one (the ME records) in B's consumer"""
+    want = world.reference(w, h)["bands"]
+    _, op = controls(w, h)
+    last, other = launch_bands(lib, world, w, h, B_FIRST[w, h])
+    assert last == world.a
+    w0 = markers(lib, other)[1]
+    ok(lib, lib.svt_amd_ois_picture_launch(other, C.byref(op), 0))
+    assert markers(lib, other)[1] - w0 == 1
+    rc, got = world.consume(other, w, h, [0])
+    ok(lib, rc)
+    assert markers(lib, other)[1] - w0 == 2
+    assert got == want
+    for c in (world.a, world.b):
+        ok(lib, lib.svt_amd_synchronize(c))
+
+
+@pytest.mark.parametrize("w,h", BAND_SIZES)
+def test_partial_coverage_is_refused_until_the_other_lane_completes_it(lib, world, w, h):
+    """all bands but the last on lane A: the consumer is refused and waits for nothing; the last band from lane B, and it is accepted"""
+    want = world.reference(w, h)["bands"]
+    p, op = controls(w, h)
+    n = S.lcu_count(w, h)
+    launch_bands(lib, world, w, h, "a" * (n - 1))
+    w0 = markers(lib, world.b)[1]
+    rc, _ = world.consume(world.b, w, h, [0], expect=BAD_PARAM)
+    assert rc == BAD_PARAM and lib.svt_amd_last_error().startswith(R.ENTRY.encode() + b": job 0: slot 0 holds no complete ME records"), lib.svt_amd_last_error()
+    assert markers(lib, world.b)[1] == w0
+    band(lib, world.b, p, n - 1)
+    assert markers(lib, world.b)[1] - w0 == 1                           # the chain
+    ok(lib, lib.svt_amd_ois_picture_launch(world.b, C.byref(op), 0))
+    rc, got = world.consume(world.b, w, h, [0])
+    ok(lib, rc)
+    assert markers(lib, world.b)[1] - w0 == 1
+    assert got == want
+    for c in (world.a, world.b):
+        ok(lib, lib.svt_amd_synchronize(c))
+
+
+def test_whole_picture_launches_chain_to_nothing(lib, world):
+    """slot 0 holds a part of its picture's records and lane A's marker, slots 1 .. 4 whole records and lane A's marker: a full-picture launch and a batch launch
+    into them on lane B replace what the markers stood for, and wait for nothing"""
+    w, h = BAND_SIZES[0]
+    p, _ = controls(w, h)
+    launch_bands(lib, world, w, h, "a")
+    ok(lib, lib.svt_amd_me_batch_launch(world.a, me_jobs(p, range(1, N)), N - 1))
+    r0, w0 = markers(lib, world.b)
+    ok(lib, lib.svt_amd_me_picture_launch(world.b, C.byref(p), 0, (C.c_int * 2)(1, 1)))
+    ok(lib, lib.svt_amd_me_batch_launch(world.b, me_jobs(p, range(N)), N))
+    assert markers(lib, world.b) == (r0 + 2, w0)
+    for c in (world.a, world.b):
+        ok(lib, lib.svt_amd_synchronize(c))

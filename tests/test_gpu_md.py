@@ -246,74 +246,140 @@ def test_md_encode_picture_reads_the_ois_records_the_front_half_left_in_hbm(prod
         lib.svt_amd_context_destroy(ctx)
 
 
+class InPlaceWorld:
+    """a root and `lanes` lanes over four slots; a reference B picture (416x240, CHROMA_MODE_FULL LCUs) in slot 1 between its references; lanes[0] LAUNCHES motion
+    estimation and open-loop intra search of it (nothing is fetched: its kernels may still run when another lane's call arrives); every other lane gets a picture
+    object of its own.  call(i, me, ois, slot): svt_amd_md_encode_picture_inter on lanes[i] -> (rc, decisions)."""
+
+    def __init__(self, lib, lanes):
+        import torch
+        from gpu_util import upload, default_params
+        from test_oracle_md_golden import inter_inputs
+        sig(lib)
+        vp = C.c_void_p
+        lib.svt_amd_md_encode_picture_inter.restype = C.c_int
+        lib.svt_amd_md_encode_picture_inter.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+        lib.svt_amd_encdec_picture_set_inter.restype = C.c_int
+        lib.svt_amd_encdec_picture_set_inter.argtypes = [vp] * 5
+        lib.svt_amd_context_fork.argtypes = [vp, C.POINTER(vp)]
+        lib.svt_amd_me_picture_range_launch.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_uint32]
+        lib.svt_amd_ois_picture_launch.argtypes = [vp, vp, C.c_int]
+        lib.svt_amd_me_picture_fetch.argtypes = [vp, C.c_int, vp]
+        lib.svt_amd_ois_picture_fetch.argtypes = [vp, C.c_int, vp]
+        self.lib = lib
+        g = np.load(os.path.join(S.GOLDEN_DIR, "md_bref_motion_416x240_m8.npz"))
+        k = 0
+        w, h = int(g["pic"][k]["width"]), int(g["pic"][k]["height"])
+        self.nl = nl = S.lcu_count(w, h)
+        self.root, self.lanes, self.pics = vp(), [vp() for _ in range(lanes)], [vp() for _ in range(lanes)]
+        assert lib.svt_amd_context_create(0, w, (h + 7) & ~7, 4, C.byref(self.root)) == 0, lib.svt_amd_last_error()
+        try:
+            for lane in self.lanes:
+                assert lib.svt_amd_context_fork(self.root, C.byref(lane)) == 0, lib.svt_amd_last_error()
+            lane_a = self.lanes[0]
+            frames = [S.gen_luma("motion", w, h, t, 7) for t in range(3)]
+            for sl, f in enumerate(frames):
+                upload(lib, lane_a, sl, f)
+            self.mp = default_params(w, h, num_lists=2, temporal_layer_index=1, cu8x8_mode=0)
+            self.refs = (C.c_int * 2)(0, 2)
+            op = S.OisParams()
+            op.luma_width, op.luma_height, op.ois_th_set, op.temporal_layer_index = w, h, 1, 1
+            self.me_launch()
+            assert lib.svt_amd_ois_picture_launch(lane_a, C.byref(op), 1) == 0, lib.svt_amd_last_error()
+            self.P, self.lcus, cost = np.ascontiguousarray(g["pic"][k:k + 1]), np.ascontiguousarray(g["lcu"][k]), np.ascontiguousarray(g["cost"][k])
+            self.src = [np.ascontiguousarray(g[n][k]) for n in ("src_y", "src_cb", "src_cr")]
+            self.X, _, self.tmvp, rr, planes = inter_inputs(g, k)
+            self.dev = [[torch.from_numpy(a).cuda() for a in pl] for pl in planes]
+            torch.cuda.synchronize()
+            rs = [S.RefPicture(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), r.strideY, r.strideC, r.originX, r.originY, r.width, r.height) for d, r in zip(self.dev, rr)]
+            for lane, pic in zip(self.lanes[1:], self.pics[1:]):
+                assert lib.svt_amd_encdec_picture_create(lane, w, h, 1, C.byref(pic)) == 0, lib.svt_amd_last_error()
+                assert lib.svt_amd_encdec_picture_set_inter(lane, pic, C.byref(rs[0]), C.byref(rs[1]), cost.ctypes.data) == 0, lib.svt_amd_last_error()
+        except BaseException:
+            self.close()
+            raise
+
+    def me_launch(self):
+        lib = self.lib
+        assert lib.svt_amd_me_picture_range_launch(self.lanes[0], C.byref(self.mp), 1, self.refs, 0, self.nl) == 0, lib.svt_amd_last_error()
+
+    def call(self, i, me, ois, slot):
+        src, tmvp = self.src, self.tmvp
+        out = np.zeros(self.nl, S.MD_LCU_OUT_DTYPE)
+        rc = self.lib.svt_amd_md_encode_picture_inter(self.lanes[i], self.pics[i], self.P.ctypes.data, self.X.ctypes.data, self.lcus.ctypes.data, src[0].ctypes.data, src[0].shape[1],
+                                                      src[1].ctypes.data, src[2].ctypes.data, src[1].shape[1], ois, slot, me, slot, tmvp.ctypes.data if tmvp is not None else None,
+                                                      out.ctypes.data, None, None)
+        return rc, out
+
+    def from_host(self, i):
+        """the synchronised expectation: the records fetched on the producing lane and passed as host arrays"""
+        lib = self.lib
+        me_h, ois_h = np.zeros(self.nl, S.ME_LCU_DTYPE), np.zeros(self.nl, S.OIS_LCU_DTYPE)
+        assert lib.svt_amd_me_picture_fetch(self.lanes[0], 1, me_h.ctypes.data) == 0 and lib.svt_amd_ois_picture_fetch(self.lanes[0], 1, ois_h.ctypes.data) == 0, lib.svt_amd_last_error()
+        rc, out = self.call(i, me_h.ctypes.data, ois_h.ctypes.data, 0)
+        assert rc == 0, lib.svt_amd_last_error()
+        return out
+
+    def close(self):
+        self.dev = None
+        for lane, pic in zip(self.lanes, self.pics):
+            if pic:
+                self.lib.svt_amd_encdec_picture_destroy(lane, pic)
+        for c in self.lanes + [self.root]:
+            if c:
+                self.lib.svt_amd_context_destroy(c)
+
+
 def test_md_of_a_b_picture_reads_me_and_ois_records_another_lane_left_in_hbm(product):
     """me == NULL and ois == NULL: motion estimation and open-loop intra search of the picture were LAUNCHED (not fetched) on another lane's stream; the mode decision
-    reads their records where they are, ordered behind those kernels by the slot's events (ADVICE r3).  Same decisions as with the records passed as host arrays;
+    reads their records where they are, ordered behind those kernels by the slot's markers (ADVICE r3).  Same decisions as with the records passed as host arrays;
     a slot that holds no such records is refused."""
-    import torch
-    from gpu_util import upload, default_params
-    from test_oracle_md_golden import inter_inputs
     lib = product
-    sig(lib)
-    vp = C.c_void_p
-    lib.svt_amd_md_encode_picture_inter.restype = C.c_int
-    lib.svt_amd_md_encode_picture_inter.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
-    lib.svt_amd_encdec_picture_set_inter.restype = C.c_int
-    lib.svt_amd_encdec_picture_set_inter.argtypes = [vp] * 5
-    lib.svt_amd_context_fork.argtypes = [vp, C.POINTER(vp)]
-    lib.svt_amd_me_picture_range_launch.argtypes = [vp, vp, C.c_int, vp, C.c_uint32, C.c_uint32]
-    lib.svt_amd_ois_picture_launch.argtypes = [vp, vp, C.c_int]
-    lib.svt_amd_me_picture_fetch.argtypes = [vp, C.c_int, vp]
-    lib.svt_amd_ois_picture_fetch.argtypes = [vp, C.c_int, vp]
-    g = np.load(os.path.join(S.GOLDEN_DIR, "md_bref_motion_416x240_m8.npz"))   # a reference B picture: CHROMA_MODE_FULL LCUs
-    k = 0
-    w, h = int(g["pic"][k]["width"]), int(g["pic"][k]["height"])
-    nl = S.lcu_count(w, h)
-    root, lane_a, lane_b, pic = vp(), vp(), vp(), vp()
-    assert lib.svt_amd_context_create(0, w, (h + 7) & ~7, 4, C.byref(root)) == 0, lib.svt_amd_last_error()
+    wd = InPlaceWorld(lib, 2)
     try:
-        assert lib.svt_amd_context_fork(root, C.byref(lane_a)) == 0 and lib.svt_amd_context_fork(root, C.byref(lane_b)) == 0, lib.svt_amd_last_error()
-        frames = [S.gen_luma("motion", w, h, t, 7) for t in range(3)]
-        for sl, f in enumerate(frames):
-            upload(lib, lane_a, sl, f)
-        mp = default_params(w, h, num_lists=2, temporal_layer_index=1, cu8x8_mode=0)
-        refs = (C.c_int * 2)(0, 2)
-        op = S.OisParams()
-        op.luma_width, op.luma_height, op.ois_th_set, op.temporal_layer_index = w, h, 1, 1
-        # lane A: launches only - its kernels may still run when lane B's call arrives
-        assert lib.svt_amd_me_picture_range_launch(lane_a, C.byref(mp), 1, refs, 0, nl) == 0, lib.svt_amd_last_error()
-        assert lib.svt_amd_ois_picture_launch(lane_a, C.byref(op), 1) == 0, lib.svt_amd_last_error()
-        P, lcus, cost = np.ascontiguousarray(g["pic"][k:k + 1]), np.ascontiguousarray(g["lcu"][k]), np.ascontiguousarray(g["cost"][k])
-        src = [np.ascontiguousarray(g[n][k]) for n in ("src_y", "src_cb", "src_cr")]
-        X, _, tmvp, rr, planes = inter_inputs(g, k)
-        dev = [[torch.from_numpy(a).cuda() for a in pl] for pl in planes]
-        torch.cuda.synchronize()
-        rs = [S.RefPicture(d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), r.strideY, r.strideC, r.originX, r.originY, r.width, r.height) for d, r in zip(dev, rr)]
-        assert lib.svt_amd_encdec_picture_create(lane_b, w, h, 1, C.byref(pic)) == 0, lib.svt_amd_last_error()
-        assert lib.svt_amd_encdec_picture_set_inter(lane_b, pic, C.byref(rs[0]), C.byref(rs[1]), cost.ctypes.data) == 0, lib.svt_amd_last_error()
-
-        def call(me, ois, slot):
-            out = np.zeros(nl, S.MD_LCU_OUT_DTYPE)
-            rc = lib.svt_amd_md_encode_picture_inter(lane_b, pic, P.ctypes.data, X.ctypes.data, lcus.ctypes.data, src[0].ctypes.data, src[0].shape[1], src[1].ctypes.data,
-                                                     src[2].ctypes.data, src[1].shape[1], ois, slot, me, slot, tmvp.ctypes.data if tmvp is not None else None, out.ctypes.data,
-                                                     None, None)
-            return rc, out
-        rc, in_place = call(None, None, 1)                  # lane B: records of slot 1 read where lane A's kernels leave them
+        rc, in_place = wd.call(1, None, None, 1)            # lane B: records of slot 1 read where lane A's kernels leave them
         assert rc == 0, lib.svt_amd_last_error()
-        me_h, ois_h = np.zeros(nl, S.ME_LCU_DTYPE), np.zeros(nl, S.OIS_LCU_DTYPE)
-        assert lib.svt_amd_me_picture_fetch(lane_a, 1, me_h.ctypes.data) == 0 and lib.svt_amd_ois_picture_fetch(lane_a, 1, ois_h.ctypes.data) == 0, lib.svt_amd_last_error()
-        rc, from_host = call(me_h.ctypes.data, ois_h.ctypes.data, 0)
-        assert rc == 0, lib.svt_amd_last_error()
+        from_host = wd.from_host(1)
         compare_md(in_place, from_host, "records read in place vs the same records as host arrays")   # (every tested leaf; untested leaves hold no decision)
-        assert int(in_place["tested"].sum()) >= nl
-        rc, _ = call(None, None, 3)                         # a slot no motion estimation / intra search has written
+        assert int(in_place["tested"].sum()) >= wd.nl
+        rc, _ = wd.call(1, None, None, 3)                   # a slot no motion estimation / intra search has written
         assert rc != 0
-        del dev
-        lib.svt_amd_encdec_picture_destroy(lane_b, pic)
     finally:
-        for c in (lane_a, lane_b, root):
-            if c:
-                lib.svt_amd_context_destroy(c)
+        wd.close()
+
+
+def test_md_readers_of_one_slot_chain_their_read_markers(product):
+    """two lanes read slot 1's records in place, then lane A launches into the slot twice.  The first reader's marker is the slot's first: no chain.  The second
+    waits once more than the first (the chain: its marker then stands for both readers), lane A once (behind the readers), and not again: the marker is spent."""
+    lib = product
+    vp, ull = C.c_void_p, C.c_ulonglong
+    lib.svt_amd_debug_launch_markers.restype = C.c_int
+    lib.svt_amd_debug_launch_markers.argtypes = [vp, C.POINTER(ull), C.POINTER(ull)]
+
+    def markers(ctx):
+        r, w = ull(), ull()
+        assert lib.svt_amd_debug_launch_markers(ctx, C.byref(r), C.byref(w)) == 0
+        return r.value, w.value
+    wd = InPlaceWorld(lib, 3)
+    try:
+        a, b1, b2 = wd.lanes
+        rc, first = wd.call(1, None, None, 1)
+        assert rc == 0, lib.svt_amd_last_error()
+        assert markers(b1) == (0, 2)                        # the ME and the OIS launch of lane A; a read marker is no record of a producing launch
+        rc, second = wd.call(2, None, None, 1)
+        assert rc == 0, lib.svt_amd_last_error()
+        assert markers(b2) == (0, 3)
+        from_host = wd.from_host(1)
+        compare_md(first, from_host, "first reader in place vs the same records as host arrays")
+        compare_md(second, from_host, "second reader in place vs the same records as host arrays")
+        ra, wa = markers(a)
+        wd.me_launch()
+        assert markers(a) == (ra + 1, wa + 1)
+        wd.me_launch()
+        assert markers(a) == (ra + 2, wa + 1)
+        assert lib.svt_amd_synchronize(a) == 0, lib.svt_amd_last_error()
+    finally:
+        wd.close()
 
 
 def test_md_encode_picture_rejects_what_it_does_not_cover(product):
