@@ -985,11 +985,12 @@ MD_FN uint64_t md_intra_full_luma_cost_pslice(const SvtAmdMdPicture *P, int cuSi
     const uint64_t rate = (uint64_t)P->rates.transSubDivFlagBits[5 - lg] + P->rates.lumaCbfBits[(ycbf & 1) * 5 + 1] + fastLumaRate;
     return (yDistortion0 << 8) + (((lambda * coeffRate + lambda * rate) + (1u << 22)) >> 23);
 }
-/* the scaling PerformFullLoop applies to the luma coefficient bits of partial-frequency units (:4575-4590; N2_TH by QP) */
+/* the scaling PerformFullLoop applies to the luma coefficient bits of partial-frequency units (:4575-4590; N2_TH by QP).  The reference's table
+ * N2_TH[NUM_QPS = 52] has 51 initialisers, so its entry for QP 51 is 0: at QP 51 the luma coefficients of a partial-frequency unit cost nothing. */
 MD_FN uint64_t md_pf_coeff_bits(int pfMode, int qp, uint64_t yCoeffBits)
 {
     if (pfMode == 1)
-        return yCoeffBits * (uint64_t)(qp < 10 ? 3 : (qp < 29 ? 2 : 1));
+        return yCoeffBits * (uint64_t)(qp < 10 ? 3 : (qp < 29 ? 2 : (qp < 51 ? 1 : 0)));
     return yCoeffBits;
 }
 /* DerivePartialFrequencyN2Flag (:2243-2260), levels 0 / 1 */

@@ -33,6 +33,9 @@ CASES = {
     "b_416x240_m7": ("motion", 416, 240, 10, 7, ["-encMode", "7", "-pred-struct", "2", "-hierarchical-levels", "2"], 17, 260),
     "noise_320x256_m6": ("noise", 320, 256, 3, 11, ["-encMode", "6", "-pred-struct", "1", "-q", "22"], 13, 240),
     # encMode 4 P pictures: rdoqPmCoreMethod == EB_PMCORE, which re-decides luma blocks only - the chroma pair is unchanged
+    # saturated chroma (Cb and Cr hold only 0 and 255) at the ends of the QP range: the chroma QP table's first and last entries
+    "xc_binary_192x128_m7_q0": ("xc_binary", 192, 128, 6, 3, ["-encMode", "7", "-pred-struct", "2", "-hierarchical-levels", "2", "-q", "0"], 7, 260),
+    "xc_stripes_200x136_m7_q51": ("xc_stripes", 200, 136, 6, 3, ["-encMode", "7", "-pred-struct", "2", "-hierarchical-levels", "2", "-q", "51"], 7, 260),
     "pm_p_416x240_m4": ("motion", 416, 240, 4, 7, ["-encMode", "4", "-pred-struct", "0"], 41, 240),
 }
 
@@ -42,8 +45,8 @@ def run_case(name):
     with tempfile.TemporaryDirectory() as td:
         yuv, dump = os.path.join(td, "clip.yuv"), os.path.join(td, "cl.dump")
         S.write_clip(yuv, kind, w, h, n, seed)
-        cmd = [S.REF_APP, "-i", yuv, "-w", str(w), "-h", str(h), "-n", str(n), "-q", "32", "-asm", "0",
-               "-b", os.path.join(td, "out.265")] + args
+        cmd = [S.REF_APP, "-i", yuv, "-w", str(w), "-h", str(h), "-n", str(n), "-asm", "0",
+               "-b", os.path.join(td, "out.265")] + ([] if "-q" in args else ["-q", "32"]) + args
         subprocess.run(cmd, env=dict(os.environ, SVT_REF_CHROMALOOP_DUMP=dump, SVT_REF_CHROMALOOP_STRIDE=str(stride)),
                        check=True, stdout=subprocess.DEVNULL)
         recs = np.fromfile(dump, dtype=REC)

@@ -71,6 +71,15 @@ CASES = {
                                                           "-bit-depth", "10"]),
     "p_motion_416x240_m3": ("motion", 416, 240, 3, 7, ["-encMode", "3", "-pred-struct", "0", "-hierarchical-levels", "0", "-intra-period", "-1", "-q", "28"]),
     "b_noise_320x192_m4": ("noise", 320, 192, 5, 13, ["-encMode", "4", "-pred-struct", "2", "-hierarchical-levels", "2", "-intra-period", "-1", "-q", "40"]),
+    # saturated clips at the ends of the QP range ("xc_": luma and chroma hold only 0 and 255; 10 bit: 0..3 and 1020..1023): at -q 0 levels in the thousands through the
+    # quantiser, the de-quantiser's clip and the inverse transforms, at -q 51 the largest dead zone - units with and without coefficients side by side
+    "i_xc_binary_192x128_m9_q0": ("xc_binary", 192, 128, 1, 3, ["-encMode", "9", "-intra-period", "0", "-q", "0"]),
+    "i_xc_stripes_200x136_m9_q51": ("xc_stripes", 200, 136, 3, 3, ["-encMode", "9", "-intra-period", "0", "-q", "51"]),
+    "i10_xc_binary_192x128_m9_q0": ("xc_binary10", 192, 128, 1, 3, ["-encMode", "9", "-intra-period", "0", "-q", "0", "-bit-depth", "10"]),
+    # (low delay P on the stripes kind: on xc_binary and xc_whiteblack every unit of the P pictures keeps luma coefficients even at QP 51)
+    "p_xc_stripes_200x136_m7_q51": ("xc_stripes", 200, 136, 4, 3, ["-encMode", "7", "-pred-struct", "0", "-hierarchical-levels", "0", "-intra-period", "-1", "-q", "51"]),
+    "b_xc_whiteblack_192x128_m6_q0": ("xc_whiteblack", 192, 128, 5, 3, ["-encMode", "6", "-pred-struct", "2", "-hierarchical-levels", "2", "-intra-period", "-1", "-q", "0"]),
+    "sao_i_xc_stripes_200x136_m9_q51": ("xc_stripes", 200, 136, 3, 3, ["-encMode", "9", "-intra-period", "0", "-q", "51"]),
     "p10_motion_320x192_m7": ("motion10", 320, 192, 3, 7, ["-encMode", "7", "-pred-struct", "0", "-hierarchical-levels", "0", "-intra-period", "-1", "-q", "32", "-bit-depth", "10"]),
 }
 

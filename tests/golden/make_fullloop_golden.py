@@ -42,6 +42,11 @@ CASES = {
     # candidate's context model before and after the call.  encMode 7: plain quantiser; encMode 3: PM-core on every picture
     "cabac_i_motion_416x240_m7": ("motion", 416, 240, 1, 7, ["-encMode", "7", "-q", "30"], 37, 300),
     "cabac_i_noise_320x256_m7": ("noise", 320, 256, 1, 11, ["-encMode", "7", "-q", "36"], 41, 220),
+    # saturated clips at the ends of the QP range: residuals of +-255, levels in the thousands at -q 0 (the escape binarisation's long codes in the coefficient bits,
+    # the distortion sums near the top of 32 bits), the largest dead zone at -q 51
+    "xc_binary_192x128_m9_q0": ("xc_binary", 192, 128, 4, 3, ["-encMode", "9", "-pred-struct", "0", "-q", "0"], 7, 260),
+    "xc_stripes_200x136_m9_q51": ("xc_stripes", 200, 136, 4, 3, ["-encMode", "9", "-pred-struct", "0", "-q", "51"], 7, 260),
+    "cabac_i_xc_binary_192x128_m7_q0": ("xc_binary", 192, 128, 1, 3, ["-encMode", "7", "-q", "0"], 11, 300),
     "cabac_pm_ib_motion_416x240_m3": ("motion", 416, 240, 5, 7, ["-encMode", "3", "-pred-struct", "2", "-hierarchical-levels", "2", "-q", "30"], 211, 300),
 }
 

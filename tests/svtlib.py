@@ -285,6 +285,13 @@ def load_product():
 
 def gen_luma(kind, w, h, t, seed):
     """One 8-bit luma frame of clip `kind` at time t."""
+    if kind == "xc_blocks":
+        # 16x16 blocks of 0 and 255, new ones every frame: a white unit among black ones is predicted black by every intra mode, so whole units carry a
+        # flat residual of 255 - the largest DC coefficient there is (32640), which at a high QP de-quantises past the top of 16 bits
+        blocks = np.random.default_rng(seed * 100 + t).integers(0, 2, ((h + 15) // 16, (w + 15) // 16))
+        return (np.kron(blocks, np.ones((16, 16), np.int64))[:h, :w] * 255).astype(np.uint8)
+    if kind.startswith("xc_"):  # the other saturated-chroma kinds take their luma from the x_ kind of the same name
+        kind = "x_" + kind[3:]
     if kind in ("x_whiteblack", "x_binary", "x_stripes"):
         # saturated clips: every sample is 0 or 255, so block SADs reach the largest value their fields hold (64x64: 2 * 32 * 64 * 255) and
         # the period-2 patterns send the half-pel filters past both ends of the sample range
@@ -349,11 +356,30 @@ def gen_chroma(w, h, t):
             np.clip(np.floor(cr), 0, 255).astype(np.uint8))
 
 
+def gen_chroma_of(kind, w, h, t, seed):
+    """The chroma planes of clip `kind` at time t: the mild sines of gen_chroma for every kind but the xc_ ones, whose Cb and Cr hold only 0 and 255 -
+    8x8 blocks, column stripes, row stripes and a one-sample checkerboard in turn, Cr one step ahead of Cb, so that chroma residuals saturate in both signs."""
+    if not kind.startswith("xc_"):
+        return gen_chroma(w, h, t)
+    x = np.arange(w // 2)[None, :]
+    y = np.arange(h // 2)[:, None]
+    rng = np.random.default_rng(seed * 100 + 50 + t)
+
+    def plane(k):
+        if k % 4 == 0:
+            blocks = rng.integers(0, 2, ((h // 2 + 7) // 8, (w // 2 + 7) // 8))
+            bits = np.kron(blocks, np.ones((8, 8), np.int64))[:h // 2, :w // 2]
+        else:
+            bits = ((x + t) & 1) + 0 * y if k % 4 == 1 else ((y + t) & 1) + 0 * x if k % 4 == 2 else (x + y + t) & 1
+        return (bits * 255).astype(np.uint8)
+    return plane(t), plane(t + 1)
+
+
 def write_clip(path, kind, w, h, n, seed):
     with open(path, "wb") as f:
         for t in range(n):
             f.write(gen_luma(kind, w, h, t, seed).tobytes())
-            cb, cr = gen_chroma(w, h, t)
+            cb, cr = gen_chroma_of(kind, w, h, t, seed)
             f.write(cb.tobytes())
             f.write(cr.tobytes())
 
@@ -363,7 +389,7 @@ def write_clip10(path, kind, w, h, n, seed):
     rng = np.random.default_rng(seed + 1000)
     with open(path, "wb") as f:
         for t in range(n):
-            cb, cr = gen_chroma(w, h, t)
+            cb, cr = gen_chroma_of(kind, w, h, t, seed)
             for plane in (gen_luma(kind, w, h, t, seed), cb, cr):
                 lsb = rng.integers(0, 4, plane.shape, dtype=np.uint16)
                 f.write(((plane.astype(np.uint16) << 2) | lsb).astype("<u2").tobytes())
@@ -377,7 +403,7 @@ def write_clip10_compressed(path, kind, w, h, n, seed):
     rng = np.random.default_rng(seed + 2000)
     with open(path, "wb") as f:
         for t in range(n):
-            cb, cr = gen_chroma(w, h, t)
+            cb, cr = gen_chroma_of(kind, w, h, t, seed)
             for plane in (gen_luma(kind, w, h, t, seed), cb, cr):
                 f.write(plane.tobytes())
             for size in (w * h // 4, w * h // 16, w * h // 16):

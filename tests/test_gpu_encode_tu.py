@@ -15,6 +15,43 @@ vp, u32 = C.c_void_p, C.c_uint32
 EUNIT = np.dtype([("src_off", "<i4"), ("rec_off", "<i4"), ("qp", "u1"), ("slice_type", "u1"), ("pad", "u1", 2), ("dz_offset", "<u4")])
 
 
+def tu_inputs(size, bps):
+    """the units of one (size, bit depth) case: random source against a prediction whose residual energy varies per unit, QPs over the whole range [0, 52); below
+    them saturated units - source 0 or max against a prediction of max or 0 as flats of both signs, column and row stripes of both phases and the one-sample
+    checkerboard of both phases - each kind at QP 0, at QP 51 and at QPs drawn from [0, 52)"""
+    rng = np.random.default_rng(size * 3 + bps)
+    W, H = 256 + 8, 128
+    dt, maxv = (np.uint8, 255) if bps == 1 else (np.uint16, 1023)
+    src = rng.integers(0, maxv + 1, (H, W)).astype(dt)
+    # prediction: source plus a residual whose energy varies per unit (flat / small / large)
+    pos = [(x, y) for y in range(0, H, size) for x in range(0, 256, size)]
+    pred = src.astype(np.int64)
+    for k, (x, y) in enumerate(pos):
+        amp = [0, 2, 12, 90][k % 4] * (4 if bps == 2 else 1)
+        pred[y:y + size, x:x + size] += rng.integers(-amp, amp + 1, (size, size))
+    pred = np.clip(pred, 0, maxv).astype(dt)
+    units = np.zeros(len(pos), EUNIT)
+    for k, (x, y) in enumerate(pos):
+        units[k] = (y * W + x, y * W + x, int(rng.integers(0, 52)), int(rng.integers(0, 3)), (0, 0), int(rng.integers(1, 20)) if k % 7 == 0 else 0)
+    # the saturated units: 32 of them (8 kinds x 4 QPs), in whole rows of units below the random ones
+    per_row = 256 // size
+    rows = -(-32 // per_row)
+    xs, ys = np.meshgrid(np.arange(size), np.arange(size))
+    kinds = [0 * xs, 0 * xs + 1, xs & 1, ~xs & 1, ys & 1, ~ys & 1, (xs + ys) & 1, ~(xs + ys) & 1]
+    sat_src, sat_units, sat_pos = np.zeros((rows * size, W), dt), np.zeros(rows * per_row, EUNIT), []
+    sat_pred = rng.integers(0, maxv + 1, (rows * size, W)).astype(dt)   # the columns right of the units stay as they are, as above
+    sat_src[:] = sat_pred
+    for k in range(rows * per_row):
+        x, y = (k % per_row) * size, (k // per_row) * size
+        bits = kinds[k % 8]
+        sat_src[y:y + size, x:x + size] = bits * maxv
+        sat_pred[y:y + size, x:x + size] = (1 - bits) * maxv
+        qp = (0, 51, int(rng.integers(0, 52)), int(rng.integers(0, 52)))[(k // 8) % 4]
+        sat_units[k] = ((H + y) * W + x, (H + y) * W + x, qp, int(rng.integers(0, 3)), (0, 0), int(rng.integers(1, 20)) if k % 7 == 0 else 0)
+        sat_pos.append((x, H + y))
+    return np.vstack([src, sat_src]), np.vstack([pred, sat_pred]), np.concatenate([units, sat_units]), pos + sat_pos, W
+
+
 @pytest.mark.parametrize("size,bps", [(4, 1), (8, 1), (16, 1), (32, 1), (8, 2), (16, 2), (32, 2)])
 def test_encode_tu_matches_oracle_composition(product, gpu_ctx, oracle, size, bps):
     import torch
@@ -24,21 +61,8 @@ def test_encode_tu_matches_oracle_composition(product, gpu_ctx, oracle, size, bp
     oracle.svt_oracle_unified_quantize.restype = None
     oracle.svt_oracle_recon_tu.argtypes = [C.c_int, u32, C.c_int, C.c_int, vp, vp, u32, vp, u32]
     oracle.svt_oracle_recon_tu.restype = None
-    rng = np.random.default_rng(size * 3 + bps)
-    W, H = 256 + 8, 128
-    dt, maxv = (np.uint8, 255) if bps == 1 else (np.uint16, 1023)
-    src = rng.integers(0, maxv + 1, (H, W)).astype(dt)
-    # prediction: source plus a residual whose energy varies per unit (flat / small / large)
-    pos = [(x, y) for y in range(0, H, size) for x in range(0, 256, size)]
+    src, pred, units, pos, W = tu_inputs(size, bps)
     n = len(pos)
-    pred = src.astype(np.int64)
-    for k, (x, y) in enumerate(pos):
-        amp = [0, 2, 12, 90][k % 4] * (4 if bps == 2 else 1)
-        pred[y:y + size, x:x + size] += rng.integers(-amp, amp + 1, (size, size))
-    pred = np.clip(pred, 0, maxv).astype(dt)
-    units = np.zeros(n, EUNIT)
-    for k, (x, y) in enumerate(pos):
-        units[k] = (y * W + x, y * W + x, int(rng.integers(4, 52)), int(rng.integers(0, 3)), (0, 0), int(rng.integers(1, 20)) if k % 7 == 0 else 0)
     # --- device
     to_t = (lambda a: torch.from_numpy(a.view(np.int16)).cuda()) if bps == 2 else (lambda a: torch.from_numpy(a).cuda())
     d_src, d_rec = to_t(src), to_t(pred.copy())

@@ -89,8 +89,43 @@ def test_fullloop_matches_reference_golden(product, gpu_ctx, name):
             check_out(g, i, as_struct(outs[j]), qs[j, :size * size].reshape(size, size), rs[j, :size * size].reshape(size, size), name)
 
 
+def saturated_residuals(size):
+    """residuals at the bound of 8-bit content, source 0 or 255 against a prediction of 255 or 0: flats of both signs, column and row stripes, the one-sample
+    checkerboard and a single sample of either sign"""
+    x, y = np.meshgrid(np.arange(size), np.arange(size))
+    one = np.zeros((size, size), np.int64)
+    one[size // 2 + 1, size - 1] = 255
+    kinds = [np.full((size, size), 255), np.full((size, size), -255), 255 - 510 * (x & 1), 255 - 510 * (y & 1), 255 - 510 * ((x + y) & 1), one, -one]
+    return [k.astype(np.int16) for k in kinds]
+
+
+def saturated_candidates(seed):
+    """appended to the random draws of the two tests below: every saturated residual at every size, each at QP 0, at QP 51 and at two QPs drawn from [0, 52);
+    the other inputs drawn as the random candidates' are"""
+    rng = np.random.default_rng(seed)
+    ins, ress = [], []
+    for size in (8, 16, 32, 64):
+        for res in saturated_residuals(size):
+            for qp in (0, 51, int(rng.integers(0, 52)), int(rng.integers(0, 52))):
+                fin = FullLoopIn()
+                fin.size, fin.qp, fin.slice_type = size, qp, int(rng.integers(0, 3))
+                fin.pf_mode = int(rng.integers(0, 2)) if size >= 16 else 0
+                if len(ins) % 3 == 0:
+                    fin.pf_mode |= 2 << 16
+                fin.cand_type, fin.intra_luma_mode = int(rng.integers(1, 3)), int(rng.integers(0, 35))
+                fin.full_lambda = int(rng.integers(1000, 4000000))
+                for j, v in enumerate(rng.integers(1000, 90000, 4)):
+                    fin.cbf_bits[j] = int(v)
+                fin.ycbf, fin.coeff_bits = int(rng.integers(0, 2)) << 7, int(rng.integers(0, 5000))
+                fin.dist[0], fin.dist[1] = int(rng.integers(0, 9000)), int(rng.integers(0, 9000))
+                ins.append(fin)
+                ress.append(res)
+    return ins, ress
+
+
 def test_fullloop_matches_oracle_random(product, gpu_ctx, oracle):
-    """Random residuals over every size / slice type / PF mode / candidate type / qp, incl. all-zero outcomes."""
+    """Random residuals over every size / slice type / PF mode / candidate type / qp, incl. all-zero outcomes; behind them the saturated residuals of
+    saturated_candidates, whose QPs cover [0, 52) with both ends at every size and kind."""
     oracle.svt_oracle_product_full_loop_luma.argtypes = [C.c_void_p] * 6
     oracle.svt_oracle_product_full_loop_luma.restype = None
     rng = np.random.default_rng(1)
@@ -115,6 +150,8 @@ def test_fullloop_matches_oracle_random(product, gpu_ctx, oracle):
             res = (np.add.outer(np.arange(size), np.arange(size)) * amp // size - amp // 2).astype(np.int16)
         ins.append(fin)
         ress.append(res)
+    sat_ins, sat_ress = saturated_candidates(101)
+    ins, ress = ins + sat_ins, ress + sat_ress
     outs, qs, rs = run_batch(product, gpu_ctx, cost, ins, ress)
     zero = nonzero = 0
     for k, (fin, res) in enumerate(zip(ins, ress)):
@@ -163,6 +200,8 @@ def test_fullloop_cabac_matches_oracle_random(product, gpu_ctx, oracle):
             res = (np.add.outer(np.arange(size), np.arange(size)) * amp // size - amp // 2).astype(np.int16)
         ins.append(fin)
         ress.append(res)
+    sat_ins, sat_ress = saturated_candidates(107)
+    ins, ress = ins + sat_ins, ress + sat_ress
     models0 = rng.integers(0, 126, (len(ins), 136)).astype(np.uint32)
     models = models0.copy()
     outs, qs, rs = run_batch(product, gpu_ctx, cost, ins, ress, models)

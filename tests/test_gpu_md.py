@@ -148,7 +148,13 @@ def test_md_of_p_and_b_pictures_matches_the_reference(product, name):
         lib.svt_amd_context_destroy(ctx)
 
 
-@pytest.mark.parametrize("name", [c for c in INTER_CASES if c.startswith(("b_motion", "bref_motion", "p_"))][:4])
+# the saturated fixtures (luma and chroma of 0 and 255 at the ends of the QP range) are where the matrix-core forward transforms come nearest to the bounds they leave the
+# matrix cores at, so where the equality of the two transform forms matters most
+BUTTERFLY_CASES = ["b_motion_416x240_m8", "bref_motion_416x240_m8", "p_motion_416x240_m8_ld", "p_objects_320x192_m8_ld",
+                   "b_xc_whiteblack_192x128_m8_q0", "bref_xc_whiteblack_192x128_m8_q0", "b_xc_binary_200x136_m8_q51", "bref_xc_binary_200x136_m8_q51"]
+
+
+@pytest.mark.parametrize("name", BUTTERFLY_CASES)
 def test_md_of_p_and_b_pictures_with_the_transforms_on_the_register_butterflies(product, name):
     """the full loops' 16x16 / 32x32 forward transforms run on the matrix cores (exact f16 x f16 -> f32 integer products) and fall back to the register butterflies for a
     unit outside the Estimate butterflies' wrap-free domain - which no fixture reaches by itself.  svt_amd_debug_md_force_butterflies sends EVERY unit down that path: the
@@ -452,7 +458,7 @@ def _check_source16(works, src16, w, h, tag):
             assert np.array_equal(works[i][nm].reshape(32, 32)[:lh // 2, :lw // 2], src16[p][y0 // 2:(y0 + lh) // 2, x0 // 2:(x0 + lw) // 2]), (tag, i, nm)
 
 
-@pytest.mark.parametrize("name", ["i_motion_416x240_m9", "i_tiles_motion_640x384_m9"])
+@pytest.mark.parametrize("name", ["i_motion_416x240_m9", "i_tiles_motion_640x384_m9", "i_xc_binary_192x128_m9_q0"])
 def test_md_encode_picture16_decides_on_the_8_msbs_and_encodes_the_10_bit_samples(product, oracle, name):
     lib = product
     sig(lib)
@@ -492,7 +498,8 @@ def test_md_encode_picture16_decides_on_the_8_msbs_and_encodes_the_10_bit_sample
         lib.svt_amd_context_destroy(ctx)
 
 
-@pytest.mark.parametrize("name", [c for c in INTER_CASES if c in ("b_motion_416x240_m8", "bref_motion_416x240_m8", "pref_motion_416x240_m8_ld", "bref_tiles_motion_640x384_m8")])
+@pytest.mark.parametrize("name", [c for c in INTER_CASES if c in ("b_motion_416x240_m8", "bref_motion_416x240_m8", "pref_motion_416x240_m8_ld", "bref_tiles_motion_640x384_m8",
+                                                                  "bref_xc_binary_200x136_m8_q51")])
 def test_md_encode_picture_inter16_decides_on_the_8_msbs_and_encodes_the_10_bit_samples(product, oracle, name):
     import torch
     from test_oracle_encodepass_golden import inter_oracle_fn

@@ -107,3 +107,35 @@ def test_uqiq_optional_branches_match_reference_function(oracle):
         hit["dc"] += int(u["shape"][0] == 3)
         hit["dz"] += int(u["dz_offset"][0] != 0)
     assert hit["dc"] > 50 and hit["dz"] > 100
+
+
+@pytest.mark.skipif(not os.path.exists(S.REF_SO), reason="oracle/_ref/libsvtref.so not built (needs /root/reference)")
+def test_uqiq_at_the_qp_ends_with_coefficients_at_the_int16_bounds_matches_reference_function(oracle):
+    """the sibling of the test above at the ends of both ranges, by construction and not by the odds of a draw: every QP of 0..3 and 49..51 at every size, bit depth
+    and slice type, on blocks that hold 32767, -32767 and -32768 (whole blocks of each, and all three mixed with zeros and small values) - the quantiser's products,
+    its clip to 16 bits and the de-quantiser's clip at the largest magnitudes they can meet"""
+    ref = C.CDLL(S.REF_SO)
+    ref.svt_ref_unified_quantize.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    ref.svt_ref_unified_quantize.restype = None
+    rng = np.random.default_rng(13)
+    count, clipped = 0, 0
+    for qp in (0, 1, 2, 3, 49, 50, 51):
+        for n in (4, 8, 16, 32):
+            mixed = rng.choice(np.array([32767, -32767, -32768, 0, 1, -1, 300], np.int64), (n, n))
+            mixed[0, 0], mixed[0, 1], mixed[1, 0] = 32767, -32768, -32767
+            for coeff in (np.full((n, n), 32767), np.full((n, n), -32767), np.full((n, n), -32768), mixed):
+                coeff = coeff.astype(np.int16)
+                for bit_depth in (8, 10):
+                    for slice_type in (0, 1, 2):
+                        u = np.zeros(1, UNIT)
+                        u["size"], u["qp"], u["bit_depth"], u["slice_type"] = n, qp, bit_depth, slice_type
+                        u["component"], u["temporal_layer"] = count % 3, count % 4 % 3
+                        u["dz_offset"] = 7 if count % 5 == 0 else 0
+                        wq, wr, gq, gr = (np.zeros((n, n), np.int16) for _ in range(4))
+                        wnz, coeff_ref = C.c_uint32(0), coeff.copy()
+                        ref.svt_ref_unified_quantize(u.ctypes.data, coeff_ref.ctypes.data, n, wq.ctypes.data, wr.ctypes.data, C.byref(wnz))
+                        gnz = oracle_call(oracle, u, coeff, gq, gr)
+                        assert gnz == wnz.value and np.array_equal(gq, wq) and np.array_equal(gr, wr), (qp, n, bit_depth, slice_type, u)
+                        count += 1
+                        clipped += int((np.abs(wq.astype(np.int32)) >= 32767).any() or (np.abs(wr.astype(np.int32)) >= 32767).any())
+    assert count == 7 * 4 * 4 * 2 * 3 and clipped > 0
