@@ -731,6 +731,128 @@ SVT_AMD_API int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmd
 /* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
 SVT_AMD_API size_t svt_amd_source_ops_bytes(uint16_t luma_width, uint16_t luma_height, int which);
 
+/*
+ * Batched mode-decision configuration: what ModeDecisionConfigurationKernel (Codec/EbModeDecisionConfigurationProcess.c:1905) with EarlyModeDecisionLcu
+ * (Codec/EbModeDecisionConfiguration.c:1059) derives for a P or B picture from the records of the stages before it - the picture signals, the aura status,
+ * the search method and the leaf list of every LCU (the lcu_md_mode, leaf_count, leaf_index and leaf_split fields of SvtAmdMdLcu) - for up to 256 pictures of
+ * ONE geometry per call, stream-ordered on the context's lane like svt_amd_source_ops_batch_launch: the call never blocks and never copies to the host, and it
+ * allocates at its first call only.  Pure integer logic on records that already lie in HBM; no plane is read.  A batch of one picture is the single-picture form.
+ * Job (all pointers DEVICE memory, read where the earlier batches wrote them):
+ *   me              SvtAmdMeLcuResult[lcus], or NULL: the records resident in picture slot cur_slot (the call waits, on the device, for the launches that
+ *                   wrote them; the slot has to hold complete records of a picture of the batch's size; a later ME launch into that slot from ANOTHER lane
+ *                   is the caller's to order behind this call, as for svt_amd_source_ops_batch_launch)
+ *   stats, detect   required: svt_amd_side_stats_batch_launch's block statistics and svt_amd_picture_detect_batch_launch's LCU records
+ *   sbo_lcu, sbo_pic   required: the two records of svt_amd_source_ops_batch_launch (want_qpm set: inter_complexity_min / max [0] are read)
+ *   pic_detect, noise_pic   required: the picture records of svt_amd_picture_detect_batch_launch and svt_amd_noise_detect_batch_launch
+ *   stationary_edge one byte per LCU (stationaryEdgeOverTimeFlag, the host's StationaryEdgeOverUpdateOverTimeLcu), or NULL - as the reference's NULL pointer:
+ *                   the clause of IsAvcPartitioningMode that reads it never holds
+ *   the scalars     the fields of the control sets the reference's host stages own, below.  slice_type is 1 (P) or 2 (B): the I-picture arm of DeriveLcuScore
+ *                   (:1596) has no restatement pinned on the reference and is OUT OF SCOPE - an I picture is refused
+ * The rules, restated as the reference has them (nothing is repaired; tests/mdc_numpy.py spells every width out):
+ *   picture signals sceneCaracteristicId and adjustMinQPFlag (:1949-1975), highIntraSlection (:212-240), the chroma QP offsets (SetSliceAndPictureChromaQpOffsets :112),
+ *                   tc / beta offset 0 (AdaptiveDlfParameterComputation :175), average_qp = the picture QP
+ *   aura_status     AuraDetection / AuraDetection64x64 (:791-939): B pictures, LCUs with a column on either side and a row below; 128 (INVALID_AURA_STATUS)
+ *                   everywhere else.  rightDist is assigned from topRDist (:888): the right neighbour's distortion is never read.  10 * cur and th * min are
+ *                   32-bit products
+ *   PICT_LCU_SWITCH pictures (depth_mode 0), DeriveLcuMdMode (:1826): ConfigureAdp (:1288), SetTargetBudgetOq (:1079), DeriveDefaultSegments (:942),
+ *                   IsAvcPartitioningMode (:1232), ComputeRefinementCost, DeriveLcuScore (:1596; the score of a partial LCU is the wrapping mean over its
+ *                   valid 8x8 units), PerformOutlierRemoval (:1736), DeriveOptimalBudgetPerLcu / SetLcuBudget (up to 101 passes), DeriveSearchMethod
+ *                   (:1360-1392).  Every EB_U32 expression wraps at 32 bits; a score threshold of -1 multiplies as 0xFFFFFFFF (:1431); the deviation is the
+ *                   SIGNED product ABS((EB_S32)(predictedCost - budget)) * 1000 (:1522), defined for pictures of up to 13,854 LCUs - larger ones are refused
+ *   leaf list       PICT_LCU_SWITCH: Forward85 / 84 / 8x816x16 / 16x16CuToModeDecisionLCU (:370-704) for the full and AVC methods; EarlyModeDecisionLcu for the
+ *                   open-loop methods - the 21 costs of depths 0..2 from the ME records (MdcInterCuRate :307; 64-bit), the 16 -> 32 and 32 -> 64 inter-depth
+ *                   decisions with their running group counters (EbHevcMdcInterDepthDecision :715), EbHevcRefinementPredictionLoop (:436) with
+ *                   EbHevcMdcRefinement (:82; the Pm3 arm tests Pm2, :232, as written), EbHevcForwardCuToModeDecision (:586); BDP and light-BDP LCUs:
+ *                   leaf_count 0.  PICT_FULL85 / PICT_FULL84 pictures (1, 2): the two fixed lists.  Depth modes 3..5: leaf_count 0 - those pictures do not
+ *                   go through the list.  Entries at and behind leaf_count are 0.
+ * Left to the host: the scalars, StationaryEdgeOverUpdateOverTimeLcu (Codec/EbSourceBasedOperationsProcess.c:1142) and SetDefaultDeltaQpRange (:609).
+ * Three stages in stream order - a wave per LCU (aura, AVC clause, score; stored - not added - into context-owned scratch), a workgroup per picture (the
+ * budgeting loop, every LCU's score in LDS), a wave per LCU (the leaf list: a lane per coded unit, the 85-unit masks as wave ballots, the list a compaction in
+ * MD-scan order).  No atomics, nothing to zero.  The arrays are DEVICE memory, both required, picture i of the batch at i times svt_amd_md_config_bytes(...)
+ * bytes of each.  Everything is checked before anything is queued: a NULL required pointer or array, a slice type other than 1 / 2, a temporal layer or
+ * hierarchical levels above 5, a class above 3, a depth mode above 5, a QP above 51, a picture of more than 13,854 LCUs or of more LCUs than the context was
+ * made for, me == NULL with a slot that is out of range, holds no picture, one of another size or no complete ME records return SVT_AMD_ERR_BAD_PARAM
+ * (svt_amd_last_error names the entry and the job), queue nothing and wait for nothing.
+ */
+#define SVT_AMD_MDC_MAX_LCUS 13854
+typedef struct SvtAmdMdcJob {
+    const SvtAmdMeLcuResult *me;            /* or NULL: cur_slot's; ppcs->meResults[lcu] (Codec/EbModeDecisionConfiguration.c:1015)           */
+    const SvtAmdPaLcuStats  *stats;         /* required: ppcs->variance[lcu][0], ->yMean[lcu][0] (:1684, :1691)                              */
+    const SvtAmdPaLcuDetect *detect;        /* required: sharpEdgeLcuFlag[lcu], edgeResultsPtr[lcu].edgeBlockNum (:1251, :1240)              */
+    const SvtAmdSboLcu      *sbo_lcu;       /* required: similarColocatedLcuArrayAllLayers, complexLcuArray, failingMotionLcuFlag, nonMovingIndexArray */
+    const SvtAmdSboPic      *sbo_pic;       /* required: grassPercentageInPicture, zzCostAverage, nonMovingIndexAverage, interComplexityMin / Max[0], ... */
+    const SvtAmdPaPicDetect *pic_detect;    /* required: logoPicFlag (:1265)                                                                 */
+    const SvtAmdNoisePic    *noise_pic;     /* required: picNoiseClass (:130, :1958, :1330)                                                  */
+    const uint8_t           *stationary_edge; /* [lcus] or NULL: lcuStatArray[lcu].stationaryEdgeOverTimeFlag (:1242)                        */
+    int32_t cur_slot;
+    uint8_t slice_type;                     /* pcs->sliceType: 1 P, 2 B                                                                      */
+    uint8_t temporal_layer_index;           /* pcs->temporalLayerIndex, 0..5                                                                 */
+    uint8_t hierarchical_levels;            /* ppcs->hierarchicalLevels, 0..5                                                                */
+    uint8_t is_used_as_reference;           /* ppcs->isUsedAsReferenceFlag                                                                   */
+    uint8_t depth_mode;                     /* ppcs->depthMode - 1: 0 PICT_LCU_SWITCH, 1 FULL85, 2 FULL84, 3 BDP, 4 LIGHT_BDP, 5 OPEN_LOOP      */
+    uint8_t enc_mode;                       /* pcs->encMode (SetTargetBudgetOq :1079)                                                        */
+    uint8_t resolution_class;               /* scs->inputResolution, 0..3                                                                    */
+    uint8_t qp;                             /* pcs->pictureQp, 0..51                                                                         */
+    uint8_t is_pan, is_tilt;                /* ppcs->isPan, ->isTilt                                                                         */
+    uint8_t noise_detection_th;             /* the noiseDetectionTh setting of svt_amd_noise_detect_batch_launch: class threshold 1 (0) or 3  */
+    uint8_t homogeneity_percentage;         /* ppcs->picHomogenousOverTimeLcuPercentage (:1959)                                              */
+    uint8_t frame_rate_30;                  /* (scs->staticConfig.frameRate >> 16) > 30 (:1684)                                              */
+    uint8_t cu8x8_mode;                     /* ppcs->cu8x8Mode (Codec/EbModeDecisionConfiguration.c:474)                                     */
+    uint8_t average_intensity;              /* ppcs->averageIntensity[0] (:1325)                                                             */
+    uint8_t ref_average_intensity[2];       /* the list-0 / list-1 reference objects' averageIntensity                                       */
+    uint8_t ref_intra_coded_area[2];        /* the reference objects' intraCodedArea and tmpLayerIdx: their test (:195) is overwritten ...   */
+    uint8_t ref_temporal_layer[2];
+    uint8_t ref_penalize_skip[2];           /* ... by the one of penalizeSkipflag (:221): only this pair is read                             */
+    uint8_t pad;                            /* 0 */
+    uint32_t lambda_sad;                    /* contextPtr->lambda: the SAD lambda of the picture's QP (Codec/EbModeDecisionConfiguration.c:1006) */
+    uint32_t split_flag_bits[2];            /* mdRateEstimationPtr->splitFlagBits[0] and [3] (:1044-1045)                                    */
+} SvtAmdMdcJob;                             /* 104 bytes */
+typedef struct SvtAmdMdcLcu {
+    uint8_t  leaf_count;                    /* the first 171 bytes: the head of SvtAmdMdLcu (MdcLcuData_t.leafCount, .leafDataArray[])        */
+    uint8_t  leaf_index[SVT_AMD_ME_PU_COUNT], leaf_split[SVT_AMD_ME_PU_COUNT];
+    uint8_t  lcu_md_mode;                   /* ppcs->lcuMdModeArray[lcu] (EB_LCU_DEPTH_MODE, Codec/EbDefinitions.h:1270); 0 unless PICT_LCU_SWITCH */
+    uint8_t  aura_status;                   /* lcuPtr->auraStatus: 0, 1 or 128 (INVALID_AURA_STATUS)                                         */
+    uint8_t  pred64;                        /* lcuPtr->pred64: EarlyModeDecisionLcu kept the 64x64 unit                                      */
+    uint8_t  avc_partitioning;              /* IsAvcPartitioningMode (:1232); 0 unless PICT_LCU_SWITCH                                       */
+    uint8_t  pad0;                          /* 0 */
+    uint32_t lcu_score;                     /* lcuScoreArray[lcu] as the budgeting loop leaves it (:1420); 0 unless PICT_LCU_SWITCH           */
+    uint8_t  lcu_cost;                      /* lcuCostArray[lcu]; 0 unless PICT_LCU_SWITCH                                                   */
+    uint8_t  pad[3];                        /* 0 */
+} SvtAmdMdcLcu;                             /* 184 bytes */
+typedef struct SvtAmdMdcPic {
+    uint8_t  scene_characteristic_id;       /* pcs->sceneCaracteristicId (:1949-1967)                                                        */
+    uint8_t  adjust_min_qp;                 /* pcs->adjustMinQPFlag (:1969)                                                                  */
+    uint8_t  high_intra_selection;          /* pcs->highIntraSlection (:212-240)                                                             */
+    int8_t   slice_cb_qp_offset, slice_cr_qp_offset; /* SetSliceAndPictureChromaQpOffsets (:112)                                             */
+    int8_t   tc_offset, beta_offset;        /* pcs->tcOffset, ->betaOffset: 0 (AdaptiveDlfParameterComputation :175-186)                     */
+    uint8_t  average_qp;                    /* ppcs->averageQp (:2079)                                                                       */
+    uint8_t  adp_depth_sensitive_picture_class; /* contextPtr->adpDepthSensitivePictureClass (ConfigureAdp :1288)                            */
+    uint8_t  adp_refinement_mode;           /* contextPtr->adpRefinementMode (ComputeRefinementCost)                                         */
+    uint8_t  number_of_segments;            /* contextPtr->numberOfSegments (DeriveDefaultSegments :942)                                     */
+    uint8_t  pad0;                          /* 0 */
+    uint32_t budget;                        /* contextPtr->budget (SetTargetBudgetOq :1079)                                                  */
+    uint32_t predicted_cost;                /* contextPtr->predictedCost after the last pass                                                 */
+    uint32_t lcu_min_score, lcu_max_score;  /* contextPtr->lcuMinScore, ->lcuMaxScore after PerformOutlierRemoval (:1736)                    */
+    int8_t   score_th[7];                   /* contextPtr->scoreTh after the last pass                                                       */
+    uint8_t  interval_cost[7];              /* contextPtr->intervalCost                                                                      */
+    uint8_t  iterations;                    /* passes of the budgeting loop, 1..101                                                          */
+    uint8_t  bdp_present, md_present;       /* pcs->bdpPresentFlag, ->mdPresentFlag (:1355-1390)                                             */
+    uint8_t  pad[3];                        /* 0 */
+} SvtAmdMdcPic;                             /* 48 bytes; everything from adp_depth_sensitive_picture_class on is 0 unless PICT_LCU_SWITCH */
+typedef struct SvtAmdMdcArrays {            /* DEVICE pointers, picture i of the batch at index i; both required */
+    SvtAmdMdcLcu *lcu;                      /* [n][lcus] */
+    SvtAmdMdcPic *picture;                  /* [n]       */
+} SvtAmdMdcArrays;
+SVT_AMD_API int svt_amd_md_config_batch_launch(SvtAmdContext *ctx, const SvtAmdMdcJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
+                                               const SvtAmdMdcArrays *out);
+#define SVT_AMD_MDC_LCU     0
+#define SVT_AMD_MDC_PICTURE 1
+/* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_md_config_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+/* Development aid (tools/md_config_time.py): the stages the launches of this process run from now on - bit 0 k_mdc_lcu, bit 1 k_mdc_budget, bit 2 k_mdc_leaves;
+ * 7 is the start value and the only one that gives complete records. */
+SVT_AMD_API void svt_amd_debug_md_config_stages(int mask);
+
 
 /* Device-side timing of the launches issued between begin/end on the context's
  * own stream (HIP events); used for roofline.achieved in bench.py. */

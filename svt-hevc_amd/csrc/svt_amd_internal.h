@@ -124,6 +124,7 @@ struct SvtAmdContext {
     void *d_detect;                /* descriptor table + per-picture reduction of svt_amd_picture_detect_batch_launch (detect_kernels.hip), allocated at its first call */
     void *d_noise;                 /* descriptor table + per-picture reduction of svt_amd_noise_detect_batch_launch (noise_kernels.hip), allocated at its first call */
     void *d_sbo;                   /* descriptor table + per-LCU / per-workgroup partials of svt_amd_source_ops_batch_launch (sbo_kernels.hip), allocated at its first call */
+    void *d_mdc;                   /* descriptor table + per-LCU scores and flags of svt_amd_md_config_batch_launch (mdc_kernels.hip), allocated at its first call */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
