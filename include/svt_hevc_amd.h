@@ -853,6 +853,127 @@ SVT_AMD_API size_t svt_amd_md_config_bytes(uint16_t luma_width, uint16_t luma_he
  * 7 is the start value and the only one that gives complete records. */
 SVT_AMD_API void svt_amd_debug_md_config_stages(int mask);
 
+/*
+ * Batched initial rate control: the look-ahead stage of InitialRateControlKernel (Codec/EbInitialRateControlProcess.c:849), the two per-LCU checks in front of it
+ * in the ME process (StationaryEdgeOverUpdateOverTimeLcuPart1 / Part2, Codec/EbMotionEstimationProcess.c:502, :554) and the final stationary-edge stage of
+ * SourceBasedOperationsKernel (StationaryEdgeOverUpdateOverTimeLcu, Codec/EbSourceBasedOperationsProcess.c:1142) - the stage the two blocks above leave to the
+ * host - for up to 256 pictures of ONE geometry per call, stream-ordered on the context's lane like svt_amd_md_config_batch_launch: the call never blocks and
+ * never copies to the host, and it allocates at its first call only.  Pure integer logic on records that already lie in HBM; no plane is read.  Its
+ * stationary_edge array is what SvtAmdMdcJob.stationary_edge takes, its picture record holds SvtAmdMdcJob's is_pan, is_tilt and homogeneity_percentage.
+ * Job (all pointers DEVICE memory):
+ *   me              SvtAmdMeLcuResult[lcus], or NULL: the records resident in picture slot cur_slot - meaning, waits and refusals as for SvtAmdMdcJob.me.  Read
+ *                   for P / B pictures and above temporal layer 0 (the only pictures whose rules read a vector or a distortion); an I picture of layer 0
+ *                   ignores me and cur_slot
+ *   stats           required: SvtAmdPaLcuStats[lcus] of the picture
+ *   the three look-ahead lists, walked BY THE CALLER as SvtAmdSboJob.zz is - the queue rules (below) are the caller's, tests/irc_numpy.py window_lists spells
+ *   them out.  Their entries may be arrays this same batch writes or arrays of earlier batches:
+ *     edge_checks[4], edge_detect[4], edge_count 0..4   the SvtAmdIrcChecks and SvtAmdPaLcuDetect arrays of the window entries whose edges count
+ *     hom_stats[16], hom_count 0..16                    the SvtAmdPaLcuStats arrays of the window entries the homogeneity sums run over
+ *     pan_motion[8], pan_count 0..8                     the SvtAmdIrcMotion records of the non-I pictures among the first MIN(8, framesInSw) queue entries
+ *   slice_type 0 I / 1 P / 2 B; temporal_layer_index <= hierarchical_levels <= 5; resolution_class 0..3; look_ahead: !endOfSequenceFlag && lookAheadDistance
+ *   != 0; frames_to_check: noFramesToCheck = MIN(2 * predStructPeriod + 1, framesInSw, lookAheadDistance), 1..17 (1 without a look-ahead)
+ * The rules, restated as the reference has them (nothing is repaired; tests/irc_numpy.py spells every width out).  "complete" is lcuParams->isCompleteLcu, "logo"
+ * lcuParams->potentialLogoLcu (Codec/EbSequenceControlSet.c:216-273):
+ *   check1, pm_check1   Part1 (:502), complete logo LCUs, 0 elsewhere: the four 32x32 variances (units 1..4), averageVar = sum >> 2, varOfVar = the int sum of
+ *                   the four (EB_S32) squared differences, converted to EB_U64, >> 2 (:527-530); check1 = varOfVar > 50000 && lowMotion, pm_check1 = varOfVar >
+ *                   1000; lowMotion: temporal layer 0, or |x| < 16 && |y| < 16 of meResults[lcu][0].xMvL0 / yMvL0 (EbHevcGetMv :431)
+ *   check2, low_dist_logo   Part2 (:554), with look_ahead only: low_dist_logo = B picture && meResults[lcu][0].distortionDirection[0].distortion < 64 * 64 * (5
+ *                   below class 2, else 2) on complete logo LCUs; check2 is assigned 1 unconditionally on the function's last line (:591) - 1 for EVERY LCU
+ *                   with look_ahead, the 0 of the EB_MEMSET in EdgeDetectionMeanLumaChroma16x16 without
+ *   motion          EbHevcDetectGlobalMotion (Codec/EbInitialRateControlProcess.c:218), P / B pictures, complete LCUs: the vector of the LCU against its left, top,
+ *                   right and bottom neighbour - 0 / 0 at the left / top picture edge and where originX + 128 > width / originY + 128 > height; an
+ *                   incomplete neighbour inside those bounds IS read - through CheckMvForPan, Tilt, PanHighAmp, TiltHighAmp (:30-116) with
+ *                   GLOBAL_MOTION_THRESHOLD[hierarchicalLevels][temporalLayerIndex] (Codec/EbDefinitions.h:1184) and LOW_AMPLITUDE_TH 64; yCurrentMv < 64 is a
+ *                   signed test, the products of two vectors are int.  is_pan_raw = totalPanLcus * 100 / totalCheckedLcus > 75, is_tilt_raw alike; no
+ *                   complete LCU or an I picture: everything 0.  CheckForNonUniformMotionVectorField (:135) stores nothing and is not restated
+ *   is_pan, is_tilt EbHevcUpdateGlobalMotionDetectionOverTime (:441) with look_ahead: over the first MIN(8, framesInSw) queue entries from the head - the picture
+ *                   itself - I pictures skipped and not counted: is_pan = non-I picture && checked > 0 && pan * 100 / checked > 75 over the entries'
+ *                   is_pan_raw; is_tilt is set to 0 and never set again; disableTmvpFlag never changes (its counter stays 0).  Without: the raw flags (:1020)
+ *   similar_edge_count, pm_similar_edge_count   EbHevcUpdateMotionFieldUniformityOverTime (:598) with EbHevcStationaryEdgeCountLcu (:394): the walk covers
+ *                   noFramesToCheck - 1 entries from the head (from index 0 when the head is the last queue index - not the start of
+ *                   EbHevcUpdateBeaInfoOverTime), stops in front of an end-of-sequence picture, and only entries with (pictureNumber & 3) == 0 count: at most 4
+ *                   of 16.  For an LCU with check1 && check2 (pm: pm_check1 && check2) every entry whose own check1 (pm_check1) is set adds its edge_cu bits
+ *   var_of_var_over_time, homogeneous_over_time, homogeneity_percentage   UpdateHomogeneityOverTime (:646): the same walk, stopping in front of a scene-change
+ *                   or end-of-sequence picture; the sums of the 64x64 variance and of its square - the int product of two promoted EB_U16, which does not
+ *                   overflow for the variances of 8-bit pictures (below 16,384) - are divided by noFramesToCheck - 1, NOT by the entries walked (both 0 when
+ *                   noFramesToCheck == 1); meanSqr - mean * mean in 64 bits, homogeneous: <= 4096; the percentage is (EB_U8)(count * 100 / lcuTotalCount).
+ *                   Without look_ahead: 0xFFFFFFFFFFFFFFFF, 0 and 0 (ResetHomogeneityStructures :729)
+ *   stationary_edge, pm_stationary_edge   StationaryEdgeOverUpdateOverTimeLcu with totalCheckedPictures = noFramesToCheck, with look_ahead only (0 without):
+ *                   slideWindowTh = totalCheckedPictures / 4 - 1 is unsigned - below 4 pictures no flag is ever set; 1 where check1 && check2 (pm_check1 &&
+ *                   check2) and at least 4 of the 16 counts exceed it; then three passes over the 3x3 window clamped at the picture edges: (a) a 1 whose
+ *                   window holds no other 1 is cleared (the in-place raster loop equals this gather: tests/test_irc_cpu.py), (b) a 0 on a logo LCU with
+ *                   check2 or incomplete becomes 2 next to a 1, (c) the same LCUs become 3 with more than three 2s in their window.  The PM plane uses the
+ *                   same gate in (b) and (c): pm_check1 does not enter it (:1339, :1369)
+ * Four stages in stream order - a wave per LCU (checks, votes; the workgroups' vote totals stored - not added - into context-owned scratch), a workgroup per
+ * picture (the motion record), a wave per LCU behind the first stage of EVERY picture (a lane per 16x16 unit and flavour, the homogeneity sums a lane per
+ * entry), a workgroup per picture (the passes with a byte per LCU in LDS, pan over time, the picture record).  No atomics, nothing to zero; every array is
+ * written by one kernel only.  The arrays are DEVICE memory, all required, picture i of the batch at i times svt_amd_initial_rc_bytes(...) bytes of each.
+ * Everything is checked before anything is queued: a NULL stats pointer or array, a count above its bound, a NULL entry below a count, a slice type above 2, a
+ * layer above the levels, levels above 5, a class above 3, frames_to_check outside 1..17, look_ahead 0 with a non-empty list or frames_to_check other than 1, a
+ * picture of more than 16,384 LCUs or of more LCUs than the context was made for, me == NULL (where it is read) with a slot that is out of range, holds no
+ * picture, one of another size or no complete ME records return SVT_AMD_ERR_BAD_PARAM (svt_amd_last_error names the entry and the job), queue nothing and
+ * wait for nothing.
+ */
+#define SVT_AMD_IRC_MAX_LCUS 16384
+typedef struct SvtAmdIrcChecks {
+    uint8_t check1;                         /* lcuStatArray[lcu].check1ForLogoStationaryEdgeOverTimeFlag (Codec/EbMotionEstimationProcess.c:532)   */
+    uint8_t pm_check1;                      /* .pmCheck1ForLogoStationaryEdgeOverTimeFlag (:539)                                                  */
+    uint8_t check2;                         /* .check2ForLogoStationaryEdgeOverTimeFlag (:591)                                                    */
+    uint8_t low_dist_logo;                  /* .lowDistLogo (:578)                                                                                */
+} SvtAmdIrcChecks;                          /* 4 bytes */
+typedef struct SvtAmdIrcMotion {
+    uint32_t total_checked_lcus, total_pan_lcus, total_tilt_lcus, total_pan_high_amp_lcus, total_tilt_high_amp_lcus; /* (Codec/EbInitialRateControlProcess.c:227-246) */
+    uint8_t  is_pan_raw, is_tilt_raw;       /* ppcs->isPan, ->isTilt as EbHevcDetectGlobalMotion leaves them (:342-353)                           */
+    uint8_t  pad[2];                        /* 0 */
+} SvtAmdIrcMotion;                          /* 24 bytes */
+typedef struct SvtAmdIrcLcu {
+    uint8_t  similar_edge_count[16];        /* cuStatArray[RASTER_SCAN_CU_INDEX_16x16_0 + i].similarEdgeCount (:415)                              */
+    uint8_t  pm_similar_edge_count[16];     /* .pmSimilarEdgeCount (:428)                                                                         */
+    uint64_t var_of_var_over_time;          /* lcuVarianceOfVarianceOverTime[lcu] (:712)                                                          */
+    uint8_t  homogeneous_over_time;         /* isLcuHomogeneousOverTime[lcu] (:714)                                                               */
+    uint8_t  motion_votes;                  /* bit 0 pan, 1 tilt, 2 pan high amplitude, 3 tilt high amplitude (:298-338); 0: incomplete LCU, I picture */
+    uint8_t  pad[6];                        /* 0 */
+} SvtAmdIrcLcu;                             /* 48 bytes */
+typedef struct SvtAmdIrcPic {
+    uint8_t  is_pan, is_tilt;               /* ppcs->isPan, ->isTilt when the picture leaves the stage (:487-506, :1020)                          */
+    uint8_t  homogeneity_percentage;        /* picHomogenousOverTimeLcuPercentage (:724)                                                          */
+    uint8_t  pad0;                          /* 0 */
+    uint16_t homogeneous_lcu_count;         /* countOfHomogeneousOverTime (:718)                                                                  */
+    uint16_t stationary_lcu_count[4];       /* LCUs whose stationary_edge byte is 0, 1, 2, 3                                                      */
+    uint8_t  pad[2];                        /* 0 */
+} SvtAmdIrcPic;                             /* 16 bytes */
+typedef struct SvtAmdIrcJob {
+    const SvtAmdMeLcuResult *me;            /* or NULL: cur_slot's */
+    const SvtAmdPaLcuStats  *stats;         /* required */
+    const SvtAmdIrcChecks   *edge_checks[4]; /* entries from edge_count on are not read */
+    const SvtAmdPaLcuDetect *edge_detect[4];
+    const SvtAmdPaLcuStats  *hom_stats[16]; /* entries from hom_count on are not read */
+    const SvtAmdIrcMotion   *pan_motion[8]; /* entries from pan_count on are not read */
+    int32_t cur_slot;
+    uint8_t edge_count, hom_count, pan_count;
+    uint8_t slice_type, temporal_layer_index, hierarchical_levels, resolution_class;
+    uint8_t look_ahead, frames_to_check;
+    uint8_t pad[3];                         /* 0 */
+} SvtAmdIrcJob;                             /* 288 bytes */
+typedef struct SvtAmdIrcArrays {            /* DEVICE pointers, picture i of the batch at index i; all required */
+    SvtAmdIrcChecks *checks;                /* [n][lcus] */
+    SvtAmdIrcMotion *motion;                /* [n]       */
+    SvtAmdIrcLcu    *lcu;                   /* [n][lcus] */
+    uint8_t *stationary_edge;               /* [n][lcus rounded up to a multiple of 64]: stationaryEdgeOverTimeFlag, 0..3; the tail 0 */
+    uint8_t *pm_stationary_edge;            /* the same of pmStationaryEdgeOverTimeFlag */
+    SvtAmdIrcPic    *picture;               /* [n]       */
+} SvtAmdIrcArrays;
+SVT_AMD_API int svt_amd_initial_rc_batch_launch(SvtAmdContext *ctx, const SvtAmdIrcJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
+                                                const SvtAmdIrcArrays *out);
+#define SVT_AMD_IRC_CHECKS        0
+#define SVT_AMD_IRC_MOTION        1
+#define SVT_AMD_IRC_LCU           2
+#define SVT_AMD_IRC_STATIONARY    3
+#define SVT_AMD_IRC_PM_STATIONARY 4
+#define SVT_AMD_IRC_PICTURE       5
+/* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_initial_rc_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+
 
 /* Device-side timing of the launches issued between begin/end on the context's
  * own stream (HIP events); used for roofline.achieved in bench.py. */

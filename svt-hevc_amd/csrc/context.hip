@@ -128,6 +128,8 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
         (void)hipFree(ctx->d_sbo);
     if (ctx->d_mdc)
         (void)hipFree(ctx->d_mdc);
+    if (ctx->d_irc)
+        (void)hipFree(ctx->d_irc);
     if (ctx->d_dbg)
         (void)hipFree(ctx->d_dbg);
     for (int i = 0; i < ctx->cap_stamps; i++) {

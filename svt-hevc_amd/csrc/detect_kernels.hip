@@ -180,12 +180,6 @@ __global__ __launch_bounds__(256) void k_chroma_hist_finish(const ChromaJobDev *
 
 /* ---------------------------------------------------------------- picture detectors ---------------------------------------------------------------- */
 
-/* lcuParams->potentialLogoLcu (Codec/EbSequenceControlSet.c:253-272): the comparisons are the reference's signed ones (lumaWidth - 3 * 64 may be negative) */
-__device__ __forceinline__ bool detect_logo_lcu(int ox, int oy, int width, int height, int cols, int rows)
-{
-    return ((ox >= width - cols * 64 || ox < cols * 64) && oy < rows * 64) || oy >= height - rows * 64;
-}
-
 /* contextPtr->grad[lcu][5 + k] (:3551-3594): y / cr / cb point at the means of the sixteen 16x16 units */
 __device__ __forceinline__ uint32_t detect_grad16(const uint8_t *y, const uint8_t *cr, const uint8_t *cb, int k)
 {
@@ -457,8 +451,8 @@ extern "C" int svt_amd_picture_detect_batch_launch(SvtAmdContext *ctx, const Svt
         d.pic = out->picture + i;
         d.red = d_red + i;
         /* INPUT_SIZE_576p_RANGE_OR_LOWER: 3 x 2 LCUs; below INPUT_SIZE_4K_RANGE: 7 x 4; 4K: 14 x 8 */
-        d.logo_cols = j.resolution_class == 0 ? 3 : j.resolution_class < 3 ? 7 : 14;
-        d.logo_rows = j.resolution_class == 0 ? 2 : j.resolution_class < 3 ? 4 : 8;
+        d.logo_cols = svt_amd_logo_cols(j.resolution_class);
+        d.logo_rows = svt_amd_logo_rows(j.resolution_class);
     }
     SVT_AMD_TRY(svt_amd_upload_descriptors(ctx, d_tab, tab, sizeof(DetectJobDev) * (size_t)num_jobs));
     /* the stages are ordered on the lane: a batch queued behind this one zeroes the reduction only after this one's finish kernel has read it */

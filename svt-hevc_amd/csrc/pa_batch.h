@@ -19,4 +19,13 @@ int svt_amd_batch_begin(SvtAmdContext *ctx, void **owned, size_t record_bytes, s
 int svt_amd_batch_wait_slot(SvtAmdContext *ctx, int slot);
 bool svt_amd_batch_run(const uint8_t *want, size_t stride, int num_jobs, int *begin, int *end);
 
+/* lcuParams->potentialLogoLcu (Codec/EbSequenceControlSet.c:253-272), shared by detect_kernels.hip and irc_kernels.hip: the map of the resolution class in LCUs,
+ * and the rule - the comparisons are the reference's signed ones (lumaWidth - 3 * 64 may be negative) */
+__host__ __device__ static inline int svt_amd_logo_cols(int resolution_class) { return resolution_class == 0 ? 3 : resolution_class < 3 ? 7 : 14; }
+__host__ __device__ static inline int svt_amd_logo_rows(int resolution_class) { return resolution_class == 0 ? 2 : resolution_class < 3 ? 4 : 8; }
+__device__ __forceinline__ bool detect_logo_lcu(int ox, int oy, int width, int height, int cols, int rows)
+{
+    return ((ox >= width - cols * 64 || ox < cols * 64) && oy < rows * 64) || oy >= height - rows * 64;
+}
+
 #endif

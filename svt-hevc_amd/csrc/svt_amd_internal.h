@@ -125,6 +125,7 @@ struct SvtAmdContext {
     void *d_noise;                 /* descriptor table + per-picture reduction of svt_amd_noise_detect_batch_launch (noise_kernels.hip), allocated at its first call */
     void *d_sbo;                   /* descriptor table + per-LCU / per-workgroup partials of svt_amd_source_ops_batch_launch (sbo_kernels.hip), allocated at its first call */
     void *d_mdc;                   /* descriptor table + per-LCU scores and flags of svt_amd_md_config_batch_launch (mdc_kernels.hip), allocated at its first call */
+    void *d_irc;                   /* descriptor table + per-LCU votes and flags, per-workgroup vote totals of svt_amd_initial_rc_batch_launch (irc_kernels.hip), allocated at its first call */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
