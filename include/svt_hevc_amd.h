@@ -974,6 +974,82 @@ SVT_AMD_API int svt_amd_initial_rc_batch_launch(SvtAmdContext *ctx, const SvtAmd
 /* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
 SVT_AMD_API size_t svt_amd_initial_rc_bytes(uint16_t luma_width, uint16_t luma_height, int which);
 
+/*
+ * Batched mode-decision LCU controls: the SvtAmdMdLcu records (below, "Device-resident mode decision") svt_amd_md_encode_picture* reads, assembled on the device from
+ * the records of the batches above - what integration/svt_md_fill.h:svt_md_fill_lcu reads out of the reference's control sets on the host - for up to 256 pictures
+ * of ONE geometry per call, stream-ordered on the context's lane like svt_amd_initial_rc_batch_launch: the call never blocks and never copies to the host, and it
+ * allocates at its first call only.  svt_amd_md_picture_set_controls hands such an array to the mode-decision call, which reads it in place.
+ * Job (all pointers DEVICE memory, read where the earlier batches wrote them):
+ *   mdc_lcu         SvtAmdMdcLcu[lcus] of svt_amd_md_config_batch_launch, or NULL.  Its first 171 bytes are the head of SvtAmdMdLcu and are copied; lcu_md_mode
+ *                   (kept under depth_mode 0 only, Codec/EbEncDecProcess.c:2893) and aura_status are read.  NULL is allowed with depth_mode 1 or 2 only
+ *                   (PICT_FULL85 / PICT_FULL84): the fixed leaf list is built here as k_mdc_leaves builds it (Forward85 / 84CuToModeDecisionLCU,
+ *                   Codec/EbModeDecisionConfiguration.c:370-484) and aura_status is 128 - the I pictures svt_amd_md_config_batch_launch refuses
+ *   stats, detect, sbo_lcu, sbo_pic   required: the records of svt_amd_side_stats_ / picture_detect_ / source_ops_batch_launch
+ *   irc_lcu, ac_energy   SvtAmdIrcLcu[lcus] of svt_amd_initial_rc_batch_launch and uint64_t[lcus][5] of svt_amd_side_stats_batch_launch: both, or both NULL -
+ *                   then every contouring_class is 0
+ *   stationary_edge uint8_t[lcus] of svt_amd_initial_rc_batch_launch, or NULL: all 0
+ *   sticky          uint8_t[lcus], or NULL: bit 0 cuStatArray[0].highLuma, bit 1 cuStatArray[0].highChroma as the caller's pool object carried them from earlier
+ *                   pictures (the note on cuStatArray[parent] in the source-ops block above); each is OR-ed with high_luma != 0 / high_chroma != 0
+ *   slice_type 0 I / 1 P / 2 B (no rule reads it); depth_mode in SvtAmdMdcJob's encoding, 0..5; chroma_level 0..5; resolution_class 0..3; tile_cols x tile_rows
+ *   uniformly spaced tiles, 1 .. the LCU columns / rows
+ * The rules, restated as the reference has them (nothing is repaired; tests/mdctl_numpy.py spells them out):
+ *   contouring_class[q]   DeriveContouringClass (Codec/EbModeDecisionConfiguration.c:395) of leaves 1, 22, 43, 64: 0 unless isLcuHomogeneousOverTime; on an edge LCU
+ *                   (isEdgeLcu, Codec/EbSequenceControlSet.c:210: first column or row, or originX > width - 64, originY > height - 64) 2 / 3 / 3 below 1024 / 2048 /
+ *                   3072 (ANTI_CONTOURING_TH_1, _2 and their unparenthesised sum), elsewhere 1 / 2 / 3 below 256 / 1024 / 2048; 64-bit comparisons of
+ *                   lcuYSrcEnergyCuArray[lcu][1 + q]
+ *   chroma_encode_mode   ConfigureChroma (Codec/EbModeDecisionProcess.c:383-437): cond0 stationary edge over time, cond1 homogeneous area && highChroma, cond2
+ *                   !highLuma, cond3 grass_percentage > 60 || aura_status == 1 || is_pan; level 0 full, 1 best, 2 cond0 || 1 || 2, 3 cond0 || 1, 4 cond2 || 3,
+ *                   5 cond0; 4:2:2 / 4:4:4 is always CHROMA_MODE_BEST (:435)
+ *   tile_left / _top / _right   ConfigureLcuEdgeInfo (Codec/EbPictureControlSet.c:36) over tileColStartLcu[c] = c * columns / tile_cols (:743), rows alike
+ *   the flags       as svt_md_fill_lcu: is_complete (EbSequenceControlSet.c:206), complexity_status_2, restrict_intra_global_motion ((is_pan || is_tilt) &&
+ *                   non_moving_index < 2 && y_mean[0] < 50, Codec/EbEncDecProcess.c:2890), skip_small_cu (aura_status 0, no stationary edge), cmplx_noise
+ *                   (cmplx_status == 4), variance_below_200, edge_block, no_stop_split (isolated_non_homogeneous, or aura_status 1 below class 3)
+ * One stage - a wave per LCU: the head as words, a lane per byte of the tail, the record built in LDS and stored once as aligned words.  No atomics, nothing to
+ * zero.  Every byte of SvtAmdMdLcu[n][lcus] is written (pads 0), none behind it.  Everything is checked before anything is queued: a NULL required pointer or
+ * output array, mdc_lcu == NULL with a depth mode other than 1 / 2, exactly one of irc_lcu / ac_energy, a slice type above 2, a chroma level above 5, a class above
+ * 3, a depth mode above 5, a tile count of 0 or above the LCU columns / rows, a non-zero pad, a picture of more than 16,384 LCUs or of more LCUs than the context
+ * was made for, num_jobs outside 1..256 return SVT_AMD_ERR_BAD_PARAM (svt_amd_last_error names the entry and the job), queue nothing and wait for nothing.
+ */
+#define SVT_AMD_MDCTL_MAX_LCUS 16384
+struct SvtAmdMdLcu;
+typedef struct SvtAmdMdCtlJob {
+    const SvtAmdMdcLcu      *mdc_lcu;       /* or NULL (depth_mode 1 / 2): pcs->mdcLcuArray[lcu] (integration/svt_md_fill.h:60), lcuPtr->auraStatus, ppcs->lcuMdModeArray */
+    const SvtAmdPaLcuStats  *stats;         /* required: ppcs->variance[lcu][0], ->yMean[lcu][0] (Codec/EbCodingLoop.c:3866, EbEncDecProcess.c:2890)            */
+    const SvtAmdPaLcuDetect *detect;        /* required: edgeResultsPtr[lcu].edgeBlockNum, lcuHomogeneousAreaArray[lcu] (Codec/EbModeDecisionProcess.c:389, :395) */
+    const SvtAmdSboLcu      *sbo_lcu;       /* required: complexLcuArray, cmplxStatusLcu, lcuIsolatedNonHomogeneousAreaArray, nonMovingIndexArray, highLuma / highChroma */
+    const SvtAmdSboPic      *sbo_pic;       /* required: grassPercentageInPicture (:397)                                                                        */
+    const SvtAmdIrcLcu      *irc_lcu;       /* with ac_energy, or NULL: isLcuHomogeneousOverTime[lcu] (Codec/EbModeDecisionConfiguration.c:404)                 */
+    const uint64_t          *ac_energy;     /* with irc_lcu, or NULL: [lcus][5] lcuYSrcEnergyCuArray[lcu][0..4] (:409-426)                                      */
+    const uint8_t           *stationary_edge; /* [lcus] or NULL: lcuStatArray[lcu].stationaryEdgeOverTimeFlag (Codec/EbModeDecisionProcess.c:394)              */
+    const uint8_t           *sticky;        /* [lcus] or NULL: bit 0 cuStatArray[0].highLuma, bit 1 .highChroma of the pool object (:395-396)                   */
+    uint8_t slice_type;                     /* 0 I, 1 P, 2 B                                                                                                    */
+    uint8_t depth_mode;                     /* ppcs->depthMode in the numbers of SvtAmdMdcJob.depth_mode: 0 PICT_LCU_SWITCH, 1 FULL85, 2 FULL84, ... 5 OPEN_LOOP   */
+    uint8_t chroma_level;                   /* ModeDecisionContext_t.chromaLevel, 0..5 (:407-432)                                                               */
+    uint8_t resolution_class;               /* scs->inputResolution, 0..3 (Codec/EbFullLoop.c:1445)                                                             */
+    uint8_t is_pan, is_tilt;                /* ppcs->isPan, ->isTilt (SvtAmdIrcPic)                                                                             */
+    uint8_t color_format_422_or_444;        /* pcs->colorFormat >= EB_YUV422 (:435)                                                                             */
+    uint8_t pad0;                           /* 0 */
+    uint16_t tile_cols, tile_rows;          /* ppcs->tileColumnCount, ->tileRowCount (Codec/EbPictureControlSet.c:743-746)                                      */
+    uint8_t pad[4];                         /* 0 */
+} SvtAmdMdCtlJob;                           /* 88 bytes */
+SVT_AMD_API int svt_amd_md_controls_batch_launch(SvtAmdContext *ctx, const SvtAmdMdCtlJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
+                                                 struct SvtAmdMdLcu *out);
+#define SVT_AMD_MDCTL_LCU 0
+/* bytes ONE picture takes in array `which`; 0 for an unknown `which`.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_md_controls_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+/* What the mode-decision call learns about a bound device array (svt_amd_md_picture_set_controls) without reading it on the host: one record per picture */
+typedef struct SvtAmdMdCtlCheck {
+    uint32_t bad_leaf_count;                /* LCUs whose leaf_count is outside 1..85                                          */
+    uint32_t bad_leaf_list;                 /* LCUs whose leaf list (its first MIN(leaf_count, 85) entries) is not strictly ascending or holds an index above 84 */
+    uint32_t md_mode[16];                   /* LCUs by lcu_md_mode; values above 15 count in bin 15                            */
+    uint32_t bad_chroma;                    /* LCUs whose chroma_encode_mode is neither 1 nor 2                                */
+    uint32_t tiles;                         /* LCUs with tile_left && tile_top                                                 */
+    uint32_t first_bad;                     /* the first LCU the call refuses, 0xFFFFFFFF: none                                */
+    uint32_t first_kind;                    /* of that LCU: 0 leaf_count, 1 leaf list, 2 not decided by ModeDecisionLcu (P / B calls only) */
+} SvtAmdMdCtlCheck;                         /* 88 bytes */
+/* debug / test: that record of n DEVICE records under SvtAmdMdPicture.depth_mode, for an I (inter 0) or a P / B call; blocking */
+SVT_AMD_API int svt_amd_debug_md_controls_check(SvtAmdContext *ctx, const struct SvtAmdMdLcu *d_lcus, int n, int depth_mode, int inter, SvtAmdMdCtlCheck *out);
+
 
 /* Device-side timing of the launches issued between begin/end on the context's
  * own stream (HIP events); used for roofline.achieved in bench.py. */
@@ -2229,7 +2305,9 @@ SVT_AMD_API int svt_amd_md_picture_supported(const SvtAmdMdPicture *P);
  * caller's inter-row padding too - stride * (rows - 1) + width bytes from src_y / src_cb / src_cr must be readable (an encoder's padded picture buffer is;
  * a plane assembled from separately allocated rows must be passed with a stride that fails the test, or copied first).
  * Round 6: the call is two kernels on the context's stream - the decisions of every LCU (wavefront on the device), then the encode pass of every LCU from the work
- * records the first left in HBM. */
+ * records the first left in HBM.
+ * lcus == NULL: the controls are the DEVICE array svt_amd_md_picture_set_controls bound to `pic` for this call - read in place, no upload, no host loop over
+ * the LCUs; without a binding the call is refused as before. */
 SVT_AMD_API int svt_amd_md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus,
                                           const uint8_t *src_y, uint32_t stride_y, const uint8_t *src_cb, const uint8_t *src_cr,
                                           uint32_t stride_c, const SvtAmdOisLcuResult *ois, int ois_slot, const SvtAmdCabacCost *cost,
@@ -2261,6 +2339,15 @@ SVT_AMD_API int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncD
 SVT_AMD_API int svt_amd_md_picture_supported_inter(const SvtAmdMdPicture *P, const SvtAmdMdInter *X);
 /* 1 when every one of the n LCUs is decided by ModeDecisionLcu with luma-only candidates (the per-LCU half of the two checks above) */
 SVT_AMD_API int svt_amd_md_lcus_supported(const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus, int n);
+/* Binds a DEVICE array of the picture object's LCU count (svt_amd_md_controls_batch_launch's output, or any array of that layout) as the controls of the NEXT
+ * svt_amd_md_encode_picture[_inter][16] call on `pic`, and of that call only: the call consumes the binding whether it succeeds or refuses.  That call must pass
+ * lcus == NULL; one that passes host lcus as well is refused and drops the binding.  d_lcus == NULL drops a binding.  The array must stay valid until the blocking
+ * call returns.  Written on the context the call runs on, stream order suffices; written on another lane, ordering it is the caller's
+ * (svt_amd_lane_event_record / _wait), as for every raw device pointer here.  The call then runs a check kernel over the array first (SvtAmdMdCtlCheck above), copies
+ * that one record to the host and synchronises once, refuses what the host loop refuses - in the same words, naming the first offending LCU - and points the
+ * mode-decision kernel at the array.  A picture object with a rank rectangle (svt_amd_encdec_picture_set_rect) is refused with a bound array: the tile-border check
+ * of that path reads host records. */
+SVT_AMD_API int svt_amd_md_picture_set_controls(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLcu *d_lcus);
 /* debug: stage clocks of the mode-decision kernel (16 shader-clock sums per LCU, accumulated over the picture object's later calls; the first call
  * switches the collection on) - see svt-hevc_amd/csrc/md_kernels.hip */
 SVT_AMD_API int svt_amd_debug_md_profile(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, unsigned long long *out);

@@ -52,6 +52,8 @@ static void svt_md_fill_picture(SvtAmdMdPicture *P, const SequenceControlSet_t *
     memcpy(&P->rates, md->mdRateEstimationPtr, sizeof(P->rates));
 }
 
+/* Restated on the device by svt_amd_md_controls_batch_launch (svt-hevc_amd/csrc/mdctl_kernels.hip), which assembles the same records from the records the batched
+ * stages leave in HBM; tests/golden/mdctl_*.npz pin that entry on what this function gives.  The binding keeps using this function. */
 static void svt_md_fill_lcu(SvtAmdMdLcu *L, const SequenceControlSet_t *scs, const PictureControlSet_t *pcs, const LargestCodingUnit_t *lcuPtr,
                             const ModeDecisionContext_t *md)
 {

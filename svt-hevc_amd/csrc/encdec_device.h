@@ -50,6 +50,8 @@ struct SvtAmdEncDecPicture {
     size_t refp_bytes[3];
     /* the mode decision's part (md_kernels.hip): neighbour maps, source planes, per-LCU arrays; allocated by the first svt_amd_md_encode_picture */
     struct SvtAmdMdState *md;
+    /* svt_amd_md_picture_set_controls: the DEVICE SvtAmdMdLcu array the next mode-decision call on the object reads in place; that call clears it */
+    const SvtAmdMdLcu *md_bound_lcus;
     /* recorded behind every picture-level call that writes the picture's stages (encode pass, mode decision + encode pass, deblocking, SAO, an exchange that fills it):
      * a reader on another context's stream - svt_amd_encdec_picture_import - orders itself behind it; `written`: the object holds an encoded picture at all */
     hipEvent_t ev_written;

@@ -2892,7 +2892,8 @@ struct SvtAmdMdState {
     int n_retired;
 };
 static constexpr size_t MD_STAGE_P = 0, MD_STAGE_X = (sizeof(SvtAmdMdPicture) + 63) & ~(size_t)63, MD_STAGE_COST = MD_STAGE_X + ((sizeof(SvtAmdMdInter) + 63) & ~(size_t)63),
-                        MD_STAGE_D = MD_STAGE_COST + ((sizeof(SvtAmdCabacCost) + 63) & ~(size_t)63), MD_STAGE_BYTES = MD_STAGE_D + ((sizeof(MdPictureDev) + 63) & ~(size_t)63);
+                        MD_STAGE_D = MD_STAGE_COST + ((sizeof(SvtAmdCabacCost) + 63) & ~(size_t)63), MD_STAGE_CHECK = MD_STAGE_D + ((sizeof(MdPictureDev) + 63) & ~(size_t)63),
+                        MD_STAGE_BYTES = MD_STAGE_CHECK + ((sizeof(SvtAmdMdCtlCheck) + 63) & ~(size_t)63);
 
 void svt_amd_md_state_free(SvtAmdEncDecPicture *pic)
 {
@@ -3159,7 +3160,16 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
                              int ois_slot, const SvtAmdMeLcuResult *me, int me_slot, const SvtAmdTmvpLcu *tmvp, const SvtAmdCabacCost *cost, SvtAmdMdLcuOut *md_out,
                              void *works, void *results, uint32_t bps)
 {
-    if (!ctx || !pic || !P || !lcus || !src_y || !src_cb || !src_cr || (!X && !cost))
+    /* svt_amd_md_picture_set_controls: a DEVICE array bound for this call, which consumes the binding whether it succeeds or refuses */
+    const SvtAmdMdLcu *bound = pic ? pic->md_bound_lcus : nullptr;
+    if (bound) {
+        pic->md_bound_lcus = nullptr;
+        if (lcus) {
+            svt_amd_set_error("svt_amd_md_encode_picture: host LCU controls AND a bound device array (svt_amd_md_picture_set_controls): pass lcus == NULL; the binding is dropped");
+            return SVT_AMD_ERR_BAD_PARAM;
+        }
+    }
+    if (!ctx || !pic || !P || (!lcus && !bound) || !src_y || !src_cb || !src_cr || (!X && !cost))
         return SVT_AMD_ERR_BAD_PARAM;
     if ((X ? !md_picture_supported_inter(P, X) : !md_picture_supported(P)) || P->width != pic->d.width || P->height != pic->d.height || pic->d.bps != bps) {
         svt_amd_set_error("svt_amd_md_encode_picture: picture outside what this revision covers (svt_amd_md_picture_supported[_inter]), or not the picture object's size / sample width");
@@ -3171,7 +3181,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     }
     const int n = pic->nlcu, wl = (pic->d.width + 63) / 64, hl = (pic->d.height + 63) / 64;
     int tiles = 0;
-    for (int i = 0; i < n; i++) {
+    for (int i = 0; lcus && i < n; i++) { /* a bound device array is checked on the device, below */
         if (lcus[i].leaf_count < 1 || lcus[i].leaf_count > SVT_AMD_MD_LEAVES) {
             svt_amd_set_error("svt_amd_md_encode_picture: LCU %d has no leaf list", i);
             return SVT_AMD_ERR_BAD_PARAM;
@@ -3186,6 +3196,11 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
             svt_amd_set_error("svt_amd_md_encode_picture_inter: LCU %d is not decided by ModeDecisionLcu with luma-only candidates", i);
             return SVT_AMD_ERR_BAD_PARAM;
         }
+    }
+    if (bound && pic->md_rect_n) {
+        svt_amd_set_error("svt_amd_md_encode_picture: a bound device array of LCU controls on a picture object with a rank rectangle (svt_amd_encdec_picture_set_rect): "
+                          "the rectangle's tile-border check reads host records");
+        return SVT_AMD_ERR_BAD_PARAM;
     }
     DevPicture *rec_slot[2] = {nullptr, nullptr}; /* records read where another lane's kernels leave them: this lane's stream orders itself behind those kernels */
     SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
@@ -3205,7 +3220,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
         }
         rec_slot[1] = &root->slots[ois_slot];
     }
-    if (pic->md_rect_n) { /* a rank's rectangle (svt_amd_encdec_picture_set_rect): its borders must be tile borders - an LCU never waits for one outside */
+    if (pic->md_rect_n) { /* a rank's rectangle (svt_amd_encdec_picture_set_rect; host controls only): its borders must be tile borders - an LCU never waits for one outside */
         const SvtAmdRect &r = pic->md_rect;
         const int x0 = r.x / 64, y0 = r.y / 64, x1 = (r.x + r.w + 63) / 64, y1 = (r.y + r.h + 63) / 64;
         for (int y = y0; y < y1; y++)
@@ -3229,6 +3244,22 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     for (int k = 0; k < 2; k++)
         if (rec_slot[k] && (rc = svt_amd_records_wait(ctx, rec_slot[k], k, nullptr, nullptr, 0)) != 0)
             return rc;
+    if (bound) { /* the host loop's refusals, its words and the tile count from the check kernel's record (mdctl_kernels.hip): one small copy, one synchronisation */
+        const SvtAmdMdCtlCheck *c = (const SvtAmdMdCtlCheck *)(m->h_stage + MD_STAGE_CHECK);
+        if ((rc = svt_amd_mdctl_check_async(ctx, bound, n, P->depth_mode, X != nullptr, (SvtAmdMdCtlCheck *)(m->h_stage + MD_STAGE_CHECK))) != 0)
+            return rc;
+        HIP_TRY(hipStreamSynchronize(st));
+        if (c->first_bad != 0xFFFFFFFFu) {
+            if (c->first_kind == 0)
+                svt_amd_set_error("svt_amd_md_encode_picture: LCU %d has no leaf list", (int)c->first_bad);
+            else if (c->first_kind == 1)
+                svt_amd_set_error("svt_amd_md_encode_picture: LCU %d: leaf list not ascending", (int)c->first_bad);
+            else
+                svt_amd_set_error("svt_amd_md_encode_picture_inter: LCU %d is not decided by ModeDecisionLcu with luma-only candidates", (int)c->first_bad);
+            return SVT_AMD_ERR_BAD_PARAM;
+        }
+        tiles = (int)c->tiles;
+    }
     /* debug (SVT_AMD_MD_TIMING): host clock around the call's three parts, with a stream synchronisation after each - one line per call on stderr */
     static const bool timing = getenv("SVT_AMD_MD_TIMING") != nullptr;
     const auto t_call = std::chrono::steady_clock::now();
@@ -3300,7 +3331,8 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
                 m->d.mref[l].plane[p] = m->d_ref8[l][p];
             }
     }
-    HIP_TRY(hipMemcpyAsync(m->d_lcus, lcus, sizeof(SvtAmdMdLcu) * (size_t)n, hipMemcpyHostToDevice, st));
+    if (lcus)
+        HIP_TRY(hipMemcpyAsync(m->d_lcus, lcus, sizeof(SvtAmdMdLcu) * (size_t)n, hipMemcpyHostToDevice, st));
     tick("LCU controls copy");
     memcpy(m->h_stage + MD_STAGE_P, P, sizeof(*P)); /* (the block is free: the previous call on this object returned after its stream had drained) */
     HIP_TRY(hipMemcpyAsync(m->d_P, m->h_stage + MD_STAGE_P, sizeof(*P), hipMemcpyHostToDevice, st));
@@ -3338,7 +3370,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     m->d.encode = !X || works || results; /* P / B pictures: without a place for the work / result records, the mode decision alone */
     if (ois)
         HIP_TRY(hipMemcpyAsync(m->d_ois, ois, sizeof(SvtAmdOisLcuResult) * (size_t)n, hipMemcpyHostToDevice, st));
-    m->d.ois = ois ? m->d_ois : d_ois_slot, m->d.lcus = m->d_lcus, m->d.P = m->d_P, m->d.out = m->d_out;
+    m->d.ois = ois ? m->d_ois : d_ois_slot, m->d.lcus = lcus ? m->d_lcus : bound, m->d.P = m->d_P, m->d.out = m->d_out;
     pic->epoch++;
     pic->deblocked = pic->sao_done = false;
     HIP_TRY(hipMemsetAsync(pic->d_sync, 0, sizeof(unsigned), st));
@@ -3460,16 +3492,22 @@ extern "C" int svt_amd_md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture
                                          uint32_t stride_y, const uint8_t *src_cb, const uint8_t *src_cr, uint32_t stride_c, const SvtAmdOisLcuResult *ois,
                                          int ois_slot, const SvtAmdCabacCost *cost, SvtAmdMdLcuOut *md_out, SvtAmdLcuWork *works, SvtAmdLcuResult *results)
 {
-    if (!cost)
+    if (!cost) {
+        if (pic)
+            pic->md_bound_lcus = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
+    }
     return md_encode_picture(ctx, pic, P, nullptr, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, nullptr, -1, nullptr, cost, md_out, works, results, 1);
 }
 extern "C" int svt_amd_md_encode_picture16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus, const uint16_t *src_y,
                                            uint32_t stride_y, const uint16_t *src_cb, const uint16_t *src_cr, uint32_t stride_c, const SvtAmdOisLcuResult *ois,
                                            int ois_slot, const SvtAmdCabacCost *cost, SvtAmdMdLcuOut *md_out, SvtAmdLcuWork16 *works, SvtAmdLcuResult16 *results)
 {
-    if (!cost)
+    if (!cost) {
+        if (pic)
+            pic->md_bound_lcus = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
+    }
     return md_encode_picture(ctx, pic, P, nullptr, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, nullptr, -1, nullptr, cost, md_out, works, results, 2);
 }
 
@@ -3478,8 +3516,11 @@ extern "C" int svt_amd_md_encode_picture_inter(SvtAmdContext *ctx, SvtAmdEncDecP
                                                const SvtAmdOisLcuResult *ois, int ois_slot, const SvtAmdMeLcuResult *me, int me_slot, const SvtAmdTmvpLcu *tmvp,
                                                SvtAmdMdLcuOut *md_out, SvtAmdLcuWork *works, SvtAmdLcuResult *results)
 {
-    if (!X)
+    if (!X) {
+        if (pic)
+            pic->md_bound_lcus = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
+    }
     return md_encode_picture(ctx, pic, P, X, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, me, me_slot, tmvp, nullptr, md_out, works, results, 1);
 }
 extern "C" int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdInter *X, const SvtAmdMdLcu *lcus,
@@ -3487,8 +3528,11 @@ extern "C" int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncDe
                                                  const SvtAmdOisLcuResult *ois, int ois_slot, const SvtAmdMeLcuResult *me, int me_slot, const SvtAmdTmvpLcu *tmvp,
                                                  SvtAmdMdLcuOut *md_out, SvtAmdLcuWork16 *works, SvtAmdLcuResult16 *results)
 {
-    if (!X)
+    if (!X) {
+        if (pic)
+            pic->md_bound_lcus = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
+    }
     return md_encode_picture(ctx, pic, P, X, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, me, me_slot, tmvp, nullptr, md_out, works, results, 2);
 }
 
@@ -3637,3 +3681,13 @@ extern "C" __attribute__((visibility("default"))) int svt_amd_debug_window_count
     return SVT_AMD_OK;
 }
 #endif
+
+extern "C" int svt_amd_md_picture_set_controls(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLcu *d_lcus)
+{
+    if (!ctx || !pic) {
+        svt_amd_set_error("svt_amd_md_picture_set_controls: a context and a picture object");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    pic->md_bound_lcus = d_lcus;
+    return SVT_AMD_OK;
+}

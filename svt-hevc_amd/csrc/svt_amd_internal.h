@@ -126,6 +126,7 @@ struct SvtAmdContext {
     void *d_sbo;                   /* descriptor table + per-LCU / per-workgroup partials of svt_amd_source_ops_batch_launch (sbo_kernels.hip), allocated at its first call */
     void *d_mdc;                   /* descriptor table + per-LCU scores and flags of svt_amd_md_config_batch_launch (mdc_kernels.hip), allocated at its first call */
     void *d_irc;                   /* descriptor table + per-LCU votes and flags, per-workgroup vote totals of svt_amd_initial_rc_batch_launch (irc_kernels.hip), allocated at its first call */
+    void *d_mdctl;                 /* descriptor table of svt_amd_md_controls_batch_launch + the check record of a bound controls array (mdctl_kernels.hip), allocated at first use */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
@@ -152,6 +153,10 @@ int svt_amd_records_wait(SvtAmdContext *ctx, DevPicture *s, int which, hipEvent_
 int svt_amd_records_read_mark(SvtAmdContext *ctx, SvtAmdContext *root, int slot);
 
 void svt_amd_set_error(const char *fmt, ...);
+
+/* mdctl_kernels.hip: queues the check kernel over a DEVICE array of n SvtAmdMdLcu records on the context's stream and the copy of its record to `h_out`
+ * (page-locked); the caller synchronises.  depth_mode: SvtAmdMdPicture.depth_mode; inter: a P / B call (md_lcu_supported is applied) */
+int svt_amd_mdctl_check_async(SvtAmdContext *ctx, const SvtAmdMdLcu *d_lcus, int n, int depth_mode, int inter, SvtAmdMdCtlCheck *h_out);
 
 /* The context's stream.  A context holds none until its first stream-ordered use (a launch, an asynchronous copy, an event
  * record or wait, a timer): one that only allocates, pins host memory, copies blocking and forks lanes - the root of a host that
