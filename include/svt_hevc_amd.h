@@ -2348,6 +2348,63 @@ SVT_AMD_API int svt_amd_md_lcus_supported(const SvtAmdMdPicture *P, const SvtAmd
  * mode-decision kernel at the array.  A picture object with a rank rectangle (svt_amd_encdec_picture_set_rect) is refused with a bound array: the tile-border check
  * of that path reads host records. */
 SVT_AMD_API int svt_amd_md_picture_set_controls(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLcu *d_lcus);
+
+/* ------------------------------------------------------------------------- */
+/* Temporal motion field on the device: the co-located picture's field and intra-coded area from its work records */
+/* ------------------------------------------------------------------------- */
+/* The one closed-loop input of a P / B picture's mode decision: the motion field of its co-located picture (SvtAmdTmvpLcu above).  The field is nothing but the
+ * final coding tree of that picture, and the device holds the tree: the SvtAmdLcuWork[16] records the mode-decision call (or svt_amd_encode_picture*) left in HBM.
+ * What the reference does (tests/tmvp_numpy.py restates it; tests/golden/tmvp_*.npz hold its own results):
+ *   EncodePass keeps the map for pictures with isUsedAsReferenceFlag (Codec/EbCodingLoop.c:3142-3158) and updates it per coded unit (:4500-4585): a unit at
+ *   LCU-local (x, y) of size s writes the 16x16 map units vx in [(x + 15) >> 4, (x + s + 15) >> 4), vy likewise, at index vy * 4 + vx - a map unit takes the coded
+ *   unit that contains its top-left sample; of four 8x8 units in a 16x16 only the top-left one writes, units at x or y = 8 (mod 16) write nothing.  An intra unit
+ *   writes availabilityFlag = 0; an inter unit availabilityFlag = 1, predictionDirection = interPredDirectionIndex and, for each list the direction uses, mv[list]
+ *   and refPicPOC[list] = the picture's own refPicPtrArray[list]->refPOC.  Everything else keeps what the pooled reference object held before.  The readers
+ *   (GetTemporalMVP, GetTemporalMVP_V2, Codec/EbAdaptiveMotionVectorPrediction.c:1342-1386, :1412-1447) read only what the direction names, and never a unit whose
+ *   top-left sample is outside the picture.
+ *   intraCodedArea (Codec/EbCodingLoop.c:3264-3269, :3574; Codec/EbEncDecProcess.c:1887-1891): (EB_U8)((100 * sum of size^2 of the intra units) / (lumaWidth *
+ *   lumaHeight)) in 32-bit unsigned arithmetic, 0 for an I picture.  (intraCodedAreaLCU has no reader and is not built.)
+ * Here EVERY byte of the field is defined: the observable fields - `available`; `pred_dir` where available; mv[l] and ref_poc[l] of the lists the direction uses - as
+ * above (a unit is inter when pred_mode == 1), everything else 0: units outside the picture, pred_dir / mv / ref_poc of unavailable units, the list a uni-predicted
+ * unit does not use, and the whole record behind the last LCU (the mode-decision kernel reads record lcu and lcu + 1).
+ * The intra-coded area serves two inputs that stay HOST bytes in this revision, SvtAmdMdInter.skip_cost_bias and SvtAmdMdcJob.ref_intra_coded_area: the host reads
+ * the 8 bytes of SvtAmdRefStats per reference picture instead of walking its tree; reading them in place is a later step. */
+typedef struct SvtAmdMotionFieldJob {
+    const void *d_works;                   /* DEVICE: SvtAmdLcuWork or SvtAmdLcuWork16 of every LCU, raster order (heads and unit lists are shared); 4-byte aligned */
+    size_t      work_stride;               /* sizeof the record type (any multiple of 4 that holds head and unit list, 1584 bytes: only those are read)            */
+    uint16_t    width, height;             /* luma                                                                                                                   */
+    uint8_t     slice_type;                /* EB_PICTURE of the picture the records belong to: 0 B, 1 P, 2 I                                                        */
+    uint8_t     pad[3];                    /* 0                                                                                                                      */
+    uint64_t    ref_poc[2];                /* its refPOC per list (unused lists: any value)                                                                          */
+} SvtAmdMotionFieldJob;
+typedef struct SvtAmdRefStats {
+    uint32_t intra_area_sum;               /* sum of size^2 over the intra units (pred_mode == 2) of the picture                                                    */
+    uint8_t  intra_coded_area;             /* EbReferenceObject_t.intraCodedArea: the percentage above, 0 for an I picture                                          */
+    uint8_t  pad[3];                       /* written as 0                                                                                                           */
+} SvtAmdRefStats;
+#define SVT_AMD_MOTION_FIELD 0
+#define SVT_AMD_MOTION_FIELD_STATS 1
+/* bytes of the outputs: SVT_AMD_MOTION_FIELD (LCUs + 1) * sizeof(SvtAmdTmvpLcu), SVT_AMD_MOTION_FIELD_STATS sizeof(SvtAmdRefStats); 0 for anything else */
+SVT_AMD_API size_t svt_amd_motion_field_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+/* Queues the field of one picture on the context's stream and returns: d_field (DEVICE, 8-byte aligned, svt_amd_motion_field_bytes) receives LCUs + 1 records,
+ * nothing behind them is written; d_stats (DEVICE, or NULL) one SvtAmdRefStats.  Everything is checked before anything is queued (pictures of at most
+ * SVT_AMD_MDCTL_MAX_LCUS LCUs - the picture may be of any size up to that, larger than the one the context was made for too: the entry reads no picture slot).
+ * Per-LCU sums pass through a scratch the context owns (a word per LCU of the largest picture the entry takes, 64 KB, allocated at the first call): calls on
+ * one context are stream-ordered among themselves, callers serialise per context as everywhere. */
+SVT_AMD_API int svt_amd_motion_field_launch(SvtAmdContext *ctx, const SvtAmdMotionFieldJob *job, SvtAmdTmvpLcu *d_field, SvtAmdRefStats *d_stats);
+/* The same from a picture object: the work records the LAST svt_amd_md_encode_picture[_inter][16] call on `pic` left on the device.  Refused when no such call has
+ * completed on the object (or the last one was a P / B call without works and results: the mode decision alone, which writes no work records), and on an
+ * object with a rank rectangle (svt_amd_encdec_picture_set_rect: the records of its other LCUs are zeroed, the field would be wrong).  ref_poc may be NULL for an I picture (slice_type 2).  Queued on ctx's stream: on the context the mode-decision call ran on, stream order suffices. */
+SVT_AMD_API int svt_amd_encdec_picture_motion_field(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, int slice_type, const uint64_t ref_poc[2], SvtAmdTmvpLcu *d_field,
+                                                    SvtAmdRefStats *d_stats);
+/* svt_amd_md_picture_set_controls for the motion field: binds a DEVICE array of LCUs + 1 records (svt_amd_motion_field_launch's output, or any array of that layout
+ * whose last record is zero) as the co-located motion field of the NEXT svt_amd_md_encode_picture_inter[16] call on `pic`, and of that call only: every call on the
+ * object consumes the binding, whether it succeeds or refuses.  That call passes tmvp == NULL; with X->tmvp_enable it points the kernel at the array - no upload, no
+ * fill.  One that passes a host tmvp as well is refused and drops the binding; with tmvp_enable == 0 or X == NULL the binding is dropped unread; d_field == NULL drops a
+ * binding.  Without a binding, tmvp == NULL with tmvp_enable is refused as before.  Ordering as for svt_amd_md_picture_set_controls: written on the context the call
+ * runs on, stream order suffices; across lanes it is the caller's.  The array must stay valid until the blocking call returns.  May be combined with a controls
+ * binding in the same call. */
+SVT_AMD_API int svt_amd_md_picture_set_motion_field(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdTmvpLcu *d_field);
 /* debug: stage clocks of the mode-decision kernel (16 shader-clock sums per LCU, accumulated over the picture object's later calls; the first call
  * switches the collection on) - see svt-hevc_amd/csrc/md_kernels.hip */
 SVT_AMD_API int svt_amd_debug_md_profile(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, unsigned long long *out);

@@ -132,6 +132,8 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
         (void)hipFree(ctx->d_irc);
     if (ctx->d_mdctl)
         (void)hipFree(ctx->d_mdctl);
+    if (ctx->d_tmvp)
+        (void)hipFree(ctx->d_tmvp);
     if (ctx->d_dbg)
         (void)hipFree(ctx->d_dbg);
     for (int i = 0; i < ctx->cap_stamps; i++) {

@@ -52,6 +52,10 @@ struct SvtAmdEncDecPicture {
     struct SvtAmdMdState *md;
     /* svt_amd_md_picture_set_controls: the DEVICE SvtAmdMdLcu array the next mode-decision call on the object reads in place; that call clears it */
     const SvtAmdMdLcu *md_bound_lcus;
+    /* svt_amd_md_picture_set_motion_field: the DEVICE SvtAmdTmvpLcu array (LCUs + 1 records) the next mode-decision call on the object reads in place; every call clears it */
+    const SvtAmdTmvpLcu *md_bound_tmvp;
+    /* the last mode-decision call on the object ran to its end: its work records in HBM are a whole picture's (svt_amd_encdec_picture_motion_field) */
+    bool md_works_whole;
     /* recorded behind every picture-level call that writes the picture's stages (encode pass, mode decision + encode pass, deblocking, SAO, an exchange that fills it):
      * a reader on another context's stream - svt_amd_encdec_picture_import - orders itself behind it; `written`: the object holds an encoded picture at all */
     hipEvent_t ev_written;

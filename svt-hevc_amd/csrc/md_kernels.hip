@@ -3162,6 +3162,9 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
 {
     /* svt_amd_md_picture_set_controls: a DEVICE array bound for this call, which consumes the binding whether it succeeds or refuses */
     const SvtAmdMdLcu *bound = pic ? pic->md_bound_lcus : nullptr;
+    const SvtAmdTmvpLcu *bound_tmvp = pic ? pic->md_bound_tmvp : nullptr;
+    if (pic)
+        pic->md_bound_tmvp = nullptr;
     if (bound) {
         pic->md_bound_lcus = nullptr;
         if (lcus) {
@@ -3169,13 +3172,18 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
             return SVT_AMD_ERR_BAD_PARAM;
         }
     }
+    /* svt_amd_md_picture_set_motion_field: likewise for the co-located motion field - read below only by a P / B call with tmvp_enable, dropped unread otherwise */
+    if (bound_tmvp && tmvp) {
+        svt_amd_set_error("svt_amd_md_encode_picture_inter: a host motion field AND a bound device array (svt_amd_md_picture_set_motion_field): pass tmvp == NULL; the binding is dropped");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
     if (!ctx || !pic || !P || (!lcus && !bound) || !src_y || !src_cb || !src_cr || (!X && !cost))
         return SVT_AMD_ERR_BAD_PARAM;
     if ((X ? !md_picture_supported_inter(P, X) : !md_picture_supported(P)) || P->width != pic->d.width || P->height != pic->d.height || pic->d.bps != bps) {
         svt_amd_set_error("svt_amd_md_encode_picture: picture outside what this revision covers (svt_amd_md_picture_supported[_inter]), or not the picture object's size / sample width");
         return SVT_AMD_ERR_BAD_PARAM;
     }
-    if (X && (!pic->has_cost || !pic->has_ref[0] || (P->slice_type == 0 && !pic->has_ref[1]) || (X->tmvp_enable && !tmvp))) {
+    if (X && (!pic->has_cost || !pic->has_ref[0] || (P->slice_type == 0 && !pic->has_ref[1]) || (X->tmvp_enable && !tmvp && !bound_tmvp))) {
         svt_amd_set_error("svt_amd_md_encode_picture_inter: reference pictures / rate tables not set (svt_amd_encdec_picture_set_inter), or no co-located motion field");
         return SVT_AMD_ERR_BAD_PARAM;
     }
@@ -3349,12 +3357,12 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
         if (me)
             HIP_TRY(hipMemcpyAsync(m->d_me, me, sizeof(SvtAmdMeLcuResult) * (size_t)n, hipMemcpyHostToDevice, st));
         tick("ME records copy");
-        if (X->tmvp_enable) {
+        if (X->tmvp_enable && tmvp) {
             HIP_TRY(hipMemcpyAsync(m->d_tmvp, tmvp, sizeof(SvtAmdTmvpLcu) * (size_t)n, hipMemcpyHostToDevice, st));
             HIP_TRY(hipMemsetAsync(m->d_tmvp + n, 0, sizeof(SvtAmdTmvpLcu), st));
             tick("motion-field copy + fill");
         }
-        m->d.X = m->d_X, m->d.me = me ? m->d_me : d_me_slot, m->d.tmvp = m->d_tmvp;
+        m->d.X = m->d_X, m->d.me = me ? m->d_me : d_me_slot, m->d.tmvp = X->tmvp_enable && bound_tmvp ? bound_tmvp : m->d_tmvp; /* a bound field is read in place */
         HIP_TRY(hipMemsetAsync(m->d.md_mv, 0, m->mv_bytes, st));
         tick("mv fill");
     }
@@ -3373,6 +3381,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     m->d.ois = ois ? m->d_ois : d_ois_slot, m->d.lcus = lcus ? m->d_lcus : bound, m->d.P = m->d_P, m->d.out = m->d_out;
     pic->epoch++;
     pic->deblocked = pic->sao_done = false;
+    pic->md_works_whole = false; /* until this call has run to its end */
     HIP_TRY(hipMemsetAsync(pic->d_sync, 0, sizeof(unsigned), st));
     HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, st));
     HIP_TRY(hipMemsetAsync(m->d.md_info, 0xFF, m->info_bytes, st));
@@ -3485,6 +3494,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
         fprintf(stderr, "svt_amd_md_encode_picture%s: layer %d, %d LCUs, stream + front-half records ready %.2f ms, inputs up %.2f ms, kernel %.2f ms, records down %.2f ms\n", X ? "_inter" : "",
                 (int)P->temporal_layer, n_active, ms(t_call, t_begin), ms(t_begin, t_up), ms(t_up, t_kernel), ms(t_kernel, t_end));
     }
+    pic->md_works_whole = !pic->md_rect_n && m->d.encode; /* (a P / B call that asked for decisions only writes no work records) */
     return SVT_AMD_OK;
 }
 
@@ -3494,7 +3504,7 @@ extern "C" int svt_amd_md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture
 {
     if (!cost) {
         if (pic)
-            pic->md_bound_lcus = nullptr;
+            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
     }
     return md_encode_picture(ctx, pic, P, nullptr, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, nullptr, -1, nullptr, cost, md_out, works, results, 1);
@@ -3505,7 +3515,7 @@ extern "C" int svt_amd_md_encode_picture16(SvtAmdContext *ctx, SvtAmdEncDecPictu
 {
     if (!cost) {
         if (pic)
-            pic->md_bound_lcus = nullptr;
+            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
     }
     return md_encode_picture(ctx, pic, P, nullptr, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, nullptr, -1, nullptr, cost, md_out, works, results, 2);
@@ -3518,7 +3528,7 @@ extern "C" int svt_amd_md_encode_picture_inter(SvtAmdContext *ctx, SvtAmdEncDecP
 {
     if (!X) {
         if (pic)
-            pic->md_bound_lcus = nullptr;
+            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
     }
     return md_encode_picture(ctx, pic, P, X, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, me, me_slot, tmvp, nullptr, md_out, works, results, 1);
@@ -3530,7 +3540,7 @@ extern "C" int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncDe
 {
     if (!X) {
         if (pic)
-            pic->md_bound_lcus = nullptr;
+            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
         return SVT_AMD_ERR_BAD_PARAM;
     }
     return md_encode_picture(ctx, pic, P, X, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, me, me_slot, tmvp, nullptr, md_out, works, results, 2);
@@ -3690,4 +3700,48 @@ extern "C" int svt_amd_md_picture_set_controls(SvtAmdContext *ctx, SvtAmdEncDecP
     }
     pic->md_bound_lcus = d_lcus;
     return SVT_AMD_OK;
+}
+
+extern "C" int svt_amd_md_picture_set_motion_field(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdTmvpLcu *d_field)
+{
+    if (!ctx || !pic) {
+        svt_amd_set_error("svt_amd_md_picture_set_motion_field: a context and a picture object");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    if ((uintptr_t)d_field % 8) {
+        svt_amd_set_error("svt_amd_md_picture_set_motion_field: the field at %p is not 8-byte aligned", (const void *)d_field);
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    pic->md_bound_tmvp = d_field;
+    return SVT_AMD_OK;
+}
+
+/* the field and the intra-coded area of the picture the last mode-decision call on `pic` decided, from the work records it left in HBM (tmvp_kernels.hip) */
+extern "C" int svt_amd_encdec_picture_motion_field(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, int slice_type, const uint64_t ref_poc[2], SvtAmdTmvpLcu *d_field,
+                                                   SvtAmdRefStats *d_stats)
+{
+    if (!ctx || !pic || !d_field) {
+        svt_amd_set_error("svt_amd_encdec_picture_motion_field: a context, a picture object and a device array for the field");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    if (slice_type < 0 || slice_type > 2 || (!ref_poc && slice_type != 2)) {
+        svt_amd_set_error("svt_amd_encdec_picture_motion_field: slice type %d%s", slice_type, ref_poc ? "" : " without reference POCs");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    if (pic->md_rect_n) {
+        svt_amd_set_error("svt_amd_encdec_picture_motion_field: the picture object has a rank rectangle (svt_amd_encdec_picture_set_rect): the work records of its other LCUs "
+                          "are zeroed");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    if (!pic->md || !pic->md_works_whole) {
+        svt_amd_set_error("svt_amd_encdec_picture_motion_field: no svt_amd_md_encode_picture* call that writes work records has completed on the picture object");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    SvtAmdMotionFieldJob job;
+    memset(&job, 0, sizeof(job));
+    job.d_works = pic->md->d_works, job.work_stride = pic->md->work_bytes;
+    job.width = pic->d.width, job.height = pic->d.height, job.slice_type = (uint8_t)slice_type;
+    if (ref_poc)
+        job.ref_poc[0] = ref_poc[0], job.ref_poc[1] = ref_poc[1];
+    return svt_amd_motion_field_launch(ctx, &job, d_field, d_stats);
 }

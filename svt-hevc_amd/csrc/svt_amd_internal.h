@@ -127,6 +127,7 @@ struct SvtAmdContext {
     void *d_mdc;                   /* descriptor table + per-LCU scores and flags of svt_amd_md_config_batch_launch (mdc_kernels.hip), allocated at its first call */
     void *d_irc;                   /* descriptor table + per-LCU votes and flags, per-workgroup vote totals of svt_amd_initial_rc_batch_launch (irc_kernels.hip), allocated at its first call */
     void *d_mdctl;                 /* descriptor table of svt_amd_md_controls_batch_launch + the check record of a bound controls array (mdctl_kernels.hip), allocated at first use */
+    void *d_tmvp;                  /* per-LCU intra-area sums of svt_amd_motion_field_launch (tmvp_kernels.hip), allocated at its first call */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
