@@ -1901,6 +1901,73 @@ SVT_AMD_API int svt_amd_encdec_picture_sao_decide(SvtAmdContext *ctx, SvtAmdEncD
 SVT_AMD_API int svt_amd_encdec_picture_reference(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, uint32_t origin_x, uint32_t origin_y,
                                                  SvtAmdRefPicture *ref, void *out_y, void *out_cb, void *out_cr);
 
+/* ------------------------------------------------------------------------- */
+/* Picture tail on the device: deblocking, SAO and padding from the records in HBM */
+/* ------------------------------------------------------------------------- */
+/* The three blocking entries above take HOST records: they walk every unit of every LCU on the host, upload the maps and (for SAO) the whole work array again, and
+ * synchronise five times a reference picture.  The records are in HBM already - the device-array encode entries and the mode-decision calls leave them there - so the
+ * tail below derives the filters' inputs from them ON the device and queues the same chain without touching the host.  What the reference does is what the blocking
+ * entries cite: LCUInternalAreaDLFCore / LCUBoundaryDLFCore / LCUPictureEdgeDLFCore (Codec/EbDeblockingFilter.c:2222, 2828, 3518; Codec/EbCodingLoop.c:4600-4631) on
+ * the strengths of SetBSArrayBasedOnPUBoundary / TUBoundary (:339, :472); SaoGenerationDecision[16bit] (Codec/EbCodingLoop.c:4640-4750,
+ * Codec/EbSampleAdaptiveOffsetGenerationDecision.c:647-850, :936-1140); ApplySaoOffsetsPicture (Codec/EbEncDecProcess.c:522-757); PadRefAndSetFlags
+ * (Codec/EbEncDecProcess.c:1805).  The blocking entries keep their code and behaviour; on the same inputs the tail leaves the same bytes: the deblocked planes, the
+ * finished planes, the parameters, the padded reference.
+ *
+ * Inputs derived per LCU (tests/tail_numpy.py restates them; svt-hevc_amd/csrc/tail_logic.h is the one text the device and a plain C program compile):
+ *   SvtAmdCuMapEntry per 8x8 block (mode and size_log2 of the covering unit; dir and mv of inter units only; everything else 0), QP per 8x8 block, luma cbf per 4x4
+ *   block (a 64x64 unit: result slots c + 1 .. c + 4, one per 32x32 quadrant), picture-sized as the filter kernels read them; where two units cover a cell the later one
+ *   in list order wins; a cell no unit covers is 0;
+ *   per LCU the deblocking edge byte (tile_left | tile_top << 1), SvtAmdSaoLcuParams.edge_flags (1 left, 2 right, 4 top, 8 bottom: the last LCU row, or the LCU
+ *   below has tile_top) and the follow bits of the encoder-order composite (1: an LCU of the same tile follows to the right, 2: below);
+ *   the LCUs' source samples as three planes.
+ * The records are not validated on the host; what the host loops refuse is COUNTED: an LCU that is not at its raster position or has num_cus > 64 (none of its units
+ * is taken, its source samples are not scattered), and a unit whose size is not 8 / 16 / 32 / 64, that leaves its LCU or the picture, or - a 64x64 unit - whose result
+ * slots leave the record.  An offending unit writes nothing (its cells stay 0); no access leaves the arrays.  first_* are 0xFFFFFFFF when there is none. */
+typedef struct SvtAmdTailCheck { uint32_t bad_lcus, first_bad_lcu, bad_units, first_bad_unit_lcu; } SvtAmdTailCheck;
+#define SVT_AMD_TAIL_DEBLOCK    1u  /* boundary strengths + deblocking: the object's deblocked planes                                                     */
+#define SVT_AMD_TAIL_SAO_DECIDE 2u  /* statistics + parameter decision; without SVT_AMD_TAIL_DEBLOCK on the picture as encoded (allowEncDecMismatch pictures) */
+#define SVT_AMD_TAIL_SAO_APPLY  4u  /* the finished planes; needs SVT_AMD_TAIL_SAO_DECIDE and SVT_AMD_TAIL_DEBLOCK in the same job                         */
+#define SVT_AMD_TAIL_REFERENCE  8u  /* the latest stage padded (origin_x / origin_y: luma padding, even, 8..256); needs `ref`                                */
+typedef struct SvtAmdTailJob {
+    const void *d_works;                   /* DEVICE: SvtAmdLcuWork[16] of every LCU, raster order; 4-byte aligned (16-byte aligned records are scattered 16 bytes a lane) */
+    size_t      work_stride;               /* any multiple of 4 that holds the record type of the object's sample width                                        */
+    const void *d_results;                 /* DEVICE: SvtAmdLcuResult[16]; only cu[].cbf[0] is read                                                           */
+    size_t      result_stride;
+    const uint8_t *d_sao_enable;           /* DEVICE, one byte an LCU as svt_amd_sao_decide_picture takes it, or NULL = all 1                                 */
+    SvtAmdDeblockParams deblock;
+    SvtAmdSaoDecisionParams sao;
+    uint32_t    origin_x, origin_y;        /* SVT_AMD_TAIL_REFERENCE                                                                                          */
+    uint32_t    stages;                    /* SVT_AMD_TAIL_*                                                                                                  */
+    uint32_t    pad;                       /* 0                                                                                                               */
+} SvtAmdTailJob;
+#define SVT_AMD_TAIL_LCU_PARAMS 0
+#define SVT_AMD_TAIL_CHECK 1
+/* bytes of the optional outputs: SVT_AMD_TAIL_LCU_PARAMS LCUs * sizeof(SvtAmdSaoLcuParams), SVT_AMD_TAIL_CHECK sizeof(SvtAmdTailCheck); 0 for anything else */
+SVT_AMD_API size_t svt_amd_picture_tail_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+/* Queues the stages of job->stages on ctx's stream behind whatever encoded the picture there, and returns: no synchronisation, no copy from or to the host (the two
+ * parameter structs travel by value), no allocation after the first call on the object (or after the warm-up below).  The working memory - maps, both strength
+ * arrays, source and composite planes, statistics, parameters, costs - belongs to the picture object and is freed with it: tails of two objects on two lanes can be
+ * in flight together.  d_works == NULL && d_results == NULL: the records the LAST svt_amd_md_encode_picture[_inter][16] call left on the object, refused as
+ * svt_amd_encdec_picture_motion_field refuses (no completed call, a P / B call without works and results, an object with a rank rectangle).
+ * d_lcu_params (DEVICE, optional): the decided SvtAmdSaoLcuParams of every LCU; d_check (DEVICE, optional): one SvtAmdTailCheck (written when a filter stage runs);
+ * nothing behind either is written.  ref (HOST, required with SVT_AMD_TAIL_REFERENCE) is filled at queue time, as svt_amd_encdec_picture_reference fills it; the planes
+ * are ready in stream order.  The object's deblocked / finished state is set as the blocking calls set it.  Everything is checked before anything is queued: a refusal
+ * names the entry in svt_amd_last_error and writes nothing. */
+SVT_AMD_API int svt_amd_encdec_picture_tail_launch(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdTailJob *job, SvtAmdSaoLcuParams *d_lcu_params,
+                                                   SvtAmdTailCheck *d_check, SvtAmdRefPicture *ref);
+/* everything the first tail on the object would allocate, made now; origin_x = origin_y = 0: without the padded reference planes */
+SVT_AMD_API int svt_amd_encdec_picture_tail_warmup(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, uint32_t origin_x, uint32_t origin_y);
+/* the 16-bit twins of svt_amd_encode_picture_device / svt_amd_encode_picture_device_inter: a 10-bit sequence stays on the device as an 8-bit one does */
+SVT_AMD_API int svt_amd_encode_picture_device16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork16 *d_works, SvtAmdLcuResult16 *d_results,
+                                                int tiles);
+SVT_AMD_API int svt_amd_encode_picture_device_inter16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork16 *d_works,
+                                                      SvtAmdLcuResult16 *d_results, int tiles, int free_lcus);
+/* debug / test: what the object's last tail with a filter stage derived from the records, downloaded (blocking); every pointer HOST and optional.  map / cbf / qp:
+ * picture-sized as above; lcu_bytes: [4][LCUs] - deblocking edge byte, SAO edge flags, follow bits, status byte (0x80: the LCU is refused, else its number of
+ * refused units); check: the reduced record; src_*: the source planes, tightly packed, of the object's sample width */
+SVT_AMD_API int svt_amd_debug_picture_tail_maps(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, SvtAmdCuMapEntry *map, uint8_t *cbf, uint8_t *qp, uint8_t *lcu_bytes,
+                                                SvtAmdTailCheck *check, void *src_y, void *src_cb, void *src_cr);
+
 /* debug: out == NULL arms per-LCU shader-clock sums in the encode-pass kernels (16 x u64 per LCU: prediction, encode, copy-out, units,
  * wait for neighbours, start, end, -, the prediction's four sub-phases, 4 unused), a later call with a HOST buffer of 16 * LCUs u64
  * fetches them (tools/encodepass_bench.py) */

@@ -60,6 +60,8 @@ struct SvtAmdEncDecPicture {
      * a reader on another context's stream - svt_amd_encdec_picture_import - orders itself behind it; `written`: the object holds an encoded picture at all */
     hipEvent_t ev_written;
     bool written;
+    /* the stream-ordered picture tail's working memory (tail_kernels.hip), allocated by its first call or its warm-up */
+    struct SvtAmdTailState *tail;
 };
 /* the picture's stages are (being) written by work queued on ctx's stream */
 static inline int ep_picture_written(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic)
@@ -74,6 +76,9 @@ static inline int ep_picture_written(SvtAmdContext *ctx, SvtAmdEncDecPicture *pi
     return SVT_AMD_OK;
 }
 void svt_amd_md_state_free(SvtAmdEncDecPicture *pic); /* md_kernels.hip */
+void svt_amd_tail_state_free(SvtAmdEncDecPicture *pic); /* tail_kernels.hip */
+/* md_kernels.hip: the DEVICE records of the object's mode-decision state and their strides; 0 when the object has none */
+int svt_amd_md_picture_records(const SvtAmdEncDecPicture *pic, const void **d_works, size_t *work_stride, const void **d_results, size_t *result_stride);
 /* encdec_kernels.hip: the encode pass of every LCU of the picture from work records the mode-decision kernel left in HBM, queued on ctx's stream behind it */
 int svt_amd_ep_launch_behind_md(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const void *d_works, void *d_results, int n_active, const unsigned *d_order, int inter, int tiles);
 

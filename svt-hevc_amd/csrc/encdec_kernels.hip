@@ -207,6 +207,7 @@ extern "C" int svt_amd_encdec_picture_destroy(SvtAmdContext *ctx, SvtAmdEncDecPi
     if (pic->h_cost)
         (void)hipHostFree(pic->h_cost);
     svt_amd_md_state_free(pic);
+    svt_amd_tail_state_free(pic);
     if (pic->ev_written)
         (void)hipEventDestroy(pic->ev_written);
     for (int k = 0; k < 3; k++) {
@@ -600,6 +601,20 @@ extern "C" int svt_amd_encode_picture_device_inter(SvtAmdContext *ctx, SvtAmdEnc
     if (!ctx || !pic || !d_works || !d_results || tiles < 1 || free_lcus < 0)
         return SVT_AMD_ERR_BAD_PARAM;
     return encode_picture<uint8_t>(ctx, pic, nullptr, nullptr, d_works, d_results, tiles, free_lcus);
+}
+/* the 16-bit twins of the two device-array forms: a 10-bit sequence stays on the device as an 8-bit one does */
+extern "C" int svt_amd_encode_picture_device16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork16 *d_works, SvtAmdLcuResult16 *d_results, int tiles)
+{
+    if (!ctx || !pic || !d_works || !d_results || tiles < 1)
+        return SVT_AMD_ERR_BAD_PARAM;
+    return encode_picture<uint16_t>(ctx, pic, nullptr, nullptr, d_works, d_results, tiles);
+}
+extern "C" int svt_amd_encode_picture_device_inter16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork16 *d_works, SvtAmdLcuResult16 *d_results,
+                                                     int tiles, int free_lcus)
+{
+    if (!ctx || !pic || !d_works || !d_results || tiles < 1 || free_lcus < 0)
+        return SVT_AMD_ERR_BAD_PARAM;
+    return encode_picture<uint16_t>(ctx, pic, nullptr, nullptr, d_works, d_results, tiles, free_lcus);
 }
 
 /* ---- deblocking behind the encode pass ------------------------------------------------------------------------------------------ */

@@ -3716,6 +3716,15 @@ extern "C" int svt_amd_md_picture_set_motion_field(SvtAmdContext *ctx, SvtAmdEnc
     return SVT_AMD_OK;
 }
 
+/* the records the mode-decision calls on `pic` leave in HBM, for the picture tail (tail_kernels.hip) */
+int svt_amd_md_picture_records(const SvtAmdEncDecPicture *pic, const void **d_works, size_t *work_stride, const void **d_results, size_t *result_stride)
+{
+    if (!pic->md)
+        return 0;
+    *d_works = pic->md->d_works, *work_stride = pic->md->work_bytes, *d_results = pic->md->d_results, *result_stride = pic->md->result_bytes;
+    return 1;
+}
+
 /* the field and the intra-coded area of the picture the last mode-decision call on `pic` decided, from the work records it left in HBM (tmvp_kernels.hip) */
 extern "C" int svt_amd_encdec_picture_motion_field(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, int slice_type, const uint64_t ref_poc[2], SvtAmdTmvpLcu *d_field,
                                                    SvtAmdRefStats *d_stats)
