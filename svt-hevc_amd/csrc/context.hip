@@ -116,22 +116,9 @@ extern "C" void svt_amd_context_destroy(SvtAmdContext *ctx)
         (void)hipFree(ctx->d_prep_jobs);
     if (ctx->d_pack_src)
         (void)hipFree(ctx->d_pack_src);
-    if (ctx->d_side)
-        (void)hipFree(ctx->d_side);
-    if (ctx->d_chroma)
-        (void)hipFree(ctx->d_chroma);
-    if (ctx->d_detect)
-        (void)hipFree(ctx->d_detect);
-    if (ctx->d_noise)
-        (void)hipFree(ctx->d_noise);
-    if (ctx->d_sbo)
-        (void)hipFree(ctx->d_sbo);
-    if (ctx->d_mdc)
-        (void)hipFree(ctx->d_mdc);
-    if (ctx->d_irc)
-        (void)hipFree(ctx->d_irc);
-    if (ctx->d_mdctl)
-        (void)hipFree(ctx->d_mdctl);
+    for (int i = 0; i < BATCH_ENTRIES; i++)
+        if (ctx->d_batch[i])
+            (void)hipFree(ctx->d_batch[i]);
     if (ctx->d_tmvp)
         (void)hipFree(ctx->d_tmvp);
     if (ctx->d_dbg)

@@ -376,7 +376,7 @@ extern "C" int svt_amd_chroma_stats_batch_launch(SvtAmdContext *ctx, const SvtAm
 
     ChromaJobDev *d_tab;
     unsigned long long *d_sums; /* the per-region sums the histogram kernels accumulate into */
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_chroma, sizeof(ChromaJobDev), CHROMA_SUMS_BYTES, (void **)&d_tab, (void **)&d_sums));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_CHROMA, sizeof(ChromaJobDev), CHROMA_SUMS_BYTES, (void **)&d_tab, (void **)&d_sums));
     const size_t b_hist = (size_t)regions * 2 * 256 * 4;
     static thread_local ChromaJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
@@ -421,10 +421,9 @@ extern "C" int svt_amd_picture_detect_batch_launch(SvtAmdContext *ctx, const Svt
 {
     SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
-    const int w = luma_width, h = luma_height;
-    const int wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl;
-    if (w < 1 || h < 1 || lcus > DETECT_MAX_LCUS)
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d (at most %d LCUs)", __func__, w, h, DETECT_MAX_LCUS);
+    SvtAmdBatchGeometry g; /* no scratch per LCU: a picture larger than the context was made for is accepted */
+    SVT_AMD_TRY(svt_amd_batch_geometry(__func__, ctx, luma_width, luma_height, DETECT_MAX_LCUS, false, &g));
+    const auto [w, h, wl, hl, lcus, groups, cap_lcus, cap_groups] = g;
     if (!out->lcu || !out->picture)
         SVT_AMD_BAD("%s: job 0: there is no %s array", __func__, out->lcu ? "picture" : "lcu");
     for (int i = 0; i < num_jobs; i++) {
@@ -439,7 +438,7 @@ extern "C" int svt_amd_picture_detect_batch_launch(SvtAmdContext *ctx, const Svt
 
     DetectJobDev *d_tab;
     DetectReduce *d_red; /* the per-picture reduction the per-LCU kernel accumulates into */
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_detect, sizeof(DetectJobDev), DETECT_RED_BYTES, (void **)&d_tab, (void **)&d_red));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_DETECT, sizeof(DetectJobDev), DETECT_RED_BYTES, (void **)&d_tab, (void **)&d_red));
     static thread_local DetectJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
     for (int i = 0; i < num_jobs; i++) {

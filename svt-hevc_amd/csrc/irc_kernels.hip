@@ -335,13 +335,9 @@ extern "C" int svt_amd_initial_rc_batch_launch(SvtAmdContext *ctx, const SvtAmdI
 {
     SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
-    const int w = luma_width, h = luma_height;
-    const int wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl, groups = (lcus + 3) / 4;
-    if (w < 1 || h < 1 || lcus > SVT_AMD_IRC_MAX_LCUS)
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d (at most %d LCUs)", __func__, w, h, SVT_AMD_IRC_MAX_LCUS);
-    const int cap_lcus = svt_amd_lcu_count(ctx->max_w, ctx->max_h), cap_groups = (cap_lcus + 3) / 4; /* the scratch is sized once, for the largest picture the context was made for */
-    if (lcus > cap_lcus)
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d in a context made for %dx%d", __func__, w, h, ctx->max_w, ctx->max_h);
+    SvtAmdBatchGeometry g;
+    SVT_AMD_TRY(svt_amd_batch_geometry(__func__, ctx, luma_width, luma_height, SVT_AMD_IRC_MAX_LCUS, true, &g));
+    const auto [w, h, wl, hl, lcus, groups, cap_lcus, cap_groups] = g;
     if (!out->checks || !out->motion || !out->lcu || !out->stationary_edge || !out->pm_stationary_edge || !out->picture)
         SVT_AMD_BAD("%s: job 0: there is no %s array", __func__, !out->checks ? "checks" : !out->motion ? "motion" : !out->lcu ? "lcu" :
                     !out->stationary_edge ? "stationary_edge" : !out->pm_stationary_edge ? "pm_stationary_edge" : "picture");
@@ -368,25 +364,17 @@ extern "C" int svt_amd_initial_rc_batch_launch(SvtAmdContext *ctx, const SvtAmdI
         for (int k = 0; k < j.pan_count; k++)
             if (!j.pan_motion[k])
                 SVT_AMD_BAD("%s: job %d: pan_motion[%d] of %d entries is NULL", __func__, i, k, j.pan_count);
-        if (irc_reads_me(j) && !j.me) { /* the records resident in the slot */
-            const DevPicture *c = j.cur_slot >= 0 && j.cur_slot < ctx->num_slots ? &ctx->slots[j.cur_slot] : nullptr;
-            if (!c || !c->valid)
-                SVT_AMD_BAD("%s: job %d reads the ME records of slot %d, which holds no picture", __func__, i, j.cur_slot);
-            if (c->width != w || c->height != h)
-                SVT_AMD_BAD("%s: job %d: slot %d holds a picture of %dx%d, the batch is %dx%d", __func__, i, j.cur_slot, c->width, c->height, w, h);
-            if (!svt_amd_slot_records(ctx, j.cur_slot, 0, w, h))
-                SVT_AMD_BAD("%s: job %d: slot %d holds no complete ME records", __func__, i, j.cur_slot);
-        }
+        if (irc_reads_me(j) && !j.me) /* the records resident in the slot */
+            SVT_AMD_TRY(svt_amd_batch_slot_records(__func__, ctx, i, j.cur_slot, BATCH_REC_ME, w, h));
     }
 
     IrcJobDev *d_tab;
     uint8_t *d_scratch; /* per picture: a word per workgroup of k_irc_lcu, then a vote byte and a flag byte per LCU */
     const size_t lcu_bytes = (size_t)((cap_lcus + 3) & ~3), pic_scratch = (size_t)cap_groups * 4 + 2 * lcu_bytes;
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_irc, sizeof(IrcJobDev), pic_scratch * SVT_AMD_MAX_BATCH, (void **)&d_tab, (void **)&d_scratch));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_IRC, sizeof(IrcJobDev), pic_scratch * SVT_AMD_MAX_BATCH, (void **)&d_tab, (void **)&d_scratch));
     static thread_local IrcJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    hipEvent_t waited[32]; /* the producing launches this call has ordered itself behind: one wait each, however many slots they wrote */
-    int nwaited = 0;
+    SvtAmdRecordsBinder bind;
     const size_t edge_bytes = (size_t)((lcus + 63) & ~63);
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdIrcJob &j = jobs[i];
@@ -394,12 +382,8 @@ extern "C" int svt_amd_initial_rc_batch_launch(SvtAmdContext *ctx, const SvtAmdI
         memset(&d, 0, sizeof(d));
         if (irc_reads_me(j)) {
             d.me = j.me;
-            if (!j.me) {
-                DevPicture *c = &ctx->slots[j.cur_slot];
-                SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, j.cur_slot));
-                SVT_AMD_TRY(svt_amd_records_wait(ctx, c, 0, waited, &nwaited, 32));
-                d.me = c->d_me_out;
-            }
+            if (!j.me)
+                SVT_AMD_TRY(svt_amd_batch_bind_records(ctx, &bind, j.cur_slot, SLOT_ME, (const void **)&d.me));
         }
         d.stats = j.stats;
         for (int k = 0; k < j.edge_count; k++)

@@ -719,13 +719,9 @@ extern "C" int svt_amd_md_config_batch_launch(SvtAmdContext *ctx, const SvtAmdMd
 {
     SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
-    const int w = luma_width, h = luma_height;
-    const int wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl, groups = (lcus + 3) / 4;
-    if (w < 1 || h < 1 || lcus > SVT_AMD_MDC_MAX_LCUS) /* the bound up to which the signed product of the budgeting loop (:1522) is defined */
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d (at most %d LCUs)", __func__, w, h, SVT_AMD_MDC_MAX_LCUS);
-    const int cap_lcus = svt_amd_lcu_count(ctx->max_w, ctx->max_h); /* the scratch is sized once, for the largest picture the context was made for */
-    if (lcus > cap_lcus)
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d in a context made for %dx%d", __func__, w, h, ctx->max_w, ctx->max_h);
+    SvtAmdBatchGeometry g; /* SVT_AMD_MDC_MAX_LCUS: the bound up to which the signed product of the budgeting loop (:1522) is defined */
+    SVT_AMD_TRY(svt_amd_batch_geometry(__func__, ctx, luma_width, luma_height, SVT_AMD_MDC_MAX_LCUS, true, &g));
+    const auto [w, h, wl, hl, lcus, groups, cap_lcus, cap_groups] = g;
     if (!out->lcu || !out->picture)
         SVT_AMD_BAD("%s: job 0: there is no %s array", __func__, out->lcu ? "picture" : "lcu");
     for (int i = 0; i < num_jobs; i++) {
@@ -738,36 +734,24 @@ extern "C" int svt_amd_md_config_batch_launch(SvtAmdContext *ctx, const SvtAmdMd
         if (j.temporal_layer_index > 5 || j.hierarchical_levels > 5 || j.resolution_class > 3 || j.depth_mode > 5 || j.qp > 51)
             SVT_AMD_BAD("%s: job %d: temporal layer %d, hierarchical levels %d, resolution class %d, depth mode %d, QP %d", __func__, i, j.temporal_layer_index,
                         j.hierarchical_levels, j.resolution_class, j.depth_mode, j.qp);
-        if (!j.me) { /* the records resident in the slot */
-            const DevPicture *c = j.cur_slot >= 0 && j.cur_slot < ctx->num_slots ? &ctx->slots[j.cur_slot] : nullptr;
-            if (!c || !c->valid)
-                SVT_AMD_BAD("%s: job %d reads the ME records of slot %d, which holds no picture", __func__, i, j.cur_slot);
-            if (c->width != w || c->height != h)
-                SVT_AMD_BAD("%s: job %d: slot %d holds a picture of %dx%d, the batch is %dx%d", __func__, i, j.cur_slot, c->width, c->height, w, h);
-            if (!svt_amd_slot_records(ctx, j.cur_slot, 0, w, h))
-                SVT_AMD_BAD("%s: job %d: slot %d holds no complete ME records", __func__, i, j.cur_slot);
-        }
+        if (!j.me) /* the records resident in the slot */
+            SVT_AMD_TRY(svt_amd_batch_slot_records(__func__, ctx, i, j.cur_slot, BATCH_REC_ME, w, h));
     }
 
     MdcJobDev *d_tab;
     uint8_t *d_scratch; /* per picture: a score word, then a flag byte per LCU */
     const size_t pic_scratch = (size_t)((cap_lcus + 3) & ~3) * 5;
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_mdc, sizeof(MdcJobDev), pic_scratch * SVT_AMD_MAX_BATCH, (void **)&d_tab, (void **)&d_scratch));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_MDC, sizeof(MdcJobDev), pic_scratch * SVT_AMD_MAX_BATCH, (void **)&d_tab, (void **)&d_scratch));
     static thread_local MdcJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    hipEvent_t waited[32]; /* the producing launches this call has ordered itself behind: one wait each, however many slots they wrote */
-    int nwaited = 0;
+    SvtAmdRecordsBinder bind;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdMdcJob &j = jobs[i];
         MdcJobDev &d = tab[i];
         memset(&d, 0, sizeof(d));
         d.me = j.me;
-        if (!j.me) {
-            DevPicture *c = &ctx->slots[j.cur_slot];
-            SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, j.cur_slot));
-            SVT_AMD_TRY(svt_amd_records_wait(ctx, c, 0, waited, &nwaited, 32));
-            d.me = c->d_me_out;
-        }
+        if (!j.me)
+            SVT_AMD_TRY(svt_amd_batch_bind_records(ctx, &bind, j.cur_slot, SLOT_ME, (const void **)&d.me));
         d.stats = j.stats, d.detect = j.detect, d.sbo_lcu = j.sbo_lcu, d.sbo_pic = j.sbo_pic, d.pic_detect = j.pic_detect, d.noise_pic = j.noise_pic;
         d.stationary = j.stationary_edge;
         d.lcu = out->lcu + (size_t)i * lcus;

@@ -225,7 +225,7 @@ extern "C" size_t svt_amd_md_controls_bytes(uint16_t luma_width, uint16_t luma_h
 static int mdctl_begin(SvtAmdContext *ctx, MdCtlJobDev **d_tab, SvtAmdMdCtlCheck **d_check)
 {
     void *tab, *scratch;
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_mdctl, sizeof(MdCtlJobDev), sizeof(SvtAmdMdCtlCheck), &tab, &scratch));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_MDCTL, sizeof(MdCtlJobDev), sizeof(SvtAmdMdCtlCheck), &tab, &scratch));
     *d_tab = (MdCtlJobDev *)tab, *d_check = (SvtAmdMdCtlCheck *)scratch;
     return SVT_AMD_OK;
 }
@@ -234,12 +234,9 @@ extern "C" int svt_amd_md_controls_batch_launch(SvtAmdContext *ctx, const SvtAmd
 {
     SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
-    const int w = luma_width, h = luma_height;
-    const int wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl, groups = (lcus + 3) / 4;
-    if (w < 1 || h < 1 || lcus > SVT_AMD_MDCTL_MAX_LCUS)
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d (at most %d LCUs)", __func__, w, h, SVT_AMD_MDCTL_MAX_LCUS);
-    if (lcus > svt_amd_lcu_count(ctx->max_w, ctx->max_h))
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d in a context made for %dx%d", __func__, w, h, ctx->max_w, ctx->max_h);
+    SvtAmdBatchGeometry g;
+    SVT_AMD_TRY(svt_amd_batch_geometry(__func__, ctx, luma_width, luma_height, SVT_AMD_MDCTL_MAX_LCUS, true, &g));
+    const auto [w, h, wl, hl, lcus, groups, cap_lcus, cap_groups] = g;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdMdCtlJob &j = jobs[i];
         if (!j.stats || !j.detect || !j.sbo_lcu || !j.sbo_pic)

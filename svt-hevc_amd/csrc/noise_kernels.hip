@@ -192,7 +192,7 @@ extern "C" int svt_amd_noise_detect_batch_launch(SvtAmdContext *ctx, const SvtAm
 
     NoiseJobDev *d_tab;
     unsigned long long *d_red; /* the per-picture partial sums the block kernel accumulates into */
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_noise, sizeof(NoiseJobDev), NOISE_RED_BYTES, (void **)&d_tab, (void **)&d_red));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_NOISE, sizeof(NoiseJobDev), NOISE_RED_BYTES, (void **)&d_tab, (void **)&d_red));
     const size_t b_flat = noise_flat_bytes(w, h);
     static thread_local NoiseJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);

@@ -409,14 +409,9 @@ extern "C" int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmdS
 {
     SVT_AMD_TRY(svt_amd_batch_header(__func__, ctx, jobs, out, num_jobs));
     /* ---- everything is checked before anything is queued ---- */
-    const int w = luma_width, h = luma_height;
-    const int wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl, groups = (lcus + 3) / 4;
-    if (w < 1 || h < 1 || lcus > SBO_MAX_LCUS)
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d (at most %d LCUs)", __func__, w, h, SBO_MAX_LCUS);
-    /* the scratch is sized once, for the largest picture the context was made for */
-    const int cap_lcus = svt_amd_lcu_count(ctx->max_w, ctx->max_h), cap_groups = (cap_lcus + 3) / 4;
-    if (lcus > cap_lcus)
-        SVT_AMD_BAD("%s: job 0: a picture of %dx%d in a context made for %dx%d", __func__, w, h, ctx->max_w, ctx->max_h);
+    SvtAmdBatchGeometry g;
+    SVT_AMD_TRY(svt_amd_batch_geometry(__func__, ctx, luma_width, luma_height, SBO_MAX_LCUS, true, &g));
+    const auto [w, h, wl, hl, lcus, groups, cap_lcus, cap_groups] = g;
     if (!out->lcu || !out->picture)
         SVT_AMD_BAD("%s: job 0: there is no %s array", __func__, out->lcu ? "picture" : "lcu");
     if (!svt_amd_regions_ok(regions_w, regions_h))
@@ -432,27 +427,17 @@ extern "C" int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmdS
                 SVT_AMD_BAD("%s: job %d: zz[%d] of a window of %d pictures is NULL", __func__, i, k, j.zz_count);
         if (j.slice_type > 2 || j.temporal_layer_index > 5 || j.resolution_class > 3)
             SVT_AMD_BAD("%s: job %d: slice type %d, temporal layer %d, resolution class %d", __func__, i, j.slice_type, j.temporal_layer_index, j.resolution_class);
-        if ((j.slice_type != 0 || j.want_qpm) && (!j.me || !j.ois)) { /* the records resident in the slot */
-            const DevPicture *c = j.cur_slot >= 0 && j.cur_slot < ctx->num_slots ? &ctx->slots[j.cur_slot] : nullptr;
-            if (!c || !c->valid)
-                SVT_AMD_BAD("%s: job %d reads the %s records of slot %d, which holds no picture", __func__, i, j.me ? "OIS" : "ME", j.cur_slot);
-            if (c->width != w || c->height != h)
-                SVT_AMD_BAD("%s: job %d: slot %d holds a picture of %dx%d, the batch is %dx%d", __func__, i, j.cur_slot, c->width, c->height, w, h);
-            if (!j.me && !svt_amd_slot_records(ctx, j.cur_slot, 0, w, h))
-                SVT_AMD_BAD("%s: job %d: slot %d holds no complete ME records", __func__, i, j.cur_slot);
-            if (!j.ois && !svt_amd_slot_records(ctx, j.cur_slot, 1, w, h))
-                SVT_AMD_BAD("%s: job %d: slot %d holds no complete OIS records", __func__, i, j.cur_slot);
-        }
+        if ((j.slice_type != 0 || j.want_qpm) && (!j.me || !j.ois)) /* the records resident in the slot */
+            SVT_AMD_TRY(svt_amd_batch_slot_records(__func__, ctx, i, j.cur_slot, (j.me ? 0 : BATCH_REC_ME) | (j.ois ? 0 : BATCH_REC_OIS), w, h));
     }
 
     SboJobDev *d_tab;
     uint8_t *d_scratch; /* per picture: the workgroups' QPM partials, then a flag byte per LCU */
     const size_t pic_scratch = (size_t)cap_groups * SBO_PART_WORDS * 4 + (size_t)cap_groups * 4;
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_sbo, sizeof(SboJobDev), pic_scratch * SVT_AMD_MAX_BATCH, (void **)&d_tab, (void **)&d_scratch));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_SBO, sizeof(SboJobDev), pic_scratch * SVT_AMD_MAX_BATCH, (void **)&d_tab, (void **)&d_scratch));
     static thread_local SboJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    hipEvent_t waited[32]; /* the producing launches this call has ordered itself behind: one wait each, however many slots they wrote */
-    int nwaited = 0;
+    SvtAmdRecordsBinder bind;
     for (int i = 0; i < num_jobs; i++) {
         const SvtAmdSboJob &j = jobs[i];
         SboJobDev &d = tab[i];
@@ -462,18 +447,10 @@ extern "C" int svt_amd_source_ops_batch_launch(SvtAmdContext *ctx, const SvtAmdS
             d.zz[k] = j.zz[k];
         if (j.slice_type != 0 || j.want_qpm) {
             d.me = j.me, d.ois = j.ois;
-            if (!j.me || !j.ois) {
-                DevPicture *c = &ctx->slots[j.cur_slot];
-                SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, j.cur_slot));
-                if (!j.me) {
-                    SVT_AMD_TRY(svt_amd_records_wait(ctx, c, 0, waited, &nwaited, 32));
-                    d.me = c->d_me_out;
-                }
-                if (!j.ois) {
-                    SVT_AMD_TRY(svt_amd_records_wait(ctx, c, 1, waited, &nwaited, 32));
-                    d.ois = c->d_ois_out;
-                }
-            }
+            if (!j.me)
+                SVT_AMD_TRY(svt_amd_batch_bind_records(ctx, &bind, j.cur_slot, SLOT_ME, (const void **)&d.me));
+            if (!j.ois)
+                SVT_AMD_TRY(svt_amd_batch_bind_records(ctx, &bind, j.cur_slot, SLOT_OIS, (const void **)&d.ois));
         }
         d.lcu = out->lcu + (size_t)i * lcus;
         d.pic = out->picture + i;

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void k_side_zz(const SideJobDev *__restrict__ 
     }
 }
 
-/* ---- what the four batched picture-analysis entries share on the host (pa_batch.h) ---- */
+/* ---- what the batched entries share on the host (pa_batch.h) ---- */
 
 int svt_amd_batch_header(const char *entry, const SvtAmdContext *ctx, const void *jobs, const void *out, int num_jobs)
 {
@@ -250,9 +250,10 @@ int svt_amd_batch_slot(const char *entry, const SvtAmdContext *ctx, int job, int
 static thread_local uint8_t seen[4096]; /* the slots this call has waited on; a context of more slots waits once per use instead */
 
 /* the first device call of a launcher.  The entry's descriptor table (SVT_AMD_MAX_BATCH records) and, behind it, the scratch its kernels accumulate into are
- * one allocation the context owns (*owned: the entry's member of the context), made at the entry's first call and freed by svt_amd_context_destroy. */
-int svt_amd_batch_begin(SvtAmdContext *ctx, void **owned, size_t record_bytes, size_t scratch_bytes, void **d_tab, void **d_scratch)
+ * one allocation the context owns (d_batch[which]), made at the entry's first call and freed by svt_amd_context_destroy. */
+int svt_amd_batch_begin(SvtAmdContext *ctx, SvtAmdBatchEntry which, size_t record_bytes, size_t scratch_bytes, void **d_tab, void **d_scratch)
 {
+    void **owned = &ctx->d_batch[which];
     HIP_TRY(hipSetDevice(ctx->device));
     if (!*owned)
         HIP_TRY(hipMalloc(owned, record_bytes * SVT_AMD_MAX_BATCH + scratch_bytes));
@@ -270,6 +271,46 @@ int svt_amd_batch_wait_slot(SvtAmdContext *ctx, int slot)
     if (!*s)
         HIP_TRY(hipStreamWaitEvent(svt_amd_ctx_stream(ctx), ctx->slots[slot].ev_ready, 0));
     *s = 1;
+    return SVT_AMD_OK;
+}
+
+/* the size of a batch that takes it as arguments.  The LCU bound of the entry's kernels is tested first: only a picture within it lets the context be read.
+ * must_fit: a picture of more LCUs than the largest the context was made for is refused - per-LCU scratch is sized once, for that one. */
+int svt_amd_batch_geometry(const char *entry, const SvtAmdContext *ctx, int luma_width, int luma_height, int max_lcus, bool must_fit, SvtAmdBatchGeometry *g)
+{
+    const int w = luma_width, h = luma_height, wl = (w + 63) / 64, hl = (h + 63) / 64, lcus = wl * hl;
+    if (w < 1 || h < 1 || lcus > max_lcus)
+        SVT_AMD_BAD("%s: job 0: a picture of %dx%d (at most %d LCUs)", entry, w, h, max_lcus);
+    const int cap_lcus = svt_amd_lcu_count(ctx->max_w, ctx->max_h);
+    if (must_fit && lcus > cap_lcus)
+        SVT_AMD_BAD("%s: job 0: a picture of %dx%d in a context made for %dx%d", entry, w, h, ctx->max_w, ctx->max_h);
+    *g = SvtAmdBatchGeometry{w, h, wl, hl, lcus, (lcus + 3) / 4, cap_lcus, (cap_lcus + 3) / 4};
+    return SVT_AMD_OK;
+}
+
+/* a job reads the records of `kinds` (BATCH_REC_ME, BATCH_REC_OIS or both) resident in a slot: it has to hold a picture of the batch's size and complete
+ * records of it (svt_amd_slot_records) */
+int svt_amd_batch_slot_records(const char *entry, SvtAmdContext *ctx, int job, int slot, int kinds, int w, int h)
+{
+    const DevPicture *c = slot >= 0 && slot < ctx->num_slots ? &ctx->slots[slot] : nullptr;
+    if (!c || !c->valid)
+        SVT_AMD_BAD("%s: job %d reads the %s records of slot %d, which holds no picture", entry, job, kinds & BATCH_REC_ME ? "ME" : "OIS", slot);
+    if (c->width != w || c->height != h)
+        SVT_AMD_BAD("%s: job %d: slot %d holds a picture of %dx%d, the batch is %dx%d", entry, job, slot, c->width, c->height, w, h);
+    for (int kind = SLOT_ME; kind <= SLOT_OIS; kind++)
+        if ((kinds >> kind & 1) && !svt_amd_slot_records(ctx, slot, kind, w, h))
+            SVT_AMD_BAD("%s: job %d: slot %d holds no complete %s records", entry, job, slot, kind == SLOT_ME ? "ME" : "OIS");
+    return SVT_AMD_OK;
+}
+
+/* ... and where its descriptor is filled: the launch waits for the slot's planes (svt_amd_batch_wait_slot) and for the launch that wrote the records, once per
+ * distinct producing launch and call (svt_amd_records_wait), and reads *records in place.  kind: SLOT_ME or SLOT_OIS. */
+int svt_amd_batch_bind_records(SvtAmdContext *ctx, SvtAmdRecordsBinder *b, int slot, int kind, const void **records)
+{
+    DevPicture *c = &ctx->slots[slot];
+    SVT_AMD_TRY(svt_amd_batch_wait_slot(ctx, slot));
+    SVT_AMD_TRY(svt_amd_records_wait(ctx, c, kind, b->waited, &b->nwaited, 32));
+    *records = kind == SLOT_ME ? (const void *)c->d_me_out : (const void *)c->d_ois_out;
     return SVT_AMD_OK;
 }
 
@@ -343,7 +384,7 @@ extern "C" int svt_amd_side_stats_batch_launch(SvtAmdContext *ctx, const SvtAmdS
 
     SideJobDev *d_tab;
     unsigned long long *d_sums; /* the per-region sums the histogram kernels accumulate into */
-    SVT_AMD_TRY(svt_amd_batch_begin(ctx, &ctx->d_side, sizeof(SideJobDev), SIDE_SUMS_BYTES, (void **)&d_tab, (void **)&d_sums));
+    SVT_AMD_TRY(svt_amd_batch_begin(ctx, BATCH_SIDE, sizeof(SideJobDev), SIDE_SUMS_BYTES, (void **)&d_tab, (void **)&d_sums));
     const size_t b_stats = (size_t)lcus * sizeof(SvtAmdPaLcuStats), b_hist = (size_t)regions * 256 * 4;
     static thread_local SideJobDev tab[SVT_AMD_MAX_BATCH];
     hipStream_t st = svt_amd_ctx_stream(ctx);

@@ -79,6 +79,11 @@ struct PackSrc {
     const uint32_t *me, *ois;      /* the slot's d_me_out / d_ois_out */
 };
 
+/* the batched, stream-ordered entries of pa_batch.h: each owns one device allocation of the context (SvtAmdContext.d_batch), what follows the descriptor table
+ * in it is the entry's own.  side / chroma: per-region sums; detect / noise: a per-picture reduction; sbo: per-workgroup partials and per-LCU flags; mdc: per-LCU
+ * scores and flags; irc: per-workgroup vote totals, per-LCU votes and flags; mdctl: the check record of a bound controls array */
+enum SvtAmdBatchEntry { BATCH_SIDE, BATCH_CHROMA, BATCH_DETECT, BATCH_NOISE, BATCH_SBO, BATCH_MDC, BATCH_IRC, BATCH_MDCTL, BATCH_ENTRIES };
+
 struct SvtAmdContext {
     int device;
     SvtAmdContext *parent;         /* lane (svt_amd_context_fork): shares the parent's picture slots, owns everything else */
@@ -119,15 +124,8 @@ struct SvtAmdContext {
     int launch_next;
     unsigned long long mark_records, mark_waits; /* svt_amd_debug_launch_markers */
     void *d_pack_src;              /* device table of the pack kernels' per-picture sources (svt_amd_records_pack_batch_async) */
-    void *d_side;                  /* descriptor table + per-region sums of svt_amd_side_stats_batch_launch (side_kernels.hip), allocated at its first call */
-    void *d_chroma;                /* descriptor table + per-region sums of svt_amd_chroma_stats_batch_launch (detect_kernels.hip), allocated at its first call */
-    void *d_detect;                /* descriptor table + per-picture reduction of svt_amd_picture_detect_batch_launch (detect_kernels.hip), allocated at its first call */
-    void *d_noise;                 /* descriptor table + per-picture reduction of svt_amd_noise_detect_batch_launch (noise_kernels.hip), allocated at its first call */
-    void *d_sbo;                   /* descriptor table + per-LCU / per-workgroup partials of svt_amd_source_ops_batch_launch (sbo_kernels.hip), allocated at its first call */
-    void *d_mdc;                   /* descriptor table + per-LCU scores and flags of svt_amd_md_config_batch_launch (mdc_kernels.hip), allocated at its first call */
-    void *d_irc;                   /* descriptor table + per-LCU votes and flags, per-workgroup vote totals of svt_amd_initial_rc_batch_launch (irc_kernels.hip), allocated at its first call */
-    void *d_mdctl;                 /* descriptor table of svt_amd_md_controls_batch_launch + the check record of a bound controls array (mdctl_kernels.hip), allocated at first use */
-    void *d_tmvp;                  /* per-LCU intra-area sums of svt_amd_motion_field_launch (tmvp_kernels.hip), allocated at its first call */
+    void *d_batch[BATCH_ENTRIES];  /* per batched entry: its descriptor table + the scratch its kernels accumulate into, allocated at its first call (svt_amd_batch_begin) */
+    void *d_tmvp;                 /* per-LCU intra-area sums of svt_amd_motion_field_launch (tmvp_kernels.hip), allocated at its first call */
     /* multi-GPU exchange (comm.hip): RCCL communicator + the all-gather buffer (one slot per rank) */
     void *comm;
     int comm_world, comm_rank;
@@ -143,7 +141,9 @@ int svt_amd_ctx_scratch(SvtAmdContext *ctx, size_t bytes, uint8_t **out);
 /* context.hip: the device's view of a range inside a svt_amd_host_register'ed buffer, or nullptr */
 const void *svt_amd_registered_device_ptr(const void *h_ptr, size_t bytes);
 
-/* context.hip: what a consumer of the records resident in a slot goes through (the mode decision, the source-based operations), in this order.
+/* context.hip: what a consumer of the records resident in a slot goes through, in this order.  The mode-decision call (md_kernels.hip) calls all three itself;
+ * the batched readers (source-based operations, mode-decision configuration, initial rate control) go through the first two by way of
+ * svt_amd_batch_slot_records and svt_amd_batch_bind_records (pa_batch.h) and leave no read mark.
  * svt_amd_slot_records: the device pointer of the slot's ME (which == 0) / OIS (which == 1) records, or nullptr unless the slot is in range, holds a picture of
  * w x h and complete records of it.  It sets no error text: the caller refuses in its own words.
  * svt_amd_records_wait: the stream of `ctx` orders itself behind the launch that wrote them (no wait where that ran on this very lane, or where there is nothing

@@ -19,6 +19,23 @@ def refused(lib, rc, entry, what=None):
     assert lib.svt_amd_last_error().startswith(entry.encode() + b": "), (lib.svt_amd_last_error(), what)
 
 
+def refused_as(lib, rc, text):
+    """the call was refused with exactly this error text"""
+    assert rc == BAD_PARAM and lib.svt_amd_last_error() == text.encode(), (rc, lib.svt_amd_last_error())
+
+
+def round_up(n):
+    """the next multiple of 256: where the next array of a device buffer begins"""
+    return (n + 255) & ~255
+
+
+def markers(lib, ctx):
+    """(completion records, waits on other lanes' records) the context has issued since it was made"""
+    r, w = C.c_ulonglong(), C.c_ulonglong()
+    ok(lib, lib.svt_amd_debug_launch_markers(ctx, C.byref(r), C.byref(w)))
+    return r.value, w.value
+
+
 def make_context(lib, w, h, slots):
     ctx = vp()
     ok(lib, lib.svt_amd_context_create(0, w, h, slots, C.byref(ctx)))

@@ -14,7 +14,7 @@ import sbo_records as R
 import svtlib as S
 from golden_util import load_case
 from gpu_util import upload
-from pa_batch_util import BAD_PARAM, DeviceBuffer, ok
+from pa_batch_util import BAD_PARAM, DeviceBuffer, markers, ok
 from test_gpu_source_ops import Pictures, Results, launch
 
 pytestmark = pytest.mark.gpu
@@ -33,13 +33,6 @@ def lib(product):
     product.svt_amd_debug_launch_markers.restype = C.c_int
     product.svt_amd_debug_launch_markers.argtypes = [vp, C.POINTER(ull), C.POINTER(ull)]
     return product
-
-
-def markers(lib, ctx):
-    """(completion records, waits on other lanes' records) the context has issued since it was made"""
-    r, w = ull(), ull()
-    ok(lib, lib.svt_amd_debug_launch_markers(ctx, C.byref(r), C.byref(w)))
-    return r.value, w.value
 
 
 def controls(w, h):

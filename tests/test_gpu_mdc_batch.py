@@ -16,7 +16,7 @@ import sbo_records as SR
 import sidelib as L
 import svtlib as S
 from gpu_util import default_params, upload
-from pa_batch_util import DeviceBuffer, is_sentinel, make_context, ok, refused
+from pa_batch_util import DeviceBuffer, is_sentinel, make_context, markers, ok, refused, round_up as _up
 from test_mdc_cpu import CASES, load_case, tables
 
 pytestmark = pytest.mark.gpu
@@ -27,16 +27,6 @@ LAMBDA, SPLIT_BITS = 261, [12171, 78934]        # for the seeded variants: any S
 @pytest.fixture(scope="module")
 def lib(product):
     return M.declare(product)
-
-
-def _up(n):
-    return (n + 255) & ~255
-
-
-def markers(lib, ctx):
-    r, w = C.c_ulonglong(), C.c_ulonglong()
-    ok(lib, lib.svt_amd_debug_launch_markers(ctx, C.byref(r), C.byref(w)))
-    return r.value, w.value
 
 
 class Pictures:

@@ -23,7 +23,7 @@ import sbo_records as SR
 import sidelib as L
 import svtlib as S
 from gpu_util import default_params, upload
-from pa_batch_util import BAD_PARAM, SENTINEL, DeviceBuffer, is_sentinel, make_context, ok, refused
+from pa_batch_util import BAD_PARAM, SENTINEL, DeviceBuffer, is_sentinel, make_context, markers, ok, refused, round_up as _up
 from test_mdctl_cpu import CASES, load_case, same
 from test_oracle_md_golden import inter_inputs
 
@@ -36,16 +36,6 @@ KINDS = M.POINTER_FIELDS
 @pytest.fixture(scope="module")
 def lib(product):
     return M.declare(product)
-
-
-def _up(n):
-    return (n + 255) & ~255
-
-
-def markers(lib, ctx):
-    r, w = C.c_ulonglong(), C.c_ulonglong()
-    ok(lib, lib.svt_amd_debug_launch_markers(ctx, C.byref(r), C.byref(w)))
-    return r.value, w.value
 
 
 class Pictures:

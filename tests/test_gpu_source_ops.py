@@ -14,7 +14,7 @@ import sbo_records as R
 import sidelib as L
 import svtlib as S
 from gpu_util import default_params, upload
-from pa_batch_util import DeviceBuffer, is_sentinel, make_context, ok, refused
+from pa_batch_util import DeviceBuffer, is_sentinel, make_context, ok, refused, round_up as _up
 from test_sbo_cpu import CASES, load_case
 
 pytestmark = pytest.mark.gpu
@@ -24,10 +24,6 @@ RECORDS = ("stats", "ref_stats", "chroma", "detect", "histogram", "me", "ois")
 @pytest.fixture(scope="module")
 def lib(product):
     return R.declare(PN.declare(L.declare(product)))
-
-
-def _up(n):
-    return (n + 255) & ~255
 
 
 class Pictures:

@@ -2,16 +2,14 @@
 ctypes views (tests/irclib.py) and the numpy layouts (tests/irc_records.py) agree on sizes and offsets, the checks that need no device answer without one, and
 svt_amd_initial_rc_bytes is the documented arithmetic."""
 import ctypes as C
-import os
-import subprocess
 
-import numpy as np
 import pytest
 
 import irc_records as R
 import irclib as M
 import svtlib as S
-from pa_batch_util import refused
+from abi_util import compiles, exported, open_library, view_matches_dtype
+from pa_batch_util import refused, refused_as
 
 VIEWS = (("SvtAmdIrcJob", M.IrcJob), ("SvtAmdIrcChecks", M.IrcChecks), ("SvtAmdIrcMotion", M.IrcMotion), ("SvtAmdIrcLcu", M.IrcLcu), ("SvtAmdIrcPic", M.IrcPic),
          ("SvtAmdIrcArrays", M.IrcArrays))
@@ -19,20 +17,11 @@ VIEWS = (("SvtAmdIrcJob", M.IrcJob), ("SvtAmdIrcChecks", M.IrcChecks), ("SvtAmdI
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return M.declare(C.CDLL(S.PRODUCT_SO))
-
-
-def _compiles(tmp_path, std, checks):
-    src = tmp_path / "t.c"
-    src.write_text('#include <stddef.h>\n#include "svt_hevc_amd.h"\n' + "".join('_Static_assert(%s, "%s");\n' % (c, c) for c in checks) + 'int main(void) { return 0; }\n')
-    subprocess.check_call(["gcc", "-std=" + std, "-Wall", "-Werror", "-I", os.path.join(S.ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    return open_library(M.declare)
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert {"svt_amd_initial_rc_batch_launch", "svt_amd_initial_rc_bytes"} <= exported
+    assert {"svt_amd_initial_rc_batch_launch", "svt_amd_initial_rc_bytes"} <= exported()
 
 
 def test_structure_sizes_in_c99(tmp_path):
@@ -42,23 +31,17 @@ def test_structure_sizes_in_c99(tmp_path):
     checks = ["sizeof(%s) == %d" % (name, C.sizeof(view)) for name, view in VIEWS]
     checks += ["SVT_AMD_IRC_CHECKS == 0 && SVT_AMD_IRC_MOTION == 1 && SVT_AMD_IRC_LCU == 2 && SVT_AMD_IRC_STATIONARY == 3 && SVT_AMD_IRC_PM_STATIONARY == 4",
                "SVT_AMD_IRC_PICTURE == 5", "SVT_AMD_IRC_MAX_LCUS == %d" % M.MAX_LCUS]
-    _compiles(tmp_path, "c99", checks)
+    compiles(tmp_path, "c99", checks)
 
 
 def test_header_offsets_field_by_field(tmp_path):
     """every field of the header's structures lies where the ctypes view has it"""
-    _compiles(tmp_path, "c11", ["offsetof(%s, %s) == %d" % (name, f, getattr(view, f).offset) for name, view in VIEWS for f, _ in view._fields_])
+    compiles(tmp_path, "c11", ["offsetof(%s, %s) == %d" % (name, f, getattr(view, f).offset) for name, view in VIEWS for f, _ in view._fields_])
 
 
 @pytest.mark.parametrize("view,dtype", [(M.IrcChecks, R.CHECKS_DTYPE), (M.IrcMotion, R.MOTION_DTYPE), (M.IrcLcu, R.IRC_LCU_DTYPE), (M.IrcPic, R.IRC_PIC_DTYPE)])
 def test_ctypes_views_have_the_dtypes_offsets(view, dtype):
-    assert C.sizeof(view) == dtype.itemsize
-    assert [f for f, _ in view._fields_] == list(dtype.names)
-    for f, t in view._fields_:
-        sub, offset = dtype.fields[f][:2]
-        assert getattr(view, f).offset == offset and C.sizeof(t) == sub.itemsize, f
-        scalar = getattr(t, "_type_", t) if hasattr(t, "_length_") else t
-        assert np.dtype(scalar) == sub.base.newbyteorder("="), f
+    view_matches_dtype(view, dtype)
 
 
 def test_job_layout():
@@ -74,6 +57,9 @@ def test_bad_headers_are_refused_without_a_device(lib):
         refused(lib, lib.svt_amd_initial_rc_batch_launch(fake, jobs, n, 64, 64, C.byref(table)), M.ENTRY, n)
     refused(lib, lib.svt_amd_initial_rc_batch_launch(fake, None, 1, 64, 64, C.byref(table)), M.ENTRY)
     refused(lib, lib.svt_amd_initial_rc_batch_launch(fake, jobs, 1, 64, 64, None), M.ENTRY)
+    # ... nor for the picture's size: the bound of the kernels is tested before the context's own
+    refused_as(lib, lib.svt_amd_initial_rc_batch_launch(fake, jobs, 1, 0, 64, C.byref(table)), M.ENTRY + ": job 0: a picture of 0x64 (at most 16384 LCUs)")
+    refused_as(lib, lib.svt_amd_initial_rc_batch_launch(fake, jobs, 1, 16384, 16384, C.byref(table)), M.ENTRY + ": job 0: a picture of 16384x16384 (at most 16384 LCUs)")
 
 
 @pytest.mark.parametrize("w,h", [(64, 64), (416, 240), (2112, 1152), (3840, 2160)])

@@ -2,28 +2,23 @@
 header, the ctypes views (tests/mdclib.py) and the numpy layouts (tests/mdc_records.py) agree on sizes and offsets, the checks that need no device answer
 without one, and svt_amd_md_config_bytes is the documented arithmetic."""
 import ctypes as C
-import os
-import subprocess
 
-import numpy as np
 import pytest
 
 import mdc_records as R
 import mdclib as M
 import svtlib as S
-from pa_batch_util import refused
+from abi_util import compiles, exported, open_library, view_matches_dtype
+from pa_batch_util import refused, refused_as
 
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return M.declare(C.CDLL(S.PRODUCT_SO))
+    return open_library(M.declare)
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert {"svt_amd_md_config_batch_launch", "svt_amd_md_config_bytes"} <= exported
+    assert {"svt_amd_md_config_batch_launch", "svt_amd_md_config_bytes"} <= exported()
 
 
 def test_structure_sizes_in_c99(tmp_path):
@@ -32,29 +27,19 @@ def test_structure_sizes_in_c99(tmp_path):
     checks = ["sizeof(SvtAmdMdcJob) == %d" % C.sizeof(M.MdcJob), "sizeof(SvtAmdMdcLcu) == %d" % R.MDC_LCU_DTYPE.itemsize,
               "sizeof(SvtAmdMdcPic) == %d" % R.MDC_PIC_DTYPE.itemsize, "sizeof(SvtAmdMdcArrays) == 2 * sizeof(void *)", "SVT_AMD_MDC_LCU == 0 && SVT_AMD_MDC_PICTURE == 1",
               "SVT_AMD_MDC_MAX_LCUS == %d" % M.MAX_LCUS]
-    src = tmp_path / "t.c"
-    src.write_text('#include "svt_hevc_amd.h"\n' + "".join('_Static_assert(%s, "%s");\n' % (c, c) for c in checks) + 'int main(void) { return 0; }\n')
-    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(S.ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    compiles(tmp_path, "c99", checks)
 
 
 def test_header_offsets_field_by_field(tmp_path):
     """every field of the header's three structures lies where the ctypes view has it"""
     checks = ["offsetof(%s, %s) == %d" % (name, f, getattr(view, f).offset) for name, view in (("SvtAmdMdcJob", M.MdcJob), ("SvtAmdMdcLcu", M.MdcLcu), ("SvtAmdMdcPic", M.MdcPic))
               for f, _ in view._fields_]
-    src = tmp_path / "t.c"
-    src.write_text('#include <stddef.h>\n#include "svt_hevc_amd.h"\n' + "".join('_Static_assert(%s, "%s");\n' % (c, c) for c in checks) + 'int main(void) { return 0; }\n')
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(S.ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    compiles(tmp_path, "c11", checks)
 
 
 @pytest.mark.parametrize("view,dtype", [(M.MdcLcu, R.MDC_LCU_DTYPE), (M.MdcPic, R.MDC_PIC_DTYPE)])
 def test_ctypes_views_have_the_dtypes_offsets(view, dtype):
-    assert C.sizeof(view) == dtype.itemsize
-    assert [f for f, _ in view._fields_] == list(dtype.names)
-    for f, t in view._fields_:
-        sub, offset = dtype.fields[f][:2]
-        assert getattr(view, f).offset == offset and C.sizeof(t) == sub.itemsize, f
-        scalar = getattr(t, "_type_", t) if hasattr(t, "_length_") else t
-        assert np.dtype(scalar) == sub.base.newbyteorder("="), f
+    view_matches_dtype(view, dtype)
 
 
 def test_the_lcu_record_begins_like_the_mode_decision_record():
@@ -79,6 +64,9 @@ def test_bad_headers_are_refused_without_a_device(lib):
         refused(lib, lib.svt_amd_md_config_batch_launch(fake, jobs, n, 64, 64, C.byref(table)), M.ENTRY, n)
     refused(lib, lib.svt_amd_md_config_batch_launch(fake, None, 1, 64, 64, C.byref(table)), M.ENTRY)
     refused(lib, lib.svt_amd_md_config_batch_launch(fake, jobs, 1, 64, 64, None), M.ENTRY)
+    # ... nor for the picture's size: the bound of the kernels is tested before the context's own
+    refused_as(lib, lib.svt_amd_md_config_batch_launch(fake, jobs, 1, 0, 64, C.byref(table)), M.ENTRY + ": job 0: a picture of 0x64 (at most 13854 LCUs)")
+    refused_as(lib, lib.svt_amd_md_config_batch_launch(fake, jobs, 1, 7552, 7552, C.byref(table)), M.ENTRY + ": job 0: a picture of 7552x7552 (at most 13854 LCUs)")   # 118 x 118
 
 
 @pytest.mark.parametrize("w,h", [(64, 64), (416, 240), (3840, 2160)])

@@ -2,10 +2,7 @@
 header, the ctypes views (tests/mdctllib.py) and the numpy layouts (svtlib.MD_LCU_DTYPE, mdctl_records.CHECK_DTYPE) agree on sizes and offsets, the head of
 SvtAmdMdcLcu is the head of SvtAmdMdLcu, the checks that need no device answer without one, and svt_amd_md_controls_bytes is the documented arithmetic."""
 import ctypes as C
-import os
-import subprocess
 
-import numpy as np
 import pytest
 
 import mdclib as MM
@@ -13,27 +10,19 @@ import mdc_records as MR
 import mdctl_records as R
 import mdctllib as M
 import svtlib as S
-from pa_batch_util import BAD_PARAM, refused
+from abi_util import compiles, exported, open_library, view_matches_dtype
+from pa_batch_util import BAD_PARAM, refused, refused_as
 
 VIEWS = (("SvtAmdMdCtlJob", M.MdCtlJob), ("SvtAmdMdLcu", M.MdLcu), ("SvtAmdMdCtlCheck", M.MdCtlCheck), ("SvtAmdMdcLcu", MM.MdcLcu))
 
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return M.declare(C.CDLL(S.PRODUCT_SO))
-
-
-def _compiles(tmp_path, std, checks):
-    src = tmp_path / "t.c"
-    src.write_text('#include <stddef.h>\n#include "svt_hevc_amd.h"\n' + "".join('_Static_assert(%s, "%s");\n' % (c, c) for c in checks) + 'int main(void) { return 0; }\n')
-    subprocess.check_call(["gcc", "-std=" + std, "-Wall", "-Werror", "-I", os.path.join(S.ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    return open_library(M.declare)
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert {"svt_amd_md_controls_batch_launch", "svt_amd_md_controls_bytes", "svt_amd_md_picture_set_controls", "svt_amd_debug_md_controls_check"} <= exported
+    assert {"svt_amd_md_controls_batch_launch", "svt_amd_md_controls_bytes", "svt_amd_md_picture_set_controls", "svt_amd_debug_md_controls_check"} <= exported()
 
 
 def test_structure_sizes_in_c99(tmp_path):
@@ -42,23 +31,17 @@ def test_structure_sizes_in_c99(tmp_path):
     assert (S.MD_LCU_DTYPE.itemsize, R.CHECK_DTYPE.itemsize) == (191, 88)
     checks = ["sizeof(%s) == %d" % (name, C.sizeof(view)) for name, view in VIEWS]
     checks += ["SVT_AMD_MDCTL_LCU == 0", "SVT_AMD_MDCTL_MAX_LCUS == %d" % M.MAX_LCUS, "SVT_AMD_MD_LEAVES == 85"]
-    _compiles(tmp_path, "c99", checks)
+    compiles(tmp_path, "c99", checks)
 
 
 def test_header_offsets_field_by_field(tmp_path):
     """every field of the header's structures lies where the ctypes view has it"""
-    _compiles(tmp_path, "c11", ["offsetof(%s, %s) == %d" % (name, f, getattr(view, f).offset) for name, view in VIEWS for f, _ in view._fields_])
+    compiles(tmp_path, "c11", ["offsetof(%s, %s) == %d" % (name, f, getattr(view, f).offset) for name, view in VIEWS for f, _ in view._fields_])
 
 
 @pytest.mark.parametrize("view,dtype", [(M.MdLcu, S.MD_LCU_DTYPE), (M.MdCtlCheck, R.CHECK_DTYPE), (MM.MdcLcu, MR.MDC_LCU_DTYPE)])
 def test_ctypes_views_have_the_dtypes_offsets(view, dtype):
-    assert C.sizeof(view) == dtype.itemsize
-    assert [f for f, _ in view._fields_] == list(dtype.names)
-    for f, t in view._fields_:
-        sub, offset = dtype.fields[f][:2]
-        assert getattr(view, f).offset == offset and C.sizeof(t) == sub.itemsize, f
-        scalar = getattr(t, "_type_", t) if hasattr(t, "_length_") else t
-        assert np.dtype(scalar) == sub.base.newbyteorder("="), f
+    view_matches_dtype(view, dtype)
 
 
 def test_the_head_of_the_configuration_record_is_the_head_of_the_control_record(tmp_path):
@@ -68,7 +51,7 @@ def test_the_head_of_the_configuration_record_is_the_head_of_the_control_record(
     for f in head:
         assert getattr(M.MdLcu, f).offset == getattr(MM.MdcLcu, f).offset == S.MD_LCU_DTYPE.fields[f][1] == MR.MDC_LCU_DTYPE.fields[f][1]
     assert M.MdLcu.tile_left.offset == MM.MdcLcu.lcu_md_mode.offset == R.HEAD_BYTES == 171 and MM.MdcLcu.aura_status.offset == 172
-    _compiles(tmp_path, "c11", ["offsetof(SvtAmdMdLcu, %s) == offsetof(SvtAmdMdcLcu, %s)" % (f, f) for f in head] +
+    compiles(tmp_path, "c11", ["offsetof(SvtAmdMdLcu, %s) == offsetof(SvtAmdMdcLcu, %s)" % (f, f) for f in head] +
               ["offsetof(SvtAmdMdLcu, tile_left) == 171 && offsetof(SvtAmdMdcLcu, lcu_md_mode) == 171"])
 
 
@@ -87,6 +70,8 @@ def test_bad_headers_are_refused_without_a_device(lib):
     refused(lib, lib.svt_amd_md_controls_batch_launch(fake, None, 1, 64, 64, out), M.ENTRY)
     refused(lib, lib.svt_amd_md_controls_batch_launch(fake, jobs, 1, 64, 64, None), M.ENTRY)
     refused(lib, lib.svt_amd_md_controls_batch_launch(fake, jobs, 1, 8256, 8192, out), M.ENTRY, "more than 16,384 LCUs")   # 129 x 128; the context is not read yet
+    refused_as(lib, lib.svt_amd_md_controls_batch_launch(fake, jobs, 1, 0, 64, out), M.ENTRY + ": job 0: a picture of 0x64 (at most 16384 LCUs)")
+    refused_as(lib, lib.svt_amd_md_controls_batch_launch(fake, jobs, 1, 16384, 16384, out), M.ENTRY + ": job 0: a picture of 16384x16384 (at most 16384 LCUs)")
     assert lib.svt_amd_md_picture_set_controls(None, fake, out) == BAD_PARAM and lib.svt_amd_md_picture_set_controls(fake, None, out) == BAD_PARAM
     assert lib.svt_amd_debug_md_controls_check(None, out, 1, 0, 0, out) == BAD_PARAM
 

@@ -12,7 +12,8 @@ import pytest
 import pa_detect_numpy as N
 import pa_detect_pictures as P
 import svtlib as S
-from pa_batch_util import refused
+from abi_util import exported, open_library
+from pa_batch_util import refused, refused_as
 from test_oracle_pa import oracle_picture as pa_oracle
 
 CASES = sorted(os.path.basename(p)[9:-4] for p in glob.glob(os.path.join(S.GOLDEN_DIR, "padetect_*.npz")))
@@ -26,8 +27,7 @@ def load_case(name):
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return N.declare(C.CDLL(S.PRODUCT_SO))
+    return open_library(N.declare)
 
 
 def test_have_the_four_cases():
@@ -35,9 +35,7 @@ def test_have_the_four_cases():
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert {"svt_amd_chroma_stats_batch_launch", "svt_amd_chroma_stats_bytes", "svt_amd_picture_detect_batch_launch", "svt_amd_picture_detect_bytes"} <= exported
+    assert {"svt_amd_chroma_stats_batch_launch", "svt_amd_chroma_stats_bytes", "svt_amd_picture_detect_batch_launch", "svt_amd_picture_detect_bytes"} <= exported()
 
 
 def test_record_layouts(tmp_path):
@@ -83,6 +81,10 @@ def test_bad_parameters_are_refused_without_a_device(lib):
         assert b"1..256 jobs" in lib.svt_amd_last_error()
     refused(lib, lib.svt_amd_chroma_stats_batch_launch(fake, None, 1, 416, 240, 4, 4, C.byref(ca)), "svt_amd_chroma_stats_batch_launch")
     refused(lib, lib.svt_amd_picture_detect_batch_launch(fake, dj, 1, 416, 240, None), "svt_amd_picture_detect_batch_launch")
+    # ... nor for the picture's size: the bound of the kernels is tested first
+    refused_as(lib, lib.svt_amd_picture_detect_batch_launch(fake, dj, 1, 0, 64, C.byref(da)), "svt_amd_picture_detect_batch_launch: job 0: a picture of 0x64 (at most 16384 LCUs)")
+    refused_as(lib, lib.svt_amd_picture_detect_batch_launch(fake, dj, 1, 16384, 16384, C.byref(da)),
+               "svt_amd_picture_detect_batch_launch: job 0: a picture of 16384x16384 (at most 16384 LCUs)")
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -13,6 +13,7 @@ import pytest
 import pa_noise_numpy as N
 import pa_noise_pictures as P
 import svtlib as S
+from abi_util import exported, open_library
 from pa_batch_util import refused
 
 CASES = sorted(os.path.basename(p)[8:-4] for p in glob.glob(os.path.join(S.GOLDEN_DIR, "panoise_*.npz")))
@@ -27,8 +28,7 @@ def load_case(name):
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return N.declare(C.CDLL(S.PRODUCT_SO))
+    return open_library(N.declare)
 
 
 def test_have_the_eight_cases():
@@ -40,9 +40,7 @@ def test_have_the_eight_cases():
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert {"svt_amd_noise_detect_batch_launch", "svt_amd_noise_detect_bytes"} <= exported
+    assert {"svt_amd_noise_detect_batch_launch", "svt_amd_noise_detect_bytes"} <= exported()
 
 
 def test_record_layouts(tmp_path):

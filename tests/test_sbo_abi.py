@@ -2,26 +2,22 @@
 Python mirrors and the header agree on sizes and offsets, the checks that need no device answer without one, and svt_amd_source_ops_bytes is the documented
 arithmetic."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import sbo_records as R
 import svtlib as S
-from pa_batch_util import refused
+from abi_util import compiles, exported, open_library
+from pa_batch_util import refused, refused_as
 
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return R.declare(C.CDLL(S.PRODUCT_SO))
+    return open_library(R.declare)
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert {"svt_amd_source_ops_batch_launch", "svt_amd_source_ops_bytes"} <= exported
+    assert {"svt_amd_source_ops_batch_launch", "svt_amd_source_ops_bytes"} <= exported()
 
 
 def test_structure_layouts(tmp_path):
@@ -37,10 +33,7 @@ def test_structure_layouts(tmp_path):
               "offsetof(SvtAmdSboJob, cu8x8_mode) == 202", "offsetof(SvtAmdSboJob, want_qpm) == 203", "SVT_AMD_SBO_LCU == 0 && SVT_AMD_SBO_PICTURE == 1"]
     checks += ["offsetof(SvtAmdSboLcu, %s) == %d" % (f, lcu.fields[f][1]) for f in lcu.names]
     checks += ["offsetof(SvtAmdSboPic, %s) == %d" % (f, pic.fields[f][1]) for f in pic.names]
-    src = tmp_path / "t.c"
-    src.write_text('#include <stddef.h>\n#include "svt_hevc_amd.h"\n' + "".join('_Static_assert(%s, "%s");\n' % (c, c.replace('"', "")) for c in checks) +
-                   'int main(void) { return 0; }\n')
-    subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(S.ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    compiles(tmp_path, "c11", checks)
 
 
 def test_bad_headers_are_refused_without_a_device(lib):
@@ -51,6 +44,10 @@ def test_bad_headers_are_refused_without_a_device(lib):
         refused(lib, lib.svt_amd_source_ops_batch_launch(fake, jobs, n, 64, 64, 1, 1, C.byref(table)), R.ENTRY, n)
     refused(lib, lib.svt_amd_source_ops_batch_launch(fake, None, 1, 64, 64, 1, 1, C.byref(table)), R.ENTRY)
     refused(lib, lib.svt_amd_source_ops_batch_launch(fake, jobs, 1, 64, 64, 1, 1, None), R.ENTRY)
+    # ... nor for the picture's size: the bound of the kernels is tested before the context's own
+    refused_as(lib, lib.svt_amd_source_ops_batch_launch(fake, jobs, 1, 0, 64, 1, 1, C.byref(table)), R.ENTRY + ": job 0: a picture of 0x64 (at most 16384 LCUs)")
+    refused_as(lib, lib.svt_amd_source_ops_batch_launch(fake, jobs, 1, 16384, 16384, 1, 1, C.byref(table)),
+               R.ENTRY + ": job 0: a picture of 16384x16384 (at most 16384 LCUs)")
 
 
 @pytest.mark.parametrize("w,h", [(48, 40), (64, 64), (416, 240), (704, 640), (1920, 1080), (3840, 2160)])

@@ -7,20 +7,18 @@ import subprocess
 import pytest
 
 import sidelib as L
+from abi_util import exported, open_library
 from pa_batch_util import refused
 import svtlib as S
 
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return L.declare(C.CDLL(S.PRODUCT_SO))
+    return open_library(L.declare)
 
 
 def test_side_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert {"svt_amd_side_stats_batch_launch", "svt_amd_side_stats_bytes"} <= exported
+    assert {"svt_amd_side_stats_batch_launch", "svt_amd_side_stats_bytes"} <= exported()
 
 
 def test_structure_layouts(tmp_path):

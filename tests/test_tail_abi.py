@@ -2,14 +2,13 @@
 views (tests/taillib.py) agree on sizes and on every offset, svt_amd_picture_tail_bytes is the documented arithmetic and the checks that need no device answer
 without one."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
 
 import svtlib as S
 import tail_numpy as N
 import taillib as T
+from abi_util import compiles, exported, open_library
 from pa_batch_util import BAD_PARAM, refused
 
 VIEWS = (("SvtAmdTailJob", T.TailJob), ("SvtAmdTailCheck", T.TailCheck), ("SvtAmdDeblockParams", T.DeblockParams), ("SvtAmdCuMapEntry", T.CuMapEntry))
@@ -19,20 +18,11 @@ ENTRIES = {"svt_amd_picture_tail_bytes", "svt_amd_encdec_picture_tail_launch", "
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return T.declare(C.CDLL(S.PRODUCT_SO))
-
-
-def _compiles(tmp_path, std, checks):
-    src = tmp_path / "t.c"
-    src.write_text('#include <stddef.h>\n#include "svt_hevc_amd.h"\n' + "".join('_Static_assert(%s, "%s");\n' % (c, c) for c in checks) + 'int main(void) { return 0; }\n')
-    subprocess.check_call(["gcc", "-std=" + std, "-Wall", "-Werror", "-I", os.path.join(S.ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    return open_library(T.declare)
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert ENTRIES <= exported, ENTRIES - exported
+    assert ENTRIES <= exported(), ENTRIES - exported()
 
 
 def test_structure_sizes_and_offsets_in_c99(tmp_path):
@@ -44,7 +34,7 @@ def test_structure_sizes_and_offsets_in_c99(tmp_path):
                "SVT_AMD_TAIL_REFERENCE == %d" % N.REFERENCE, "SVT_AMD_TAIL_LCU_PARAMS == %d" % T.LCU_PARAMS, "SVT_AMD_TAIL_CHECK == %d" % T.CHECK,
                "offsetof(SvtAmdLcuWork, src_y) == %d" % T.LIST_BYTES, "offsetof(SvtAmdLcuWork16, src_y) == %d" % T.LIST_BYTES,
                "offsetof(SvtAmdLcuResult, coeff_y) == %d" % T.RESULT_CU_BYTES, "offsetof(SvtAmdLcuResult16, coeff_y) == %d" % T.RESULT_CU_BYTES]
-    _compiles(tmp_path, "c99", checks)
+    compiles(tmp_path, "c99", checks)
 
 
 @pytest.mark.parametrize("w,h", [(64, 64), (136, 72), (200, 136), (3840, 2160)])

@@ -2,14 +2,12 @@
 header, the ctypes views (tests/tmvplib.py) and the numpy layouts agree on sizes and on every offset, svt_amd_motion_field_bytes is the documented arithmetic
 and the checks that need no device answer without one."""
 import ctypes as C
-import os
-import subprocess
 
-import numpy as np
 import pytest
 
 import svtlib as S
 import tmvplib as T
+from abi_util import compiles, exported, open_library, view_matches_dtype
 from pa_batch_util import BAD_PARAM, refused
 
 VIEWS = (("SvtAmdMotionFieldJob", T.MotionFieldJob), ("SvtAmdRefStats", T.RefStats), ("SvtAmdTmvpLcu", T.TmvpLcu), ("SvtAmdLcuCu", T.LcuCu))
@@ -18,20 +16,11 @@ ENTRIES = {"svt_amd_motion_field_bytes", "svt_amd_motion_field_launch", "svt_amd
 
 @pytest.fixture(scope="module")
 def lib():
-    assert os.path.exists(S.PRODUCT_SO), "run `python __graft_entry__.py build` first"
-    return T.declare(C.CDLL(S.PRODUCT_SO))
-
-
-def _compiles(tmp_path, std, checks):
-    src = tmp_path / "t.c"
-    src.write_text('#include <stddef.h>\n#include "svt_hevc_amd.h"\n' + "".join('_Static_assert(%s, "%s");\n' % (c, c) for c in checks) + 'int main(void) { return 0; }\n')
-    subprocess.check_call(["gcc", "-std=" + std, "-Wall", "-Werror", "-I", os.path.join(S.ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+    return open_library(T.declare)
 
 
 def test_entries_are_exported():
-    out = subprocess.check_output(["nm", "-D", "--defined-only", S.PRODUCT_SO], text=True)
-    exported = set(line.split()[-1] for line in out.splitlines() if " T " in line)
-    assert ENTRIES <= exported, ENTRIES - exported
+    assert ENTRIES <= exported(), ENTRIES - exported()
 
 
 def test_structure_sizes_in_c99(tmp_path):
@@ -41,7 +30,7 @@ def test_structure_sizes_in_c99(tmp_path):
     checks = ["sizeof(%s) == %d" % (name, C.sizeof(view)) for name, view in VIEWS]
     checks += ["SVT_AMD_MOTION_FIELD == %d" % T.FIELD, "SVT_AMD_MOTION_FIELD_STATS == %d" % T.STATS, "SVT_AMD_MDCTL_MAX_LCUS == %d" % T.MAX_LCUS,
                "sizeof(SvtAmdLcuWork) == %d" % T.WORK_BYTES, "sizeof(SvtAmdLcuWork16) == %d" % T.WORK16_BYTES]
-    _compiles(tmp_path, "c99", checks)
+    compiles(tmp_path, "c99", checks)
 
 
 def test_header_offsets_field_by_field(tmp_path):
@@ -50,21 +39,12 @@ def test_header_offsets_field_by_field(tmp_path):
     for rec in ("SvtAmdLcuWork", "SvtAmdLcuWork16"):
         checks += ["offsetof(%s, %s) == %d" % (rec, f, getattr(T.LcuWorkHead, f).offset) for f, _ in T.LcuWorkHead._fields_]
         checks += ["offsetof(%s, src_y) == %d" % (rec, T.LIST_BYTES), "offsetof(%s, cu) == %d" % (rec, T.HEAD_BYTES)]
-    _compiles(tmp_path, "c11", checks)
+    compiles(tmp_path, "c11", checks)
 
 
 @pytest.mark.parametrize("view,dtype", [(T.RefStats, T.REF_STATS_DTYPE), (T.TmvpLcu, T.TMVP_LCU_DTYPE), (T.LcuCu, S.LCU_CU_DTYPE), (T.LcuWorkHead, T.WORK_HEAD_DTYPE)])
 def test_ctypes_views_have_the_dtypes_offsets(view, dtype):
-    assert C.sizeof(view) == dtype.itemsize
-    assert [f for f, _ in view._fields_] == list(dtype.names)
-    for f, t in view._fields_:
-        sub, offset = dtype.fields[f][:2]
-        assert getattr(view, f).offset == offset and C.sizeof(t) == sub.itemsize, f
-        scalar = t
-        while hasattr(scalar, "_length_"):
-            scalar = scalar._type_
-        if not issubclass(scalar, C.Structure):
-            assert np.dtype(scalar) == sub.base.newbyteorder("="), f
+    view_matches_dtype(view, dtype)
 
 
 def test_the_work_head_is_the_head_of_both_work_dtypes():
