@@ -2416,6 +2416,69 @@ SVT_AMD_API int svt_amd_md_lcus_supported(const SvtAmdMdPicture *P, const SvtAmd
  * of that path reads host records. */
 SVT_AMD_API int svt_amd_md_picture_set_controls(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLcu *d_lcus);
 
+/* The same picture call as a STREAM-ORDERED LAUNCH on DEVICE inputs: mode decision and encode pass of one picture queued on ctx's stream, then the call returns.
+ * It synchronises nothing, copies nothing from or to host memory and waits for no event; it allocates only at the first call on the picture object (and, for the
+ * check record, on the context).  The decisions, work records and results stay in HBM, where svt_amd_encdec_picture_tail_launch (NULL records) and
+ * svt_amd_encdec_picture_motion_field read them in place - queued behind this call on the same context, stream order suffices - and
+ * svt_amd_encdec_picture_md_records hands them out.  The blocking entries above are unchanged; both kinds may alternate on one object.
+ *   P, X, cost   HOST records, read before the call returns (they travel in a kernel-argument block, so a second launch on the same object queued before the first
+ *                has run cannot disturb the first).  X == NULL: an I picture.  cost == NULL keeps the rate tables svt_amd_encdec_picture_set_inter put on the
+ *                object; required when the object has none.
+ *   d_lcus       DEVICE SvtAmdMdLcu[LCUs] (svt_amd_md_controls_batch_launch's output, or any array of that layout), required.
+ *   d_src        DEVICE source planes of the object's sample width (8-bit samples, or 10-bit samples in 16-bit words), sample (0,0); pitches in samples.
+ *                Pointers and row starts 4-byte aligned: pitch >= plane width, pitch * bytes per sample a multiple of 4.  The planes are COPIED into the object's
+ *                own (for 16-bit samples the 8-MSB view is made in the same pass): the caller may reuse them once the launch has run.
+ *   d_ois, d_me  DEVICE arrays of one record per LCU read in place, or NULL: the records resident in picture slot ois_slot / me_slot - the stream orders itself
+ *                behind the launch that wrote them and leaves a read mark, exactly as the blocking call does.  d_me and me_slot are ignored for an I picture.
+ *   d_tmvp       DEVICE SvtAmdTmvpLcu[LCUs + 1] (svt_amd_encdec_picture_motion_field's output), 8-byte aligned: required when X->tmvp_enable, ignored otherwise.
+ *   tiles        the picture's tile count (LCUs with tile_left && tile_top), 1 .. LCUs: it sizes the grids only - a wrong count costs time, never correctness.
+ *   flags        SVT_AMD_MD_LAUNCH_DECIDE_ONLY: a P / B picture's decisions alone - no work records, no encode pass (the blocking call with works == results == NULL).
+ * Every raw device pointer is the caller's to order: written on this context, stream order suffices; written on another lane, svt_amd_lane_event_record / _wait.
+ * Everything the host can judge is checked before anything is queued - svt_amd_md_picture_supported[_inter], the picture object's size and sample width,
+ * reference pictures and rate tables, complete slot records, pitches and alignment, pads and flags; an object with a rank rectangle
+ * (svt_amd_encdec_picture_set_rect) is refused, and so is a call that finds a binding of svt_amd_md_picture_set_controls / _set_motion_field pending on the object,
+ * which it drops: the job carries the arrays.  A refusal names this entry and queues nothing.
+ * What the blocking call's host loop refuses in the CONTROLS (SvtAmdMdCtlCheck: leaf_count, leaf list, an LCU not decided by ModeDecisionLcu in a P / B picture) is
+ * judged on the device: the check kernel runs over d_lcus, and for an array it refuses nothing of the picture is decided or encoded - no LCU of a malformed leaf
+ * list is read, d_out keeps what it held, work and result records are zero (the tail counts every such LCU but the first - a zero record is an empty LCU at (0, 0) - in
+ * SvtAmdTailCheck.bad_lcus, the motion field reads them as empty).  d_status (DEVICE, 4-byte aligned, or NULL) receives that check record and `refused` once per launch.
+ * Launch width: the blocking call's formulas; a launch cannot wait for the workgroup budget of the blocking calls and holds none of it - it takes the lone
+ * picture's width when no blocking call is in flight as it is queued and the narrow one otherwise.  Tickets make any width correct.
+ * The object's debug profile / trace switches apply as in the blocking call; SVT_AMD_MD_TIMING does not. */
+#define SVT_AMD_MD_LAUNCH_DECIDE_ONLY 1u
+typedef struct SvtAmdMdLaunchJob {
+    const SvtAmdMdPicture *P;              /* HOST                                                                               */
+    const SvtAmdMdInter *X;                /* HOST, or NULL: an I picture                                                        */
+    const SvtAmdCabacCost *cost;           /* HOST, or NULL: the object's rate tables                                            */
+    const SvtAmdMdLcu *d_lcus;             /* DEVICE                                                                             */
+    const void *d_src[3];                  /* DEVICE: luma, cb, cr                                                               */
+    const SvtAmdOisLcuResult *d_ois;       /* DEVICE, or NULL: slot ois_slot                                                     */
+    const SvtAmdMeLcuResult *d_me;         /* DEVICE, or NULL: slot me_slot (P / B)                                              */
+    const SvtAmdTmvpLcu *d_tmvp;           /* DEVICE, LCUs + 1 records (tmvp_enable)                                             */
+    uint32_t src_pitch_y, src_pitch_c;     /* samples                                                                            */
+    int32_t ois_slot, me_slot;
+    uint32_t tiles;
+    uint32_t flags;                        /* SVT_AMD_MD_LAUNCH_*                                                                */
+    uint32_t pad[2];                       /* 0                                                                                  */
+} SvtAmdMdLaunchJob;                       /* 112 bytes */
+typedef struct SvtAmdMdLaunchStatus {
+    SvtAmdMdCtlCheck check;                /* of d_lcus                                                                          */
+    uint32_t refused;                      /* 1: check.first_bad names an LCU - nothing of the picture was decided or encoded; 0 otherwise */
+    uint32_t pad;                          /* written as 0                                                                       */
+} SvtAmdMdLaunchStatus;                    /* 96 bytes */
+#ifdef __cplusplus
+static_assert(sizeof(SvtAmdMdLaunchJob) == 112 && sizeof(SvtAmdMdLaunchStatus) == 96, "launch records");
+#else
+_Static_assert(sizeof(SvtAmdMdLaunchJob) == 112 && sizeof(SvtAmdMdLaunchStatus) == 96, "launch records");
+#endif
+SVT_AMD_API int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLaunchJob *job, SvtAmdMdLaunchStatus *d_status);
+/* The DEVICE arrays the last mode-decision call on `pic` - blocking or launched - wrote or is writing, one record per LCU in raster order: d_out SvtAmdMdLcuOut,
+ * d_works SvtAmdLcuWork[16] at *work_stride bytes, d_results SvtAmdLcuResult[16] at *result_stride bytes; any of the five may be NULL.  They belong to the object
+ * and live as long as it does; fetch what is wanted with svt_amd_device_download_async on the context the call ran on.  Refused on an object no mode-decision call
+ * has touched. */
+SVT_AMD_API int svt_amd_encdec_picture_md_records(SvtAmdEncDecPicture *pic, const SvtAmdMdLcuOut **d_out, const void **d_works, size_t *work_stride,
+                                                  const void **d_results, size_t *result_stride);
+
 /* ------------------------------------------------------------------------- */
 /* Temporal motion field on the device: the co-located picture's field and intra-coded area from its work records */
 /* ------------------------------------------------------------------------- */

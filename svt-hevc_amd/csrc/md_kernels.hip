@@ -61,6 +61,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include "md_logic.h"
+#include "mdlaunch.h"
 
 struct MdPictureDev {
     uint8_t *md_rec;              /* the mode decision's luma reconstruction, sample (0,0) */
@@ -3153,6 +3154,8 @@ extern "C" int svt_amd_md_picture_warmup(SvtAmdContext *ctx, SvtAmdEncDecPicture
     return rc;
 }
 
+/* (svt_amd_md_encode_picture_launch below queues the same picture without a wait: md_launch_widths and md_launch_kernel restate this function's launch widths and its
+ * choice of the k_md_picture instance - whoever retunes either here changes them there) */
 /* bps: bytes per sample of the source planes, the work / result records and the picture object (1, or 2 = a 10-bit picture: the mode decision on the 8 MSBs of source
  * and reference pictures, the encode pass on the 10-bit samples) */
 static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdInter *X, const SvtAmdMdLcu *lcus,
@@ -3544,6 +3547,247 @@ extern "C" int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncDe
         return SVT_AMD_ERR_BAD_PARAM;
     }
     return md_encode_picture(ctx, pic, P, X, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, me, me_slot, tmvp, nullptr, md_out, works, results, 2);
+}
+
+/* ---- the stream-ordered launch on device inputs (include/svt_hevc_amd.h: svt_amd_md_encode_picture_launch) ---- */
+#define MDL_ENTRY "svt_amd_md_encode_picture_launch"
+#define MDL_BAD(...) do { svt_amd_set_error(MDL_ENTRY ": " __VA_ARGS__); return SVT_AMD_ERR_BAD_PARAM; } while (0)
+
+/* the blocking call's launch widths (md_encode_picture, above: the formulas, their measurements and the measurement overrides SVT_AMD_MD_GRID / _NARROW / _WIDE), kept
+ * in step with it by hand: a launch takes `lone` or `narrow` */
+static void md_launch_widths(int wl, int hl, int tiles, int n_active, int *lone_out, int *narrow_out)
+{
+    const int front = ((wl + 1) / 2 < hl ? (wl + 1) / 2 : hl) * (tiles > 0 ? tiles : 1);
+    int lone = 2 * front + 2;
+    int grid = front + 2 + (wl + 7) / 8;
+    int narrow = (grid + 1) / 2 < 8 ? 8 : (grid + 1) / 2;
+    const char *fg = getenv("SVT_AMD_MD_GRID"); /* measurement: a fixed launch width */
+    const int forced = fg ? atoi(fg) : 0;
+    if (forced > 0)
+        lone = grid = narrow = forced;
+    static const int fnarrow = getenv("SVT_AMD_MD_NARROW") ? atoi(getenv("SVT_AMD_MD_NARROW")) : 0;
+    if (fnarrow > 0)
+        narrow = fnarrow;
+    static const int fwide = getenv("SVT_AMD_MD_WIDE") ? atoi(getenv("SVT_AMD_MD_WIDE")) : 0;
+    if (fwide > 0)
+        lone = grid = fwide;
+    grid = grid > n_active ? n_active : grid > 224 ? 224 : grid;
+    lone = lone > n_active ? n_active : lone > 224 ? 224 : lone;
+    lone = lone < grid ? grid : lone;
+    narrow = narrow > grid ? grid : narrow;
+    *lone_out = lone, *narrow_out = narrow;
+}
+
+/* the instance of k_md_picture the blocking call launches for the same picture */
+static int md_launch_kernel(hipStream_t st, SvtAmdEncDecPicture *pic, SvtAmdMdState *m, bool inter, uint32_t bps, int grid, int n_active, int wl, const unsigned *d_order)
+{
+    const bool profiled = m->d.prof != nullptr;
+    if (inter && bps == 1 && !profiled)
+        hipLaunchKernelGGL((k_md_picture<true, uint8_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter && bps == 1)
+        hipLaunchKernelGGL((k_md_picture<true, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+#ifdef MD_INTER8_ONLY
+    else
+        return SVT_AMD_ERR_BAD_PARAM;
+#else
+    else if (bps == 1)
+        hipLaunchKernelGGL((k_md_picture<false, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter && !profiled)
+        hipLaunchKernelGGL((k_md_picture<true, uint16_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter)
+        hipLaunchKernelGGL((k_md_picture<true, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else
+        hipLaunchKernelGGL((k_md_picture<false, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+#endif
+    HIP_TRY(hipGetLastError());
+    return SVT_AMD_OK;
+}
+
+extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLaunchJob *job, SvtAmdMdLaunchStatus *d_status)
+{
+    /* a binding of svt_amd_md_picture_set_controls / _set_motion_field waits for a blocking call: this one consumes it, as every call on the object does, and refuses */
+    const bool pending = pic && (pic->md_bound_lcus || pic->md_bound_tmvp);
+    if (pic)
+        pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
+    if (!ctx || !pic || !job)
+        MDL_BAD("a context, a picture object and a job");
+    if (pending)
+        MDL_BAD("a device array is bound to the picture object (svt_amd_md_picture_set_controls / _set_motion_field): the job carries the arrays; the binding is dropped");
+    const SvtAmdMdPicture *P = job->P;
+    const SvtAmdMdInter *X = job->X;
+    if (job->pad[0] || job->pad[1] || (job->flags & ~SVT_AMD_MD_LAUNCH_DECIDE_ONLY))
+        MDL_BAD("a pad word is not 0, or unknown flags 0x%x", job->flags);
+    if (!P || !job->d_lcus || !job->d_src[0] || !job->d_src[1] || !job->d_src[2])
+        MDL_BAD("the job has no %s", !P ? "picture controls" : !job->d_lcus ? "device array of LCU controls" : "source planes");
+    if ((job->flags & SVT_AMD_MD_LAUNCH_DECIDE_ONLY) && !X)
+        MDL_BAD("SVT_AMD_MD_LAUNCH_DECIDE_ONLY is the P / B call without work records: an I picture has no such form");
+    if (((uintptr_t)job->d_src[0] | (uintptr_t)job->d_src[1] | (uintptr_t)job->d_src[2] | (uintptr_t)d_status) & 3)
+        MDL_BAD("source planes at %p, %p, %p and the status record at %p have to be 4-byte aligned", job->d_src[0], job->d_src[1], job->d_src[2], (void *)d_status);
+    if (job->src_pitch_y < P->width || job->src_pitch_c < P->width / 2u)
+        MDL_BAD("source pitches %u / %u below the plane widths of a %u samples wide picture", job->src_pitch_y, job->src_pitch_c, P->width);
+    if ((X ? !md_picture_supported_inter(P, X) : !md_picture_supported(P)) || P->width != pic->d.width || P->height != pic->d.height)
+        MDL_BAD("picture outside what this revision covers (svt_amd_md_picture_supported[_inter]), or not the picture object's size");
+    const uint32_t bps = pic->d.bps;
+    if ((job->src_pitch_y * bps) % 4 || (job->src_pitch_c * bps) % 4)
+        MDL_BAD("source pitches of %u / %u samples of %u bytes: rows have to start 4-byte aligned", job->src_pitch_y, job->src_pitch_c, bps);
+    const int n = pic->nlcu, wl = (pic->d.width + 63) / 64, hl = (pic->d.height + 63) / 64;
+    if (job->tiles < 1 || job->tiles > (uint32_t)n)
+        MDL_BAD("%u tiles in a picture of %d LCUs", job->tiles, n);
+    if (!X && !job->cost && !pic->has_cost)
+        MDL_BAD("no rate tables: the job has none and the picture object holds none (svt_amd_encdec_picture_set_inter)");
+    if (X && ((!job->cost && !pic->has_cost) || !pic->has_ref[0] || (P->slice_type == 0 && !pic->has_ref[1]) || (X->tmvp_enable && !job->d_tmvp)))
+        MDL_BAD("reference pictures / rate tables not set (svt_amd_encdec_picture_set_inter), or no co-located motion field");
+    if (X && X->tmvp_enable && (uintptr_t)job->d_tmvp % 8)
+        MDL_BAD("the motion field at %p is not 8-byte aligned", (const void *)job->d_tmvp);
+    if (pic->md_rect_n)
+        MDL_BAD("the picture object has a rank rectangle (svt_amd_encdec_picture_set_rect): the rectangle's tile-border check reads host records");
+    DevPicture *rec_slot[2] = {nullptr, nullptr};
+    SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
+    const SvtAmdMeLcuResult *d_me = X ? job->d_me : nullptr;
+    if (X && !d_me) {
+        if (!(d_me = (const SvtAmdMeLcuResult *)svt_amd_slot_records(root, job->me_slot, 0, pic->d.width, pic->d.height)))
+            MDL_BAD("slot %d does not hold the motion-estimation records of a %u x %u picture (none launched for the slot's current picture, or only a part of it)",
+                    job->me_slot, pic->d.width, pic->d.height);
+        rec_slot[0] = &root->slots[job->me_slot];
+    }
+    const SvtAmdOisLcuResult *d_ois = job->d_ois;
+    if (!d_ois) {
+        if (!(d_ois = (const SvtAmdOisLcuResult *)svt_amd_slot_records(root, job->ois_slot, 1, pic->d.width, pic->d.height)))
+            MDL_BAD("slot %d does not hold the open-loop intra search records of a %u x %u picture", job->ois_slot, pic->d.width, pic->d.height);
+        rec_slot[1] = &root->slots[job->ois_slot];
+    }
+
+    /* ---- nothing below reads host memory after the call has returned, copies or waits ---- */
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = rate_tables_once(ctx->device);
+    if (rc)
+        return rc;
+    SvtAmdMdState *m = nullptr;
+    if ((rc = md_state(pic, &m)) != 0) /* allocates at the first call on the object */
+        return rc;
+    hipStream_t st = svt_amd_ctx_stream(ctx);
+    for (int k = 0; k < 2; k++)
+        if (rec_slot[k] && (rc = svt_amd_records_wait(ctx, rec_slot[k], k, nullptr, nullptr, 0)) != 0)
+            return rc;
+    /* the source: the caller's planes into the object's own, at the object's pitch (the blocking call's strided form) */
+    MdSourcePlanes S;
+    memset(&S, 0, sizeof(S));
+    for (int k = 0; k < 3; k++) {
+        S.src[k] = job->d_src[k];
+        S.dst[k] = bps == 2 ? (void *)m->d_src16[k] : (void *)m->d_src[k], S.view[k] = bps == 2 ? m->d_src[k] : nullptr;
+        m->d.src[k] = m->d_src[k], m->d.src16[k] = bps == 2 ? m->d_src16[k] : nullptr;
+    }
+    S.src_pitch[0] = job->src_pitch_y, S.src_pitch[1] = job->src_pitch_c, S.dst_pitch[0] = pic->d.pitch[0], S.dst_pitch[1] = pic->d.pitch[1];
+    S.width = pic->d.width, S.height = pic->d.height;
+    m->d.src_pitch[0] = pic->d.pitch[0], m->d.src_pitch[1] = pic->d.pitch[1];
+    if ((rc = svt_amd_mdlaunch_source(ctx, &S, (int)bps)) != 0)
+        return rc;
+    for (int l = 0; l < 2; l++) { /* the reference pictures as the mode decision reads them (md_encode_picture) */
+        m->d.mref[l] = pic->d.ref[l];
+        if (bps == 2 && X && pic->has_ref[l])
+            for (int p = 0; p < 3; p++) {
+                const size_t need = (size_t)pic->d.ref[l].size[p ? 1 : 0];
+                if (m->ref8_bytes[l][p] < need) { /* the first P / B launch of a 10-bit object, or reference pictures with more padding than any before */
+                    if (m->d_ref8[l][p])
+                        (void)hipFree(m->d_ref8[l][p]);
+                    m->d_ref8[l][p] = nullptr, m->ref8_bytes[l][p] = 0;
+                    HIP_TRY(hipMalloc((void **)&m->d_ref8[l][p], need + 16));
+                    m->ref8_bytes[l][p] = need;
+                }
+                if ((rc = msb_view(st, pic->d.ref[l].plane[p], m->d_ref8[l][p], need)) != 0)
+                    return rc;
+                m->d.mref[l].plane[p] = m->d_ref8[l][p];
+            }
+    }
+    /* the small inputs and the descriptor: by value, in k_md_stage's argument block */
+    if (job->cost)
+        pic->has_cost = true;
+    m->d.X = X ? m->d_X : nullptr, m->d.me = d_me, m->d.tmvp = X ? (X->tmvp_enable ? job->d_tmvp : m->d_tmvp) : nullptr;
+    m->d.prof = m->d_prof, m->d.prof_lcus = n;
+    m->d.trace = m->d_trace, m->d.trace_lcu = m->trace_lcu, m->d.trace_unit = m->trace_unit;
+    m->d.force_butterflies = m->force_butterflies;
+    m->d.encode = !X || !(job->flags & SVT_AMD_MD_LAUNCH_DECIDE_ONLY);
+    m->d.ois = d_ois, m->d.lcus = job->d_lcus, m->d.P = m->d_P, m->d.out = m->d_out;
+    m->d.cost = pic->d_cost;
+    MdStagePart parts[4];
+    int nparts = 0;
+    parts[nparts++] = MdStagePart{m->d_P, P, sizeof(*P)};
+    if (X)
+        parts[nparts++] = MdStagePart{m->d_X, X, sizeof(*X)};
+    if (job->cost)
+        parts[nparts++] = MdStagePart{pic->d_cost, job->cost, sizeof(*job->cost)};
+    parts[nparts++] = MdStagePart{m->d_D, &m->d, sizeof(m->d)};
+    if ((rc = svt_amd_mdlaunch_stage(ctx, parts, nparts)) != 0)
+        return rc;
+    /* the controls: judged where they lie; the gate opens or closes both kernels' ticket counters */
+    pic->epoch++;
+    pic->deblocked = pic->sao_done = false;
+    pic->md_works_whole = false; /* until everything is queued: a launch that fails half-way leaves arrays no consumer may take */
+    const SvtAmdMdCtlCheck *d_check = nullptr;
+    if ((rc = svt_amd_mdctl_check_device(ctx, job->d_lcus, n, P->depth_mode, X != nullptr, &d_check)) != 0)
+        return rc;
+    if ((rc = svt_amd_mdlaunch_gate(ctx, d_check, m->d_md_ticket, pic->d_sync, (unsigned)n, d_status)) != 0)
+        return rc;
+    if (X)
+        HIP_TRY(hipMemsetAsync(m->d.md_mv, 0, m->mv_bytes, st));
+    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, st));
+    HIP_TRY(hipMemsetAsync(m->d.md_info, 0xFF, m->info_bytes, st));
+    HIP_TRY(hipMemsetAsync(m->d_results, 0, m->result_bytes * (size_t)n, st));
+    HIP_TRY(hipMemsetAsync(m->d_works, 0, m->work_bytes * (size_t)n, st));
+    if ((rc = md_kernel_attributes(ctx->device)) != 0)
+        return rc;
+    /* a launch cannot wait for the blocking calls' workgroup budget (MdFlight) and holds none of it: the lone picture's width when the budget shows no flight now */
+    int lone, narrow, flights;
+    md_launch_widths(wl, hl, (int)job->tiles, n, &lone, &narrow);
+    {
+        std::lock_guard<std::mutex> l(g_flight_mu);
+        flights = g_flight_dev[ctx->device & 63].flights;
+    }
+    const int grid = flights == 0 ? lone : narrow;
+    m->grid = grid;
+    const unsigned *d_order = pic->d_sync + 1 + n;
+    HIP_TRY(hipEventRecord(m->ev_k0, st));
+    if ((rc = md_launch_kernel(st, pic, m, X != nullptr, bps, grid, n, wl, d_order)) != 0)
+        return rc;
+    HIP_TRY(hipEventRecord(m->ev_k1, st));
+    if (m->d.encode && (rc = svt_amd_ep_launch_behind_md(ctx, pic, m->d_works, m->d_results, n, d_order, X != nullptr, (int)job->tiles)) != 0)
+        return rc;
+    HIP_TRY(hipEventRecord(m->ev_k2, st));
+    if ((rc = ep_picture_written(ctx, pic)) != 0)
+        return rc;
+    if (rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, job->me_slot)) != 0)
+        return rc;
+    if (rec_slot[1] && rec_slot[1] != rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, job->ois_slot)) != 0)
+        return rc;
+    pic->md_works_whole = m->d.encode != 0; /* at queue time: the tail and the motion field queue behind this launch in stream order */
+    return SVT_AMD_OK;
+}
+
+extern "C" int svt_amd_encdec_picture_md_records(SvtAmdEncDecPicture *pic, const SvtAmdMdLcuOut **d_out, const void **d_works, size_t *work_stride, const void **d_results,
+                                                 size_t *result_stride)
+{
+    if (!pic || !pic->md) {
+        svt_amd_set_error("svt_amd_encdec_picture_md_records: %s", pic ? "no mode-decision call has run on the picture object" : "a picture object");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    const SvtAmdMdState *m = pic->md;
+    if (d_out)
+        *d_out = m->d_out;
+    if (d_works)
+        *d_works = m->d_works;
+    if (work_stride)
+        *work_stride = m->work_bytes;
+    if (d_results)
+        *d_results = m->d_results;
+    if (result_stride)
+        *result_stride = m->result_bytes;
+    return SVT_AMD_OK;
 }
 
 /* debug: stage clocks of the mode-decision kernel.  First call (out == NULL or not): switches the collection on for the picture object's later

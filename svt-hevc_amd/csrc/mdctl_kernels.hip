@@ -18,6 +18,7 @@
  */
 #include "pa_batch.h"
 #include "mdc_units.h"
+#include "mdlaunch.h"
 #include <string.h>
 #define MD_FN __host__ __device__ __forceinline__
 #include "md_logic.h"
@@ -286,6 +287,18 @@ int svt_amd_mdctl_check_async(SvtAmdContext *ctx, const SvtAmdMdLcu *d_lcus, int
     hipLaunchKernelGGL(k_mdctl_check, dim3(1), dim3(MDCTL_CHECK_THREADS), 0, st, d_lcus, n, depth_mode, inter, d_check);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h_out, d_check, sizeof(*h_out), hipMemcpyDeviceToHost, st));
+    return SVT_AMD_OK;
+}
+
+/* mdlaunch.h */
+int svt_amd_mdctl_check_device(SvtAmdContext *ctx, const SvtAmdMdLcu *d_lcus, int n, int depth_mode, int inter, const SvtAmdMdCtlCheck **d_out)
+{
+    MdCtlJobDev *d_tab;
+    SvtAmdMdCtlCheck *d_check;
+    SVT_AMD_TRY(mdctl_begin(ctx, &d_tab, &d_check));
+    hipLaunchKernelGGL(k_mdctl_check, dim3(1), dim3(MDCTL_CHECK_THREADS), 0, svt_amd_ctx_stream(ctx), d_lcus, n, depth_mode, inter, d_check);
+    HIP_TRY(hipGetLastError());
+    *d_out = d_check;
     return SVT_AMD_OK;
 }
 
