@@ -62,6 +62,7 @@
 #include <cstdlib>
 #include "md_logic.h"
 #include "mdlaunch.h"
+#include "md_widths.h"
 
 struct MdPictureDev {
     uint8_t *md_rec;              /* the mode decision's luma reconstruction, sample (0,0) */
@@ -3126,18 +3127,6 @@ struct MdFlight {
 };
 }
 
-/* the kernel's dynamic LDS size, once per device */
-static int md_kernel_attributes(int device)
-{
-    static std::mutex mu;
-    static bool attr[64];
-    std::lock_guard<std::mutex> g(mu);
-    if (!attr[device & 63]) {
-        /* (the kernels' LCU state is static shared memory: nothing to raise) */
-        attr[device & 63] = true;
-    }
-    return SVT_AMD_OK;
-}
 /* everything the first svt_amd_md_encode_picture[_inter] call on this picture object would allocate (device state, page-locked staging, events), made now - by a host that
  * builds its picture objects before the clock starts (the encoder binding: EbInitEncoder) */
 extern "C" int svt_amd_md_picture_warmup(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic)
@@ -3149,13 +3138,159 @@ extern "C" int svt_amd_md_picture_warmup(SvtAmdContext *ctx, SvtAmdEncDecPicture
     SvtAmdMdState *m = nullptr;
     if (!rc)
         rc = md_state(pic, &m);
-    if (!rc)
-        rc = md_kernel_attributes(ctx->device);
     return rc;
 }
 
-/* (svt_amd_md_encode_picture_launch below queues the same picture without a wait: md_launch_widths and md_launch_kernel restate this function's launch widths and its
- * choice of the k_md_picture instance - whoever retunes either here changes them there) */
+/* ---- what the blocking entries (md_encode_picture) and svt_amd_md_encode_picture_launch share: each of the following exists once, and both call it ---- */
+
+/* the launch widths (md_widths.h: the formulas and their measurements) under the measurement overrides: SVT_AMD_MD_GRID, a fixed launch width, is read at every call,
+ * SVT_AMD_MD_NARROW / _WIDE once per process.  The blocking call hands all three to MdFlight::acquire; a launch takes `lone` or `narrow` */
+static MdWidths md_launch_widths(int wl, int hl, int tiles, int n_active)
+{
+    const char *fg = getenv("SVT_AMD_MD_GRID");
+    static const int fnarrow = getenv("SVT_AMD_MD_NARROW") ? atoi(getenv("SVT_AMD_MD_NARROW")) : 0;
+    static const int fwide = getenv("SVT_AMD_MD_WIDE") ? atoi(getenv("SVT_AMD_MD_WIDE")) : 0;
+    return md_widths(wl, hl, tiles, n_active, fg ? atoi(fg) : 0, fnarrow, fwide);
+}
+
+/* the instance of k_md_picture for the picture: I or P / B, 8 or 16 bits a sample; the P / B kernels exist with and without the stage marks */
+static int md_launch_kernel(hipStream_t st, SvtAmdEncDecPicture *pic, SvtAmdMdState *m, bool inter, uint32_t bps, int grid, int n_active, int wl, const unsigned *d_order)
+{
+    const bool profiled = m->d.prof != nullptr;
+    if (inter && bps == 1 && !profiled)
+        hipLaunchKernelGGL((k_md_picture<true, uint8_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter && bps == 1)
+        hipLaunchKernelGGL((k_md_picture<true, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+#ifdef MD_INTER8_ONLY
+    else
+        return SVT_AMD_ERR_BAD_PARAM;
+#else
+    else if (bps == 1)
+        hipLaunchKernelGGL((k_md_picture<false, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter && !profiled)
+        hipLaunchKernelGGL((k_md_picture<true, uint16_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter)
+        hipLaunchKernelGGL((k_md_picture<true, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else
+        hipLaunchKernelGGL((k_md_picture<false, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+#endif
+    HIP_TRY(hipGetLastError());
+    return SVT_AMD_OK;
+}
+
+/* ME ([0]) and OIS ([1]) records read where another lane's kernels leave them, in a slot of the root context: this lane's stream orders itself behind those kernels
+ * (md_records_wait), and the next launch INTO those slots behind this picture's kernel (md_records_read_mark) */
+struct MdSlotRecords {
+    SvtAmdContext *root;
+    DevPicture *slot[2];
+    int index[2];
+};
+
+/* the records of kind `which` in slot `slot`, or NULL after the refusal under the entry's name */
+static const void *md_slot_records(MdSlotRecords *r, const SvtAmdEncDecPicture *pic, int which, int slot, const char *entry)
+{
+    const void *d = svt_amd_slot_records(r->root, slot, which, pic->d.width, pic->d.height);
+    if (!d && which == 0)
+        svt_amd_set_error("%s: slot %d does not hold the motion-estimation records of a %u x %u picture (none launched for the slot's current picture, or only a part of it)", entry,
+                          slot, pic->d.width, pic->d.height);
+    else if (!d)
+        svt_amd_set_error("%s: slot %d does not hold the open-loop intra search records of a %u x %u picture", entry, slot, pic->d.width, pic->d.height);
+    else
+        r->slot[which] = &r->root->slots[slot], r->index[which] = slot;
+    return d;
+}
+
+static int md_records_wait(SvtAmdContext *ctx, const MdSlotRecords &r)
+{
+    int rc = 0;
+    for (int k = 0; k < 2 && !rc; k++)
+        if (r.slot[k])
+            rc = svt_amd_records_wait(ctx, r.slot[k], k, nullptr, nullptr, 0);
+    return rc;
+}
+
+static int md_records_read_mark(SvtAmdContext *ctx, const MdSlotRecords &r)
+{
+    int rc = r.slot[0] ? svt_amd_records_read_mark(ctx, r.root, r.index[0]) : 0;
+    if (!rc && r.slot[1] && r.slot[1] != r.slot[0])
+        rc = svt_amd_records_read_mark(ctx, r.root, r.index[1]);
+    return rc;
+}
+
+/* the reference pictures as the mode decision reads them: a 10-bit P / B picture decides on their 8 MSBs (the views grow at the first such call on the object, or with
+ * reference pictures of more padding than any before) */
+static int md_reference_views(hipStream_t st, SvtAmdEncDecPicture *pic, SvtAmdMdState *m, bool inter)
+{
+    for (int l = 0; l < 2; l++) {
+        m->d.mref[l] = pic->d.ref[l];
+        if (pic->d.bps == 2 && inter && pic->has_ref[l])
+            for (int p = 0; p < 3; p++) {
+                const size_t need = (size_t)pic->d.ref[l].size[p ? 1 : 0];
+                if (m->ref8_bytes[l][p] < need) {
+                    if (m->d_ref8[l][p])
+                        (void)hipFree(m->d_ref8[l][p]);
+                    m->d_ref8[l][p] = nullptr, m->ref8_bytes[l][p] = 0;
+                    HIP_TRY(hipMalloc((void **)&m->d_ref8[l][p], need + 16));
+                    m->ref8_bytes[l][p] = need;
+                }
+                const int rc = msb_view(st, pic->d.ref[l].plane[p], m->d_ref8[l][p], need);
+                if (rc)
+                    return rc;
+                m->d.mref[l].plane[p] = m->d_ref8[l][p];
+            }
+    }
+    return SVT_AMD_OK;
+}
+
+/* the descriptor's fields that do not depend on where the inputs come from (after the entry has taken the call's rate tables) */
+static void md_descriptor_common(const SvtAmdEncDecPicture *pic, SvtAmdMdState *m)
+{
+    m->d.prof = m->d_prof, m->d.prof_lcus = pic->nlcu;
+    m->d.trace = m->d_trace, m->d.trace_lcu = m->trace_lcu, m->d.trace_unit = m->trace_unit;
+    m->d.force_butterflies = m->force_butterflies;
+    m->d.P = m->d_P, m->d.out = m->d_out;
+    m->d.cost = pic->has_cost ? pic->d_cost : nullptr;
+}
+
+/* the picture's arrays as the kernels expect to find them, on the context's stream in front of the kernel */
+static int md_reset_arrays(hipStream_t st, SvtAmdEncDecPicture *pic, SvtAmdMdState *m, bool inter)
+{
+    if (inter)
+        HIP_TRY(hipMemsetAsync(m->d.md_mv, 0, m->mv_bytes, st));
+    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, st));
+    HIP_TRY(hipMemsetAsync(m->d.md_info, 0xFF, m->info_bytes, st));
+    HIP_TRY(hipMemsetAsync(m->d_results, 0, m->result_bytes * (size_t)pic->nlcu, st));
+    HIP_TRY(hipMemsetAsync(m->d_works, 0, m->work_bytes * (size_t)pic->nlcu, st));
+    return SVT_AMD_OK;
+}
+
+/* the queue step: `grid` workgroups of the mode decision over the n_active LCUs of d_order, the encode pass behind it, the events the measurements read, the marks */
+static int md_queue_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, SvtAmdMdState *m, const MdSlotRecords &rec, bool inter, int grid, int n_active,
+                            const unsigned *d_order, int tiles)
+{
+    hipStream_t st = svt_amd_ctx_stream(ctx);
+    int rc;
+    m->grid = grid;
+    HIP_TRY(hipEventRecord(m->ev_k0, st));
+    if ((rc = md_launch_kernel(st, pic, m, inter, pic->d.bps, grid, n_active, (pic->d.width + 63) / 64, d_order)) != 0)
+        return rc;
+    HIP_TRY(hipEventRecord(m->ev_k1, st));
+    /* the encode pass of the picture: its own kernel behind the decisions, on the same stream (every LCU's work record is in HBM; LCUs without intra units wait for nobody,
+     * so a P / B picture runs as wide as the device is) */
+    if (m->d.encode && (rc = svt_amd_ep_launch_behind_md(ctx, pic, m->d_works, m->d_results, n_active, d_order, inter, tiles)) != 0)
+        return rc;
+    HIP_TRY(hipEventRecord(m->ev_k2, st));
+    if ((rc = ep_picture_written(ctx, pic)) != 0)
+        return rc;
+    return md_records_read_mark(ctx, rec);
+}
+
 /* bps: bytes per sample of the source planes, the work / result records and the picture object (1, or 2 = a 10-bit picture: the mode decision on the 8 MSBs of source
  * and reference pictures, the encode pass on the 10-bit samples) */
 static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdInter *X, const SvtAmdMdLcu *lcus,
@@ -3213,24 +3348,13 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
                           "the rectangle's tile-border check reads host records");
         return SVT_AMD_ERR_BAD_PARAM;
     }
-    DevPicture *rec_slot[2] = {nullptr, nullptr}; /* records read where another lane's kernels leave them: this lane's stream orders itself behind those kernels */
-    SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
+    MdSlotRecords rec = {ctx->parent ? ctx->parent : ctx, {nullptr, nullptr}, {-1, -1}};
     const SvtAmdMeLcuResult *d_me_slot = nullptr;
-    if (X && !me) {
-        if (!(d_me_slot = (const SvtAmdMeLcuResult *)svt_amd_slot_records(root, me_slot, 0, pic->d.width, pic->d.height))) {
-            svt_amd_set_error("svt_amd_md_encode_picture_inter: slot %d does not hold the motion-estimation records of a %u x %u picture (none launched for the slot's current picture, or only a part of it)", me_slot, pic->d.width, pic->d.height);
-            return SVT_AMD_ERR_BAD_PARAM;
-        }
-        rec_slot[0] = &root->slots[me_slot];
-    }
+    if (X && !me && !(d_me_slot = (const SvtAmdMeLcuResult *)md_slot_records(&rec, pic, 0, me_slot, "svt_amd_md_encode_picture_inter")))
+        return SVT_AMD_ERR_BAD_PARAM;
     const SvtAmdOisLcuResult *d_ois_slot = nullptr;
-    if (!ois) {
-        if (!(d_ois_slot = (const SvtAmdOisLcuResult *)svt_amd_slot_records(root, ois_slot, 1, pic->d.width, pic->d.height))) {
-            svt_amd_set_error("svt_amd_md_encode_picture: slot %d does not hold the open-loop intra search records of a %u x %u picture", ois_slot, pic->d.width, pic->d.height);
-            return SVT_AMD_ERR_BAD_PARAM;
-        }
-        rec_slot[1] = &root->slots[ois_slot];
-    }
+    if (!ois && !(d_ois_slot = (const SvtAmdOisLcuResult *)md_slot_records(&rec, pic, 1, ois_slot, "svt_amd_md_encode_picture")))
+        return SVT_AMD_ERR_BAD_PARAM;
     if (pic->md_rect_n) { /* a rank's rectangle (svt_amd_encdec_picture_set_rect; host controls only): its borders must be tile borders - an LCU never waits for one outside */
         const SvtAmdRect &r = pic->md_rect;
         const int x0 = r.x / 64, y0 = r.y / 64, x1 = (r.x + r.w + 63) / 64, y1 = (r.y + r.h + 63) / 64;
@@ -3252,9 +3376,8 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     if ((rc = md_state(pic, &m)) != 0)
         return rc;
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    for (int k = 0; k < 2; k++)
-        if (rec_slot[k] && (rc = svt_amd_records_wait(ctx, rec_slot[k], k, nullptr, nullptr, 0)) != 0)
-            return rc;
+    if ((rc = md_records_wait(ctx, rec)) != 0)
+        return rc;
     if (bound) { /* the host loop's refusals, its words and the tile count from the check kernel's record (mdctl_kernels.hip): one small copy, one synchronisation */
         const SvtAmdMdCtlCheck *c = (const SvtAmdMdCtlCheck *)(m->h_stage + MD_STAGE_CHECK);
         if ((rc = svt_amd_mdctl_check_async(ctx, bound, n, P->depth_mode, X != nullptr, (SvtAmdMdCtlCheck *)(m->h_stage + MD_STAGE_CHECK))) != 0)
@@ -3325,23 +3448,8 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
         m->d.src[k] = m->d_src[k], m->d.src16[k] = bps == 2 ? m->d_src16[k] : nullptr;
     }
     m->d.src_pitch[0] = linear ? stride_y : pic->d.pitch[0], m->d.src_pitch[1] = linear ? stride_c : pic->d.pitch[1];
-    for (int l = 0; l < 2; l++) { /* the reference pictures as the mode decision reads them */
-        m->d.mref[l] = pic->d.ref[l];
-        if (bps == 2 && X && pic->has_ref[l])
-            for (int p = 0; p < 3; p++) {
-                const size_t need = (size_t)pic->d.ref[l].size[p ? 1 : 0];
-                if (m->ref8_bytes[l][p] < need) {
-                    if (m->d_ref8[l][p])
-                        (void)hipFree(m->d_ref8[l][p]);
-                    m->d_ref8[l][p] = nullptr, m->ref8_bytes[l][p] = 0;
-                    HIP_TRY(hipMalloc((void **)&m->d_ref8[l][p], need + 16));
-                    m->ref8_bytes[l][p] = need;
-                }
-                if ((rc = msb_view(st, pic->d.ref[l].plane[p], m->d_ref8[l][p], need)) != 0)
-                    return rc;
-                m->d.mref[l].plane[p] = m->d_ref8[l][p];
-            }
-    }
+    if ((rc = md_reference_views(st, pic, m, X != nullptr)) != 0)
+        return rc;
     if (lcus)
         HIP_TRY(hipMemcpyAsync(m->d_lcus, lcus, sizeof(SvtAmdMdLcu) * (size_t)n, hipMemcpyHostToDevice, st));
     tick("LCU controls copy");
@@ -3366,8 +3474,6 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
             tick("motion-field copy + fill");
         }
         m->d.X = m->d_X, m->d.me = me ? m->d_me : d_me_slot, m->d.tmvp = X->tmvp_enable && bound_tmvp ? bound_tmvp : m->d_tmvp; /* a bound field is read in place */
-        HIP_TRY(hipMemsetAsync(m->d.md_mv, 0, m->mv_bytes, st));
-        tick("mv fill");
     }
     int n_active = n;
     const unsigned *d_order = pic->d_sync + 1 + n;
@@ -3375,106 +3481,32 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
         n_active = pic->md_rect_n, d_order = pic->d_order_md;
         HIP_TRY(hipMemsetAsync(m->d_out, 0, sizeof(SvtAmdMdLcuOut) * (size_t)n, st));
     }
-    m->d.prof = m->d_prof, m->d.prof_lcus = n;
-    m->d.trace = m->d_trace, m->d.trace_lcu = m->trace_lcu, m->d.trace_unit = m->trace_unit;
-    m->d.force_butterflies = m->force_butterflies;
+    md_descriptor_common(pic, m);
     m->d.encode = !X || works || results; /* P / B pictures: without a place for the work / result records, the mode decision alone */
     if (ois)
         HIP_TRY(hipMemcpyAsync(m->d_ois, ois, sizeof(SvtAmdOisLcuResult) * (size_t)n, hipMemcpyHostToDevice, st));
-    m->d.ois = ois ? m->d_ois : d_ois_slot, m->d.lcus = lcus ? m->d_lcus : bound, m->d.P = m->d_P, m->d.out = m->d_out;
+    m->d.ois = ois ? m->d_ois : d_ois_slot, m->d.lcus = lcus ? m->d_lcus : bound;
     pic->epoch++;
     pic->deblocked = pic->sao_done = false;
     pic->md_works_whole = false; /* until this call has run to its end */
     HIP_TRY(hipMemsetAsync(pic->d_sync, 0, sizeof(unsigned), st));
-    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, st));
-    HIP_TRY(hipMemsetAsync(m->d.md_info, 0xFF, m->info_bytes, st));
-    HIP_TRY(hipMemsetAsync(m->d_results, 0, m->result_bytes * (size_t)n, st));
-    HIP_TRY(hipMemsetAsync(m->d_works, 0, m->work_bytes * (size_t)n, st));
-    tick("OIS copy + five fills");
-    if ((rc = md_kernel_attributes(ctx->device)) != 0)
+    if ((rc = md_reset_arrays(st, pic, m, X != nullptr)) != 0)
         return rc;
+    tick("OIS copy + five fills"); /* (and the vector fill of a P / B picture) */
     if (timing) {
         HIP_TRY(hipStreamSynchronize(st));
         tick("stream synchronisation after the uploads");
         t_up = std::chrono::steady_clock::now();
     }
-    /* the wavefront is at most min((W/64 + 1) / 2, H/64) LCUs wide; the mode decision runs ahead of the encode pass, so twice that many workgroups
-     * find work (all of them resident: a workgroup that waits holds its CU) */
-    /* ... but a workgroup holds a whole CU (its LDS) while it waits, and the encoder keeps several pictures in flight: five 62-workgroup launches do not fit the 256 CUs.
-     * The wavefront of a picture is (W/64 + 1) / 2 LCUs wide at its widest and 16 on average at 4K; one workgroup per LCU of the widest front plus a few for the encode
-     * passes behind it costs a lone picture 3 - 4 % and lets six pictures' launches run side by side (profiles/r04_w_md_flights_*: the kernel keeps its 51 ms with
-     * twelve calls in flight, 100 pictures/s - given enough hardware queues, svt_amd_runtime_env_defaults). */
-    /* Round 6: a lone picture on an idle device gets two workgroups per LCU of the widest front again - behind an LCU's decisions its workgroup spends ~15 % of the LCU's
-     * time on the merge / skip decisions with chroma and the work record, ahead of them on the next LCU's inputs, and with one workgroup per LCU of the front a ready LCU
-     * waits for a workgroup (4K: 40 / 48 / 56 / 64 workgroups = 27.1 / 27.05 / 26.85 / 26.7 ms for a layer-2 picture).  The widths a launch gets while other pictures' launches
-     * are on the device - the encoder's steady state - stay what round 5 measured best (40 / 20 at 4K). */
-    const int front = ((wl + 1) / 2 < hl ? (wl + 1) / 2 : hl) * (tiles > 0 ? tiles : 1);
-    int lone = 2 * front + 2;
-    int grid = front + 2 + (wl + 7) / 8;
-    int narrow = (grid + 1) / 2 < 8 ? 8 : (grid + 1) / 2; /* what the launch gets while other pictures share the device (MdFlight) */
-    {   /* measurement (SVT_AMD_MD_GRID): a fixed launch width */
-        const char *fg = getenv("SVT_AMD_MD_GRID");
-        const int forced = fg ? atoi(fg) : 0;
-        if (forced > 0)
-            lone = grid = narrow = forced;
-        static const int fnarrow = getenv("SVT_AMD_MD_NARROW") ? atoi(getenv("SVT_AMD_MD_NARROW")) : 0;
-        if (fnarrow > 0)
-            narrow = fnarrow;
-        static const int fwide = getenv("SVT_AMD_MD_WIDE") ? atoi(getenv("SVT_AMD_MD_WIDE")) : 0;
-        if (fwide > 0)
-            lone = grid = fwide;
-    }
-    grid = grid > n_active ? n_active : grid > 224 ? 224 : grid;
-    lone = lone > n_active ? n_active : lone > 224 ? 224 : lone;
-    lone = lone < grid ? grid : lone;
-    narrow = narrow > grid ? grid : narrow;
-    m->d.cost = pic->has_cost ? pic->d_cost : nullptr;
+    const MdWidths width = md_launch_widths(wl, hl, tiles, n_active);
     memcpy(m->h_stage + MD_STAGE_D, &m->d, sizeof(m->d));
     HIP_TRY(hipMemcpyAsync(m->d_D, m->h_stage + MD_STAGE_D, sizeof(m->d), hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(m->d_md_ticket, 0, sizeof(unsigned), st));
     MdFlight flight;
     /* the inputs first (a call that waits for its place holds no CU and no copy engine meanwhile) */
     HIP_TRY(hipStreamSynchronize(st));
-    grid = flight.acquire(ctx->device, md_wg_budget(ctx->device), lone, grid, narrow, (int)P->temporal_layer);
-    m->grid = grid;
-    HIP_TRY(hipEventRecord(m->ev_k0, st));
-    const bool profiled = m->d.prof != nullptr; /* (the P / B kernels exist with and without the stage marks) */
-    if (X && bps == 1 && !profiled)
-        hipLaunchKernelGGL((k_md_picture<true, uint8_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else if (X && bps == 1)
-        hipLaunchKernelGGL((k_md_picture<true, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-#ifdef MD_INTER8_ONLY
-    else
-        return SVT_AMD_ERR_BAD_PARAM;
-#else
-    else if (bps == 1)
-        hipLaunchKernelGGL((k_md_picture<false, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else if (X && !profiled)
-        hipLaunchKernelGGL((k_md_picture<true, uint16_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else if (X)
-        hipLaunchKernelGGL((k_md_picture<true, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else
-        hipLaunchKernelGGL((k_md_picture<false, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-#endif
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(m->ev_k1, st));
-    /* the encode pass of the picture: its own kernel behind the decisions, on the same stream (every LCU's work record is in HBM; LCUs without intra units wait for nobody,
-     * so a P / B picture runs as wide as the device is) */
-    if (m->d.encode && (rc = svt_amd_ep_launch_behind_md(ctx, pic, m->d_works, m->d_results, n_active, d_order, X != nullptr, tiles)) != 0)
-        return rc;
-    HIP_TRY(hipEventRecord(m->ev_k2, st));
-    if ((rc = ep_picture_written(ctx, pic)) != 0)
-        return rc;
-    /* records read in place: the next motion-estimation / open-loop intra launch INTO those slots orders itself behind this kernel */
-    if (rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, me_slot)) != 0)
-        return rc;
-    if (rec_slot[1] && rec_slot[1] != rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, ois_slot)) != 0)
+    const int grid = flight.acquire(ctx->device, md_wg_budget(ctx->device), width.lone, width.wide, width.narrow, (int)P->temporal_layer);
+    if ((rc = md_queue_picture(ctx, pic, m, rec, X != nullptr, grid, n_active, d_order, tiles)) != 0)
         return rc;
     if (timing) {
         HIP_TRY(hipStreamSynchronize(st));
@@ -3501,26 +3533,28 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     return SVT_AMD_OK;
 }
 
+/* a call the entry refuses by itself consumes the bindings as md_encode_picture would */
+static int md_refuse_unbound(SvtAmdEncDecPicture *pic)
+{
+    if (pic)
+        pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
+    return SVT_AMD_ERR_BAD_PARAM;
+}
+
 extern "C" int svt_amd_md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus, const uint8_t *src_y,
                                          uint32_t stride_y, const uint8_t *src_cb, const uint8_t *src_cr, uint32_t stride_c, const SvtAmdOisLcuResult *ois,
                                          int ois_slot, const SvtAmdCabacCost *cost, SvtAmdMdLcuOut *md_out, SvtAmdLcuWork *works, SvtAmdLcuResult *results)
 {
-    if (!cost) {
-        if (pic)
-            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
-        return SVT_AMD_ERR_BAD_PARAM;
-    }
+    if (!cost)
+        return md_refuse_unbound(pic);
     return md_encode_picture(ctx, pic, P, nullptr, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, nullptr, -1, nullptr, cost, md_out, works, results, 1);
 }
 extern "C" int svt_amd_md_encode_picture16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus, const uint16_t *src_y,
                                            uint32_t stride_y, const uint16_t *src_cb, const uint16_t *src_cr, uint32_t stride_c, const SvtAmdOisLcuResult *ois,
                                            int ois_slot, const SvtAmdCabacCost *cost, SvtAmdMdLcuOut *md_out, SvtAmdLcuWork16 *works, SvtAmdLcuResult16 *results)
 {
-    if (!cost) {
-        if (pic)
-            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
-        return SVT_AMD_ERR_BAD_PARAM;
-    }
+    if (!cost)
+        return md_refuse_unbound(pic);
     return md_encode_picture(ctx, pic, P, nullptr, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, nullptr, -1, nullptr, cost, md_out, works, results, 2);
 }
 
@@ -3529,11 +3563,8 @@ extern "C" int svt_amd_md_encode_picture_inter(SvtAmdContext *ctx, SvtAmdEncDecP
                                                const SvtAmdOisLcuResult *ois, int ois_slot, const SvtAmdMeLcuResult *me, int me_slot, const SvtAmdTmvpLcu *tmvp,
                                                SvtAmdMdLcuOut *md_out, SvtAmdLcuWork *works, SvtAmdLcuResult *results)
 {
-    if (!X) {
-        if (pic)
-            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
-        return SVT_AMD_ERR_BAD_PARAM;
-    }
+    if (!X)
+        return md_refuse_unbound(pic);
     return md_encode_picture(ctx, pic, P, X, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, me, me_slot, tmvp, nullptr, md_out, works, results, 1);
 }
 extern "C" int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdPicture *P, const SvtAmdMdInter *X, const SvtAmdMdLcu *lcus,
@@ -3541,73 +3572,14 @@ extern "C" int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncDe
                                                  const SvtAmdOisLcuResult *ois, int ois_slot, const SvtAmdMeLcuResult *me, int me_slot, const SvtAmdTmvpLcu *tmvp,
                                                  SvtAmdMdLcuOut *md_out, SvtAmdLcuWork16 *works, SvtAmdLcuResult16 *results)
 {
-    if (!X) {
-        if (pic)
-            pic->md_bound_lcus = nullptr, pic->md_bound_tmvp = nullptr;
-        return SVT_AMD_ERR_BAD_PARAM;
-    }
+    if (!X)
+        return md_refuse_unbound(pic);
     return md_encode_picture(ctx, pic, P, X, lcus, src_y, stride_y, src_cb, src_cr, stride_c, ois, ois_slot, me, me_slot, tmvp, nullptr, md_out, works, results, 2);
 }
 
 /* ---- the stream-ordered launch on device inputs (include/svt_hevc_amd.h: svt_amd_md_encode_picture_launch) ---- */
 #define MDL_ENTRY "svt_amd_md_encode_picture_launch"
 #define MDL_BAD(...) do { svt_amd_set_error(MDL_ENTRY ": " __VA_ARGS__); return SVT_AMD_ERR_BAD_PARAM; } while (0)
-
-/* the blocking call's launch widths (md_encode_picture, above: the formulas, their measurements and the measurement overrides SVT_AMD_MD_GRID / _NARROW / _WIDE), kept
- * in step with it by hand: a launch takes `lone` or `narrow` */
-static void md_launch_widths(int wl, int hl, int tiles, int n_active, int *lone_out, int *narrow_out)
-{
-    const int front = ((wl + 1) / 2 < hl ? (wl + 1) / 2 : hl) * (tiles > 0 ? tiles : 1);
-    int lone = 2 * front + 2;
-    int grid = front + 2 + (wl + 7) / 8;
-    int narrow = (grid + 1) / 2 < 8 ? 8 : (grid + 1) / 2;
-    const char *fg = getenv("SVT_AMD_MD_GRID"); /* measurement: a fixed launch width */
-    const int forced = fg ? atoi(fg) : 0;
-    if (forced > 0)
-        lone = grid = narrow = forced;
-    static const int fnarrow = getenv("SVT_AMD_MD_NARROW") ? atoi(getenv("SVT_AMD_MD_NARROW")) : 0;
-    if (fnarrow > 0)
-        narrow = fnarrow;
-    static const int fwide = getenv("SVT_AMD_MD_WIDE") ? atoi(getenv("SVT_AMD_MD_WIDE")) : 0;
-    if (fwide > 0)
-        lone = grid = fwide;
-    grid = grid > n_active ? n_active : grid > 224 ? 224 : grid;
-    lone = lone > n_active ? n_active : lone > 224 ? 224 : lone;
-    lone = lone < grid ? grid : lone;
-    narrow = narrow > grid ? grid : narrow;
-    *lone_out = lone, *narrow_out = narrow;
-}
-
-/* the instance of k_md_picture the blocking call launches for the same picture */
-static int md_launch_kernel(hipStream_t st, SvtAmdEncDecPicture *pic, SvtAmdMdState *m, bool inter, uint32_t bps, int grid, int n_active, int wl, const unsigned *d_order)
-{
-    const bool profiled = m->d.prof != nullptr;
-    if (inter && bps == 1 && !profiled)
-        hipLaunchKernelGGL((k_md_picture<true, uint8_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else if (inter && bps == 1)
-        hipLaunchKernelGGL((k_md_picture<true, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-#ifdef MD_INTER8_ONLY
-    else
-        return SVT_AMD_ERR_BAD_PARAM;
-#else
-    else if (bps == 1)
-        hipLaunchKernelGGL((k_md_picture<false, uint8_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else if (inter && !profiled)
-        hipLaunchKernelGGL((k_md_picture<true, uint16_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else if (inter)
-        hipLaunchKernelGGL((k_md_picture<true, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-    else
-        hipLaunchKernelGGL((k_md_picture<false, uint16_t, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork16 *)m->d_works, n_active, wl, m->d_md_ticket,
-                           m->d_md_done, d_order, pic->epoch);
-#endif
-    HIP_TRY(hipGetLastError());
-    return SVT_AMD_OK;
-}
 
 extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLaunchJob *job, SvtAmdMdLaunchStatus *d_status)
 {
@@ -3647,21 +3619,13 @@ extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDec
         MDL_BAD("the motion field at %p is not 8-byte aligned", (const void *)job->d_tmvp);
     if (pic->md_rect_n)
         MDL_BAD("the picture object has a rank rectangle (svt_amd_encdec_picture_set_rect): the rectangle's tile-border check reads host records");
-    DevPicture *rec_slot[2] = {nullptr, nullptr};
-    SvtAmdContext *root = ctx->parent ? ctx->parent : ctx;
+    MdSlotRecords rec = {ctx->parent ? ctx->parent : ctx, {nullptr, nullptr}, {-1, -1}};
     const SvtAmdMeLcuResult *d_me = X ? job->d_me : nullptr;
-    if (X && !d_me) {
-        if (!(d_me = (const SvtAmdMeLcuResult *)svt_amd_slot_records(root, job->me_slot, 0, pic->d.width, pic->d.height)))
-            MDL_BAD("slot %d does not hold the motion-estimation records of a %u x %u picture (none launched for the slot's current picture, or only a part of it)",
-                    job->me_slot, pic->d.width, pic->d.height);
-        rec_slot[0] = &root->slots[job->me_slot];
-    }
+    if (X && !d_me && !(d_me = (const SvtAmdMeLcuResult *)md_slot_records(&rec, pic, 0, job->me_slot, MDL_ENTRY)))
+        return SVT_AMD_ERR_BAD_PARAM;
     const SvtAmdOisLcuResult *d_ois = job->d_ois;
-    if (!d_ois) {
-        if (!(d_ois = (const SvtAmdOisLcuResult *)svt_amd_slot_records(root, job->ois_slot, 1, pic->d.width, pic->d.height)))
-            MDL_BAD("slot %d does not hold the open-loop intra search records of a %u x %u picture", job->ois_slot, pic->d.width, pic->d.height);
-        rec_slot[1] = &root->slots[job->ois_slot];
-    }
+    if (!d_ois && !(d_ois = (const SvtAmdOisLcuResult *)md_slot_records(&rec, pic, 1, job->ois_slot, MDL_ENTRY)))
+        return SVT_AMD_ERR_BAD_PARAM;
 
     /* ---- nothing below reads host memory after the call has returned, copies or waits ---- */
     HIP_TRY(hipSetDevice(ctx->device));
@@ -3672,9 +3636,8 @@ extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDec
     if ((rc = md_state(pic, &m)) != 0) /* allocates at the first call on the object */
         return rc;
     hipStream_t st = svt_amd_ctx_stream(ctx);
-    for (int k = 0; k < 2; k++)
-        if (rec_slot[k] && (rc = svt_amd_records_wait(ctx, rec_slot[k], k, nullptr, nullptr, 0)) != 0)
-            return rc;
+    if ((rc = md_records_wait(ctx, rec)) != 0)
+        return rc;
     /* the source: the caller's planes into the object's own, at the object's pitch (the blocking call's strided form) */
     MdSourcePlanes S;
     memset(&S, 0, sizeof(S));
@@ -3688,33 +3651,15 @@ extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDec
     m->d.src_pitch[0] = pic->d.pitch[0], m->d.src_pitch[1] = pic->d.pitch[1];
     if ((rc = svt_amd_mdlaunch_source(ctx, &S, (int)bps)) != 0)
         return rc;
-    for (int l = 0; l < 2; l++) { /* the reference pictures as the mode decision reads them (md_encode_picture) */
-        m->d.mref[l] = pic->d.ref[l];
-        if (bps == 2 && X && pic->has_ref[l])
-            for (int p = 0; p < 3; p++) {
-                const size_t need = (size_t)pic->d.ref[l].size[p ? 1 : 0];
-                if (m->ref8_bytes[l][p] < need) { /* the first P / B launch of a 10-bit object, or reference pictures with more padding than any before */
-                    if (m->d_ref8[l][p])
-                        (void)hipFree(m->d_ref8[l][p]);
-                    m->d_ref8[l][p] = nullptr, m->ref8_bytes[l][p] = 0;
-                    HIP_TRY(hipMalloc((void **)&m->d_ref8[l][p], need + 16));
-                    m->ref8_bytes[l][p] = need;
-                }
-                if ((rc = msb_view(st, pic->d.ref[l].plane[p], m->d_ref8[l][p], need)) != 0)
-                    return rc;
-                m->d.mref[l].plane[p] = m->d_ref8[l][p];
-            }
-    }
+    if ((rc = md_reference_views(st, pic, m, X != nullptr)) != 0)
+        return rc;
     /* the small inputs and the descriptor: by value, in k_md_stage's argument block */
     if (job->cost)
         pic->has_cost = true;
     m->d.X = X ? m->d_X : nullptr, m->d.me = d_me, m->d.tmvp = X ? (X->tmvp_enable ? job->d_tmvp : m->d_tmvp) : nullptr;
-    m->d.prof = m->d_prof, m->d.prof_lcus = n;
-    m->d.trace = m->d_trace, m->d.trace_lcu = m->trace_lcu, m->d.trace_unit = m->trace_unit;
-    m->d.force_butterflies = m->force_butterflies;
+    md_descriptor_common(pic, m);
     m->d.encode = !X || !(job->flags & SVT_AMD_MD_LAUNCH_DECIDE_ONLY);
-    m->d.ois = d_ois, m->d.lcus = job->d_lcus, m->d.P = m->d_P, m->d.out = m->d_out;
-    m->d.cost = pic->d_cost;
+    m->d.ois = d_ois, m->d.lcus = job->d_lcus;
     MdStagePart parts[4];
     int nparts = 0;
     parts[nparts++] = MdStagePart{m->d_P, P, sizeof(*P)};
@@ -3734,36 +3679,16 @@ extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDec
         return rc;
     if ((rc = svt_amd_mdlaunch_gate(ctx, d_check, m->d_md_ticket, pic->d_sync, (unsigned)n, d_status)) != 0)
         return rc;
-    if (X)
-        HIP_TRY(hipMemsetAsync(m->d.md_mv, 0, m->mv_bytes, st));
-    HIP_TRY(hipMemsetAsync(pic->d.mode_map, 0xFF, pic->map_bytes, st));
-    HIP_TRY(hipMemsetAsync(m->d.md_info, 0xFF, m->info_bytes, st));
-    HIP_TRY(hipMemsetAsync(m->d_results, 0, m->result_bytes * (size_t)n, st));
-    HIP_TRY(hipMemsetAsync(m->d_works, 0, m->work_bytes * (size_t)n, st));
-    if ((rc = md_kernel_attributes(ctx->device)) != 0)
+    if ((rc = md_reset_arrays(st, pic, m, X != nullptr)) != 0)
         return rc;
     /* a launch cannot wait for the blocking calls' workgroup budget (MdFlight) and holds none of it: the lone picture's width when the budget shows no flight now */
-    int lone, narrow, flights;
-    md_launch_widths(wl, hl, (int)job->tiles, n, &lone, &narrow);
+    const MdWidths width = md_launch_widths(wl, hl, (int)job->tiles, n);
+    int flights;
     {
         std::lock_guard<std::mutex> l(g_flight_mu);
         flights = g_flight_dev[ctx->device & 63].flights;
     }
-    const int grid = flights == 0 ? lone : narrow;
-    m->grid = grid;
-    const unsigned *d_order = pic->d_sync + 1 + n;
-    HIP_TRY(hipEventRecord(m->ev_k0, st));
-    if ((rc = md_launch_kernel(st, pic, m, X != nullptr, bps, grid, n, wl, d_order)) != 0)
-        return rc;
-    HIP_TRY(hipEventRecord(m->ev_k1, st));
-    if (m->d.encode && (rc = svt_amd_ep_launch_behind_md(ctx, pic, m->d_works, m->d_results, n, d_order, X != nullptr, (int)job->tiles)) != 0)
-        return rc;
-    HIP_TRY(hipEventRecord(m->ev_k2, st));
-    if ((rc = ep_picture_written(ctx, pic)) != 0)
-        return rc;
-    if (rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, job->me_slot)) != 0)
-        return rc;
-    if (rec_slot[1] && rec_slot[1] != rec_slot[0] && (rc = svt_amd_records_read_mark(ctx, root, job->ois_slot)) != 0)
+    if ((rc = md_queue_picture(ctx, pic, m, rec, X != nullptr, flights == 0 ? width.lone : width.narrow, n, pic->d_sync + 1 + n, (int)job->tiles)) != 0)
         return rc;
     pic->md_works_whole = m->d.encode != 0; /* at queue time: the tail and the motion field queue behind this launch in stream order */
     return SVT_AMD_OK;
@@ -3855,8 +3780,7 @@ extern "C" int svt_amd_debug_md_flights(int *in_flight, int *workgroups_held, in
 }
 extern "C" int svt_amd_debug_md_kernel_lds_bytes(int inter, int bytes_per_sample)
 {
-    if (bytes_per_sample == 2)
-        return (int)(inter ? sizeof(MdShared<true>) : sizeof(MdShared<false>)) + (int)sizeof(MdPictureDev);
+    (void)bytes_per_sample; /* (MdShared does not depend on the sample width) */
     return (int)(inter ? sizeof(MdShared<true>) : sizeof(MdShared<false>)) + (int)sizeof(MdPictureDev);
 }
 

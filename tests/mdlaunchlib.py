@@ -43,8 +43,16 @@ def declare(lib):
     lib.svt_amd_md_picture_supported.restype, lib.svt_amd_md_picture_supported.argtypes = C.c_int, [vp]
     lib.svt_amd_md_picture_warmup.restype, lib.svt_amd_md_picture_warmup.argtypes = C.c_int, [vp, vp]
     lib.svt_amd_synchronize.restype, lib.svt_amd_synchronize.argtypes = C.c_int, [vp]
+    lib.svt_amd_debug_md_kernel_ms.restype, lib.svt_amd_debug_md_kernel_ms.argtypes = C.c_int, [vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]
     lib.svt_amd_last_error.restype = C.c_char_p
     return lib
+
+
+def kernel_width(lib, ctx, pic):
+    """the workgroups of the picture object's last mode-decision kernel, blocking call or launch (svt_amd_debug_md_kernel_ms waits for that kernel)"""
+    ms, workgroups = C.c_float(), C.c_int(-1)
+    ok(lib, lib.svt_amd_debug_md_kernel_ms(ctx, pic, C.byref(ms), C.byref(workgroups)))
+    return workgroups.value
 
 
 def up(n):

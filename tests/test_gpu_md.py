@@ -350,6 +350,12 @@ def test_md_of_a_b_picture_reads_me_and_ois_records_another_lane_left_in_hbm(pro
         assert int(in_place["tested"].sum()) >= wd.nl
         rc, _ = wd.call(1, None, None, 3)                   # a slot no motion estimation / intra search has written
         assert rc != 0
+        assert lib.svt_amd_last_error() == (b"svt_amd_md_encode_picture_inter: slot 3 does not hold the motion-estimation records of a 416 x 240 picture "
+                                            b"(none launched for the slot's current picture, or only a part of it)")
+        me_h = np.zeros(wd.nl, S.ME_LCU_DTYPE)              # (never read: the intra search records are refused first)
+        rc, _ = wd.call(1, me_h.ctypes.data, None, 3)
+        assert rc != 0
+        assert lib.svt_amd_last_error() == b"svt_amd_md_encode_picture: slot 3 does not hold the open-loop intra search records of a 416 x 240 picture"
     finally:
         wd.close()
 
