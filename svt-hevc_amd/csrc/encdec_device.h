@@ -82,6 +82,32 @@ int svt_amd_md_picture_records(const SvtAmdEncDecPicture *pic, const void **d_wo
 /* encdec_kernels.hip: the encode pass of every LCU of the picture from work records the mode-decision kernel left in HBM, queued on ctx's stream behind it */
 int svt_amd_ep_launch_behind_md(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const void *d_works, void *d_results, int n_active, const unsigned *d_order, int inter, int tiles);
 
+/* ---- the picture tail's device chain (tail_kernels.hip): deblocking, SAO and reference padding queued on ctx's stream.  svt_amd_encdec_picture_tail_launch and the
+ * blocking entries svt_amd_encdec_picture_deblock / _sao / _sao_decide / _reference (encdec_kernels.hip) call the same three steps; they differ in where the inputs come
+ * from (k_tail_maps on records in HBM / host loops and uploads) and in what they wait for. ---- */
+struct SvtAmdTailPointers {        /* DEVICE memory the chain reads and writes: carved from the object's tail state, or from the context scratch of a blocking entry */
+    uint32_t *map;                 /* SvtAmdCuMapEntry[(height / 8) * (width / 8)] */
+    uint8_t *cbf, *qp;             /* [(height / 4) * (width / 4)], [(height / 8) * (width / 8)] */
+    uint8_t *edge, *follow;        /* [LCUs]: the deblocking edge byte; bit 0 an LCU of the same tile follows to the right, bit 1 below */
+    uint8_t *bsv, *bsh;            /* boundary strengths, 256 bytes an LCU each */
+    uint8_t *src[3], *cmp[3];      /* source planes and the encoder-order composite, the picture's pitches */
+    SvtAmdSaoStats *stats[3];      /* one run of stats_bytes bytes from stats[0] */
+    size_t stats_bytes;
+    SvtAmdSaoLcuParams *par;       /* [LCUs]: edge_flags in, the decision out */
+    int64_t *cost;
+};
+static inline bool svt_amd_tail_origin_ok(uint32_t ox, uint32_t oy) { return ox >= 8 && oy >= 8 && !(ox & 1) && !(oy & 1) && ox <= 256 && oy <= 256; }
+/* the object's lazily allocated stages: dbk[] / fin[] where wanted, refp[] for a padding (origin_x 0: none); sets the error text */
+int svt_amd_tail_stage_planes(SvtAmdEncDecPicture *pic, bool dbk, bool fin, uint32_t origin_x, uint32_t origin_y);
+/* boundary strengths from map / cbf / edge, rec[] copied to dbk[] and deblocked there (qp); the object counts as deblocked */
+int svt_amd_tail_queue_deblock(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdTailPointers &p, const SvtAmdDeblockParams *prm);
+/* statistics zeroed, the encoder-order composite of dbk[] and rec[] (follow) when `composite`, the statistics of src[] against cmp[] (composite) or rec[], the decision into
+ * par (d_enable: device bytes or null), dbk[] filtered into fin[] when `apply` */
+int svt_amd_tail_queue_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdTailPointers &p, const SvtAmdSaoDecisionParams *prm, const uint8_t *d_enable, bool composite,
+                           bool apply);
+/* the object's latest stage (after SAO, else deblocked, else as encoded) inside its padding in refp[]; `ref` describes it */
+int svt_amd_tail_queue_reference(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, uint32_t origin_x, uint32_t origin_y, SvtAmdRefPicture *ref);
+
 typedef SvtAmdLcuCu LcuCu;
 /* the contract structs of a sample type */
 template <typename T> struct EpTypes;

@@ -524,15 +524,6 @@ extern "C" int svt_amd_encdec_picture_exchange(SvtAmdContext *ctx, SvtAmdEncDecP
  * SAO-filtered: nothing else of the picture exists on them).  _broadcast: ncclBroadcast on the context's communicator; _import: the same hand-over between two
  * picture objects of one process (logical ranks on one device, peers with direct access, or a host with its own transport), a device-to-device copy. */
 extern "C" int svt_amd_recon_broadcast(SvtAmdContext *ctx, void *const d_planes[3], const size_t bytes[3], int world, int rank, int root);
-static int final_stage_planes(SvtAmdEncDecPicture *pic) /* the final stage's planes exist from the first SAO call, or from here */
-{
-    for (int k = 0; k < 3; k++)
-        if (!pic->fin[k] && hipMalloc((void **)&pic->fin[k], pic->plane_bytes[k]) != hipSuccess) {
-            svt_amd_set_error("hipMalloc (finished picture) failed");
-            return SVT_AMD_ERR_RESOURCES;
-        }
-    return SVT_AMD_OK;
-}
 extern "C" int svt_amd_encdec_picture_broadcast(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, int world, int rank, int root)
 {
     if (!ctx || !pic || world < 1 || rank < 0 || rank >= world || root < 0 || root >= world)
@@ -540,7 +531,7 @@ extern "C" int svt_amd_encdec_picture_broadcast(SvtAmdContext *ctx, SvtAmdEncDec
     if (world == 1)
         return SVT_AMD_OK;
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = rank != root ? final_stage_planes(pic) : SVT_AMD_OK;
+    int rc = rank != root ? svt_amd_tail_stage_planes(pic, false, true, 0, 0) : SVT_AMD_OK; /* the final stage's planes exist from the first SAO call, or from here */
     if (rc)
         return rc;
     uint8_t *const *stage = rank != root ? pic->fin : pic->sao_done ? pic->fin : pic->deblocked ? pic->dbk : pic->d.rec;
@@ -562,7 +553,7 @@ extern "C" int svt_amd_encdec_picture_import(SvtAmdContext *ctx, SvtAmdEncDecPic
         return SVT_AMD_ERR_BAD_PARAM;
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    int rc = final_stage_planes(pic);
+    int rc = svt_amd_tail_stage_planes(pic, false, true, 0, 0);
     if (rc)
         return rc;
     /* behind whatever the owner's stream still has queued on the source picture (its encode pass / filters run on another context, possibly another device) */
@@ -619,9 +610,10 @@ extern "C" int svt_amd_encode_picture_device_inter16(SvtAmdContext *ctx, SvtAmdE
 
 /* ---- deblocking behind the encode pass ------------------------------------------------------------------------------------------ */
 /* Once every LCU of the picture is encoded (svt_amd_encode_picture, or LCU by LCU), the device picture goes through the
- * picture-level boundary-strength and deblocking kernels (filter_kernels.hip, proven on recorded pictures) IN PLACE: what the
- * reference's reconstruction holds after its per-LCU drivers - the finished picture when SAO is off.  The two maps those kernels
- * read (coding unit per 8x8 block, luma cbf per 4x4 block) and the QP array come from the contract records the host already has. */
+ * picture-level boundary-strength and deblocking kernels (filter_kernels.hip, proven on recorded pictures; queued by
+ * svt_amd_tail_queue_deblock, tail_kernels.hip): what the reference's reconstruction holds after its per-LCU drivers - the finished
+ * picture when SAO is off.  The two maps those kernels read (coding unit per 8x8 block, luma cbf per 4x4 block) and the QP array come
+ * from the contract records the host already has: this entry's part is the host loop over them, the upload and the download. */
 template <typename T>
 static int picture_deblock(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typename EpTypes<T>::Work *works, const typename EpTypes<T>::Result *results,
                            const SvtAmdDeblockParams *prm, void *out_y, void *out_cb, void *out_cr)
@@ -663,37 +655,24 @@ static int picture_deblock(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const t
             }
         }
     }
+    if (prm->slice_type > 3 || pic->d.pitch[1] != pic->d.pitch[2]) /* what the chain would refuse, before anything is allocated or queued */
+        return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t b_map = (map.size() * sizeof(SvtAmdCuMapEntry) + 255) & ~(size_t)255, b_cbf = (cbf.size() + 255) & ~(size_t)255,
                  b_qp = (qp.size() + 255) & ~(size_t)255, b_edge = ((size_t)nlcu + 255) & ~(size_t)255, b_bs = (size_t)nlcu * 256;
     uint8_t *d = nullptr;
     int rc = svt_amd_ctx_scratch(ctx, b_map + b_cbf + b_qp + b_edge + 2 * b_bs, &d);
-    if (rc)
+    if (rc || (rc = svt_amd_tail_stage_planes(pic, true, false, 0, 0)) != 0)
         return rc;
-    uint8_t *d_map = d, *d_cbf = d_map + b_map, *d_qp = d_cbf + b_cbf, *d_edge = d_qp + b_qp, *d_bsv = d_edge + b_edge, *d_bsh = d_bsv + b_bs;
-    HIP_TRY(hipMemcpyAsync(d_map, map.data(), map.size() * sizeof(SvtAmdCuMapEntry), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
-    HIP_TRY(hipMemcpyAsync(d_cbf, cbf.data(), cbf.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
-    HIP_TRY(hipMemcpyAsync(d_qp, qp.data(), qp.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
-    HIP_TRY(hipMemcpyAsync(d_edge, edge.data(), edge.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    SvtAmdTailPointers p = {};
+    p.map = (uint32_t *)d, p.cbf = d + b_map, p.qp = p.cbf + b_cbf, p.edge = p.qp + b_qp, p.bsv = p.edge + b_edge, p.bsh = p.bsv + b_bs;
+    HIP_TRY(hipMemcpyAsync(p.map, map.data(), map.size() * sizeof(SvtAmdCuMapEntry), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(p.cbf, cbf.data(), cbf.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(p.qp, qp.data(), qp.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(p.edge, edge.data(), edge.size(), hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     HIP_TRY(svt_amd_ctx_sync(ctx)); /* the host vectors back the copies */
-    if ((rc = svt_amd_bs_picture(ctx, (const SvtAmdCuMapEntry *)d_map, d_cbf, w, h, prm->slice_type, prm->ref_poc[0], prm->ref_poc[1], d_edge, d_bsv,
-                                 d_bsh)) != 0)
+    if ((rc = svt_amd_tail_queue_deblock(ctx, pic, p, prm)) != 0)
         return rc;
-    if (pic->d.pitch[1] != pic->d.pitch[2])
-        return SVT_AMD_ERR_BAD_PARAM;
-    /* the deblocked picture is a second set of planes: the un-deblocked one stays (the neighbours of LCUs still to come, and the part of
-     * the SAO statistics that the reference gathers before an LCU's right / bottom edges are filtered) */
-    for (int k = 0; k < 3; k++) {
-        if (!pic->dbk[k] && hipMalloc((void **)&pic->dbk[k], pic->plane_bytes[k]) != hipSuccess) {
-            svt_amd_set_error("hipMalloc (deblocked picture) failed");
-            return SVT_AMD_ERR_RESOURCES;
-        }
-        HIP_TRY(hipMemcpyAsync(pic->dbk[k], pic->d.rec[k], pic->plane_bytes[k], hipMemcpyDeviceToDevice, svt_amd_ctx_stream(ctx)));
-    }
-    if ((rc = svt_amd_dlf_picture(ctx, (int)sizeof(T), pic->dbk[0], pic->d.pitch[0], pic->dbk[1], pic->dbk[2], pic->d.pitch[1], w, h, d_bsv, d_bsh,
-                                  d_qp, w8, prm->tc_offset, prm->beta_offset, prm->cb_qp_offset, prm->cr_qp_offset)) != 0)
-        return rc;
-    pic->deblocked = true;
     if ((rc = ep_picture_written(ctx, pic)) != 0)
         return rc;
     void *outs[3] = {out_y, out_cb, out_cr};
@@ -729,27 +708,9 @@ __global__ __launch_bounds__(256) void k_ep_source_planes(const typename EpTypes
     }
 }
 
-/* The picture as the reference's SaoGenerationDecision sees each LCU (EbCodingLoop.c:4600-4750): the LCU's own deblocking drivers have run,
- * those of the LCUs to its right and below have not.  Those later drivers own the 8x8 filter blocks centred on the LCU boundary
- * (LCUBoundaryDLFCore, EbDeblockingFilter.c:2828), i.e. every edge segment inside the last 4 columns / rows of the LCU (in the plane's own
- * samples) and nothing else inside it: the LCU is the deblocked picture with those strips still un-deblocked, where a neighbour OF THE SAME
- * TILE follows (at picture and tile edges the LCU's own LCUPictureEdgeDLFCore has finished them; follow: bit 0 right, bit 1 below).
- * (tests/test_oracle_encodepass_golden.py::test_encoder_order_sao_statistics_from_two_pictures proves it on the encoder's own records.) */
-template <typename T>
-__global__ __launch_bounds__(256) void k_ep_sao_composite(const T *__restrict__ dbk, const T *__restrict__ rec, T *__restrict__ out, int pitch, int w, int h,
-                                                          int lg_lcu, int wl, const uint8_t *__restrict__ follow)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, lcu = 1 << lg_lcu;
-    if (x >= w)
-        return;
-    const int f = follow[(y >> lg_lcu) * wl + (x >> lg_lcu)];
-    const bool right = (x & (lcu - 1)) >= lcu - 4 && (f & 1), bottom = (y & (lcu - 1)) >= lcu - 4 && (f & 2);
-    const size_t o = (size_t)y * pitch + x;
-    out[o] = (right || bottom) ? rec[o] : dbk[o];
-}
-
 /* Statistics of every LCU in the encoder's order, the parameter decision of the whole picture (merge wavefront) and the application, behind
- * svt_amd_encdec_picture_deblock: what is left in the picture object (and copied out) is the encoder's finished reconstruction. */
+ * svt_amd_encdec_picture_deblock: what is left in the picture object (and copied out) is the encoder's finished reconstruction.  The chain is
+ * svt_amd_tail_queue_sao (tail_kernels.hip); this entry's part is the flags from the records, the uploads, the source planes and the downloads. */
 template <typename T>
 static int picture_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typename EpTypes<T>::Work *works, const SvtAmdSaoDecisionParams *prm,
                        const uint8_t *enable, SvtAmdSaoLcuParams *lcu_out, void *out_y, void *out_cb, void *out_cr, bool apply)
@@ -761,7 +722,7 @@ static int picture_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typen
         svt_amd_set_error("svt_amd_encdec_picture_sao: svt_amd_encdec_picture_deblock comes first");
         return SVT_AMD_ERR_BAD_PARAM;
     }
-    const uint32_t w = pic->d.width, h = pic->d.height, wl = (w + 63) / 64, hl = (h + 63) / 64, nlcu = (uint32_t)pic->nlcu;
+    const uint32_t w = pic->d.width, h = pic->d.height, wl = (w + 63) / 64, nlcu = (uint32_t)pic->nlcu;
     std::vector<SvtAmdSaoLcuParams> lp(nlcu);
     std::vector<uint8_t> follow(nlcu);
     ::memset(lp.data(), 0, nlcu * sizeof(SvtAmdSaoLcuParams));
@@ -773,59 +734,44 @@ static int picture_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typen
         follow[i] = (uint8_t)(((i % wl) + 1 < wl && !works[i].tile_right ? 1 : 0) | (!bottom_edge ? 2 : 0));
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    for (int k = 0; k < 3 && apply; k++)
-        if (!pic->fin[k] && hipMalloc((void **)&pic->fin[k], pic->plane_bytes[k]) != hipSuccess)
-            return SVT_AMD_ERR_RESOURCES;
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t b_works = up(sizeof(WorkT) * nlcu), b_pl[3] = {up(pic->plane_bytes[0]), up(pic->plane_bytes[1]), up(pic->plane_bytes[2])};
-    const size_t b_stats = up(sizeof(SvtAmdSaoStats) * nlcu), b_par = up(sizeof(SvtAmdSaoLcuParams) * nlcu), b_cost = up(16 * (size_t)nlcu), b_en = up(nlcu);
-    uint8_t *d = nullptr;
-    int rc = svt_amd_ctx_scratch(ctx, b_works + 2 * (b_pl[0] + b_pl[1] + b_pl[2]) + 3 * b_stats + b_par + b_cost + 2 * b_en, &d);
+    int rc = svt_amd_tail_stage_planes(pic, false, apply, 0, 0);
     if (rc)
         return rc;
-    uint8_t *d_works = d, *d_src[3], *d_cmp[3], *q = d + b_works;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t b_works = up(sizeof(WorkT) * nlcu), b_stats = up(sizeof(SvtAmdSaoStats) * nlcu), b_par = up(sizeof(SvtAmdSaoLcuParams) * nlcu), b_cost = up(16 * (size_t)nlcu),
+                 b_en = up(nlcu);
+    size_t total = b_works + 3 * b_stats + b_par + b_cost + 2 * b_en;
     for (int k = 0; k < 3; k++)
-        d_src[k] = q, q += b_pl[k];
+        total += 2 * up(pic->plane_bytes[k]);
+    uint8_t *q = nullptr;
+    if ((rc = svt_amd_ctx_scratch(ctx, total, &q)) != 0)
+        return rc;
+    auto take = [&q](size_t bytes) { uint8_t *r = q; q += bytes; return r; };
+    SvtAmdTailPointers p = {};
+    uint8_t *d_works = take(b_works);
     for (int k = 0; k < 3; k++)
-        d_cmp[k] = q, q += b_pl[k];
-    SvtAmdSaoStats *d_stats[3];
+        p.src[k] = take(up(pic->plane_bytes[k]));
     for (int k = 0; k < 3; k++)
-        d_stats[k] = (SvtAmdSaoStats *)q, q += b_stats;
-    SvtAmdSaoLcuParams *d_par = (SvtAmdSaoLcuParams *)q;
-    q += b_par;
-    int64_t *d_cost = (int64_t *)q;
-    q += b_cost;
-    uint8_t *d_en = q, *d_follow = q + b_en;
+        p.cmp[k] = take(up(pic->plane_bytes[k]));
+    for (int k = 0; k < 3; k++)
+        p.stats[k] = (SvtAmdSaoStats *)take(b_stats);
+    p.stats_bytes = 3 * b_stats;
+    p.par = (SvtAmdSaoLcuParams *)take(b_par), p.cost = (int64_t *)take(b_cost);
+    uint8_t *d_en = take(b_en);
+    p.follow = take(b_en);
     HIP_TRY(hipMemcpyAsync(d_works, works, sizeof(WorkT) * nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
-    HIP_TRY(hipMemcpyAsync(d_follow, follow.data(), nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
-    HIP_TRY(hipMemcpyAsync(d_par, lp.data(), sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(p.follow, follow.data(), nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
+    HIP_TRY(hipMemcpyAsync(p.par, lp.data(), sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
     if (enable)
         HIP_TRY(hipMemcpyAsync(d_en, enable, nlcu, hipMemcpyHostToDevice, svt_amd_ctx_stream(ctx)));
-    HIP_TRY(hipMemsetAsync(d_stats[0], 0, 3 * b_stats, svt_amd_ctx_stream(ctx)));
     HIP_TRY(svt_amd_ctx_sync(ctx)); /* lp backs its copy */
-    const int pY = (int)pic->d.pitch[0], pC = (int)pic->d.pitch[1];
-    hipLaunchKernelGGL(k_ep_source_planes<T>, dim3(nlcu), dim3(256), 0, svt_amd_ctx_stream(ctx), (const WorkT *)d_works, (T *)d_src[0], (T *)d_src[1], (T *)d_src[2], pY, pC,
-                       (int)w, (int)h);
-    for (int k = 0; k < 3 && pic->deblocked; k++) {
-        const int pw = k ? w / 2 : w, ph = k ? h / 2 : h;
-        hipLaunchKernelGGL(k_ep_sao_composite<T>, dim3((pw + 255) / 256, ph), dim3(256), 0, svt_amd_ctx_stream(ctx), (const T *)pic->dbk[k], (const T *)pic->d.rec[k],
-                           (T *)d_cmp[k], k ? pC : pY, pw, ph, k ? 5 : 6, (int)wl, (const uint8_t *)d_follow);
-    }
+    hipLaunchKernelGGL(k_ep_source_planes<T>, dim3(nlcu), dim3(256), 0, svt_amd_ctx_stream(ctx), (const WorkT *)d_works, (T *)p.src[0], (T *)p.src[1], (T *)p.src[2],
+                       (int)pic->d.pitch[0], (int)pic->d.pitch[1], (int)w, (int)h);
     HIP_TRY(hipGetLastError());
-    /* GatherSaoStatisticsLcu* of the components the mode looks at (EbSampleAdaptiveOffsetGenerationDecision.c:647-760) */
-    const int ncomp = prm->mm_sao ? 3 : (prm->temporal_layer < 2 ? 1 : 0);
-    for (int k = 0; k < ncomp; k++)
-        if ((rc = svt_amd_sao_gather_picture(ctx, (int)sizeof(T), d_src[k], k ? pC : pY, pic->deblocked ? (const void *)d_cmp[k] : (const void *)pic->d.rec[k],
-                                             k ? pC : pY, k ? w / 2 : w, k ? h / 2 : h, k ? 32 : 64, prm->mm_sao ? 0 : 1, d_stats[k])) != 0)
-            return rc; /* a picture that is never deblocked (decide-only call) is its own encoder-order view */
-    if ((rc = svt_amd_sao_decide_picture(ctx, prm, d_stats[0], d_stats[1], d_stats[2], wl, hl, enable ? d_en : nullptr, d_par, d_cost)) != 0)
-        return rc;
-    const void *srcs[3] = {pic->dbk[0], pic->dbk[1], pic->dbk[2]};
-    void *dsts[3] = {pic->fin[0], pic->fin[1], pic->fin[2]};
-    if (apply && (rc = svt_amd_sao_apply_picture(ctx, (int)sizeof(T), srcs, dsts, pic->d.pitch[0], pic->d.pitch[1], w, h, d_par, 1, 1)) != 0)
+    if ((rc = svt_amd_tail_queue_sao(ctx, pic, p, prm, enable ? d_en : nullptr, pic->deblocked, apply)) != 0)
         return rc;
     if (lcu_out)
-        HIP_TRY(hipMemcpyAsync(lcu_out, d_par, sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
+        HIP_TRY(hipMemcpyAsync(lcu_out, p.par, sizeof(SvtAmdSaoLcuParams) * nlcu, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
     void *outs[3] = {out_y, out_cb, out_cr};
     for (int k = 0; k < 3 && apply; k++)
         if (outs[k]) {
@@ -834,19 +780,7 @@ static int picture_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const typen
                                      hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
         }
     HIP_TRY(svt_amd_ctx_sync(ctx));
-    pic->sao_done = pic->sao_done || apply;
     return ep_picture_written(ctx, pic);
-}
-
-/* PadRefAndSetFlags (Codec/EbEncDecProcess.c:1805; GeneratePadding / GeneratePadding16Bit): the finished picture inside a frame of
- * replicated edge samples */
-template <typename T>
-__global__ __launch_bounds__(256) void k_ep_pad(const T *__restrict__ src, int spitch, int w, int h, T *__restrict__ dst, int dstride, int ox, int oy)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= w + 2 * ox)
-        return;
-    dst[(size_t)y * dstride + x] = src[(size_t)min(max(y - oy, 0), h - 1) * spitch + min(max(x - ox, 0), w - 1)];
 }
 
 /* The picture object's latest stage (after SAO, else deblocked, else as encoded) as a padded reference picture in HBM: what
@@ -856,37 +790,19 @@ __global__ __launch_bounds__(256) void k_ep_pad(const T *__restrict__ src, int s
 extern "C" int svt_amd_encdec_picture_reference(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, uint32_t origin_x, uint32_t origin_y, SvtAmdRefPicture *ref,
                                                 void *out_y, void *out_cb, void *out_cr)
 {
-    if (!ctx || !pic || !ref || origin_x < 8 || origin_y < 8 || (origin_x & 1) || (origin_y & 1) || origin_x > 256 || origin_y > 256)
+    if (!ctx || !pic || !ref || !svt_amd_tail_origin_ok(origin_x, origin_y))
         return SVT_AMD_ERR_BAD_PARAM;
     HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t w = pic->d.width, h = pic->d.height, bps = pic->d.bps;
-    uint8_t *const *stage = pic->sao_done ? pic->fin : pic->deblocked ? pic->dbk : pic->d.rec;
+    int rc = svt_amd_tail_stage_planes(pic, false, false, origin_x, origin_y);
+    if (rc || (rc = svt_amd_tail_queue_reference(ctx, pic, origin_x, origin_y, ref)) != 0)
+        return rc;
     void *outs[3] = {out_y, out_cb, out_cr};
-    for (int k = 0; k < 3; k++) {
-        const int sh = k ? 1 : 0, pw = (int)(w >> sh), ph = (int)(h >> sh), ox = (int)(origin_x >> sh), oy = (int)(origin_y >> sh), stride = pw + 2 * ox, rows = ph + 2 * oy;
-        const size_t need = (size_t)stride * rows * bps;
-        if (pic->refp_bytes[k] < need) {
-            if (pic->refp[k])
-                HIP_TRY(hipFree(pic->refp[k]));
-            pic->refp[k] = nullptr, pic->refp_bytes[k] = 0;
-            if (hipMalloc((void **)&pic->refp[k], need) != hipSuccess)
-                return SVT_AMD_ERR_RESOURCES;
-            pic->refp_bytes[k] = need;
+    for (int k = 0; k < 3; k++)
+        if (outs[k]) {
+            const size_t rows = k ? (ref->height >> 1) + 2 * (origin_y >> 1) : ref->height + 2 * origin_y;
+            HIP_TRY(hipMemcpyAsync(outs[k], pic->refp[k], (k ? ref->strideC : ref->strideY) * rows * pic->d.bps, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
         }
-        if (bps == 1)
-            hipLaunchKernelGGL(k_ep_pad<uint8_t>, dim3((stride + 255) / 256, rows), dim3(256), 0, svt_amd_ctx_stream(ctx), (const uint8_t *)stage[k], (int)pic->d.pitch[k], pw, ph,
-                               (uint8_t *)pic->refp[k], stride, ox, oy);
-        else
-            hipLaunchKernelGGL(k_ep_pad<uint16_t>, dim3((stride + 255) / 256, rows), dim3(256), 0, svt_amd_ctx_stream(ctx), (const uint16_t *)stage[k], (int)pic->d.pitch[k], pw,
-                               ph, (uint16_t *)pic->refp[k], stride, ox, oy);
-        if (outs[k])
-            HIP_TRY(hipMemcpyAsync(outs[k], pic->refp[k], need, hipMemcpyDeviceToHost, svt_amd_ctx_stream(ctx)));
-    }
-    HIP_TRY(hipGetLastError());
     HIP_TRY(svt_amd_ctx_sync(ctx)); /* other lanes' pictures may read the planes right away */
-    ref->d_y = pic->refp[0], ref->d_cb = pic->refp[1], ref->d_cr = pic->refp[2];
-    ref->strideY = w + 2 * origin_x, ref->strideC = (w >> 1) + 2 * (origin_x >> 1), ref->originX = origin_x, ref->originY = origin_y;
-    ref->width = w, ref->height = h;
     return SVT_AMD_OK;
 }
 extern "C" int svt_amd_encdec_picture_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdLcuWork *works, const SvtAmdSaoDecisionParams *params,

@@ -1,8 +1,10 @@
 /*
  * tail_kernels.hip - the picture tail on the device: deblocking, SAO and reference padding of an encoded picture from the contract records where they lie in HBM
- * (include/svt_hevc_amd.h "Picture tail on the device").  The blocking entries svt_amd_encdec_picture_deblock / _sao / _sao_decide / _reference
- * (encdec_kernels.hip) keep their code; this file is the stream-ordered twin: nothing is uploaded, nothing is awaited, every byte it works on is per picture object.
- * What the reference does, as the blocking entries cite it: the per-LCU deblocking drivers LCUInternalAreaDLFCore / LCUBoundaryDLFCore / LCUPictureEdgeDLFCore
+ * (include/svt_hevc_amd.h "Picture tail on the device").  Two things live here.  The stream-ordered launch: nothing is uploaded, nothing is awaited, every
+ * byte it works on is per picture object.  And the device chain itself (svt_amd_tail_queue_deblock / _sao / _reference, encdec_device.h), which the launch and the blocking
+ * entries svt_amd_encdec_picture_deblock / _sao / _sao_decide / _reference (encdec_kernels.hip) both queue: those entries keep their checks, their host loops over the
+ * records, their uploads and downloads and their waits, and nothing else.
+ * What the reference does: the per-LCU deblocking drivers LCUInternalAreaDLFCore / LCUBoundaryDLFCore / LCUPictureEdgeDLFCore
  * (Codec/EbDeblockingFilter.c:2222, 2828, 3518, called from Codec/EbCodingLoop.c:4600-4631) on the boundary strengths of SetBSArrayBasedOnPUBoundary / TUBoundary
  * (:339, :472); SaoGenerationDecision[16bit] inside EncodePass (Codec/EbCodingLoop.c:4640-4750, Codec/EbSampleAdaptiveOffsetGenerationDecision.c:647-850, :936-1140) on
  * the picture as it stands when the LCU is done; ApplySaoOffsetsPicture (Codec/EbEncDecProcess.c:522-757); PadRefAndSetFlags (Codec/EbEncDecProcess.c:1805).
@@ -10,8 +12,8 @@
  *                     (gathered per cell, the later unit wins) and stored as whole rows; the flag bytes, the LCU's zeroed SvtAmdSaoLcuParams with its edge_flags and
  *                     its status byte; the LCU's source samples scattered into the three source planes, 16 bytes a lane where base and pitch allow.
  *   k_tail_check      grid (1): the status bytes reduced to one SvtAmdTailCheck.
- *   k_tail_composite  one launch for the three planes: the encoder-order view the SAO statistics are gathered on (k_ep_sao_composite's rule), 16 bytes a lane.
- *   k_tail_pad        one launch for the three planes: edge replication (k_ep_pad's rule), the padded plane as one run of 16-byte stores.
+ *   k_tail_composite  one launch for the three planes: the encoder-order view the SAO statistics are gathered on, 16 bytes a lane.
+ *   k_tail_pad        one launch for the three planes: edge replication, the padded plane as one run of 16-byte stores.
  * No atomics, nothing zeroed beforehand.  Bound: HBM traffic - the source scatter reads and writes 1.5 samples a pixel, the composite reads 2 x and writes 1 x, the
  * padding reads and writes 1 x the padded picture.
  */
@@ -154,8 +156,11 @@ struct TailPlanes3 {
     const uint8_t *follow;
 };
 
-/* The picture as SaoGenerationDecision sees each LCU (k_ep_sao_composite, encdec_kernels.hip): the deblocked picture, except the last 4 columns / rows of an LCU where an
- * LCU of the same tile follows (follow: bit 0 right, bit 1 below) - those still hold the samples as encoded.  grid (chunks of a luma row / 256, 2 * height): row y of the
+/* The picture as the reference's SaoGenerationDecision sees each LCU (Codec/EbCodingLoop.c:4600-4750): the LCU's own deblocking drivers have run, those of the LCUs to its
+ * right and below have not.  Those later drivers own the 8x8 filter blocks centred on the LCU boundary (LCUBoundaryDLFCore, Codec/EbDeblockingFilter.c:2828), i.e. every edge
+ * segment inside the last 4 columns / rows of the LCU (in the plane's own samples) and nothing else inside it: the LCU is the deblocked picture with those strips still as
+ * encoded, where a neighbour OF THE SAME TILE follows (at picture and tile edges the LCU's own LCUPictureEdgeDLFCore has finished them; follow: bit 0 right, bit 1 below).
+ * (tests/test_oracle_encodepass_golden.py::test_encoder_order_sao_statistics_from_two_pictures proves it on the encoder's own records.)  grid (chunks of a luma row / 256, 2 * height): row y of the
  * grid is luma row y, then the Cb rows, then the Cr rows; a lane makes N samples (N a divisor of 32: a chunk lies in one LCU). */
 template <typename T, int N>
 __global__ __launch_bounds__(256) void k_tail_composite(TailPlanes3 P)
@@ -185,7 +190,7 @@ __global__ __launch_bounds__(256) void k_tail_composite(TailPlanes3 P)
     }
 }
 
-/* PadRefAndSetFlags (Codec/EbEncDecProcess.c:1805; GeneratePadding[16Bit]): the stage inside a frame of replicated edge samples (k_ep_pad's rule).  grid (chunks of the
+/* PadRefAndSetFlags (Codec/EbEncDecProcess.c:1805; GeneratePadding / GeneratePadding16Bit): the finished picture inside a frame of replicated edge samples.  grid (chunks of the
  * padded luma plane / 256, 3): the padded plane is one run of samples, a lane makes N of them and stores them at once (the plane's start is 16-byte aligned). */
 template <typename T, int N>
 __global__ __launch_bounds__(256) void k_tail_pad(TailPlanes3 P)
@@ -224,13 +229,8 @@ __global__ __launch_bounds__(256) void k_tail_pad(TailPlanes3 P)
 /* the tail's working memory of one picture object: one allocation, carved up; freed with the object */
 struct SvtAmdTailState {
     uint8_t *block;
-    uint32_t *map;
-    uint8_t *cbf, *qp, *edge, *sao_edge, *follow, *status, *bsv, *bsh;
-    uint8_t *src[3], *cmp[3];
-    SvtAmdSaoStats *stats[3];
-    size_t stats_bytes;            /* of the three together */
-    SvtAmdSaoLcuParams *par;
-    int64_t *cost;
+    SvtAmdTailPointers p;          /* what the chain works on */
+    uint8_t *sao_edge, *status;    /* [LCUs] each: k_tail_maps' other two bytes */
     TailCheckSums *check;
     bool maps_valid;               /* a tail has run on the object: svt_amd_debug_picture_tail_maps has something to fetch */
 };
@@ -246,46 +246,15 @@ void svt_amd_tail_state_free(SvtAmdEncDecPicture *pic)
     pic->tail = nullptr;
 }
 
-static int tail_state(SvtAmdEncDecPicture *pic, bool with_fin, uint32_t origin_x, uint32_t origin_y)
+int svt_amd_tail_stage_planes(SvtAmdEncDecPicture *pic, bool dbk, bool fin, uint32_t origin_x, uint32_t origin_y)
 {
     const uint32_t w = pic->d.width, h = pic->d.height, bps = pic->d.bps;
-    if (!pic->tail) {
-        SvtAmdTailState *s = (SvtAmdTailState *)calloc(1, sizeof(*s));
-        if (!s)
-            return SVT_AMD_ERR_RESOURCES;
-        auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-        const size_t n = (size_t)pic->nlcu, cells8 = (size_t)(w / 8) * (h / 8), cells4 = (size_t)(w / 4) * (h / 4);
-        const size_t b_map = up(cells8 * sizeof(SvtAmdCuMapEntry)), b_cbf = up(cells4), b_qp = up(cells8), b_lcu = up(n), b_bs = n * 256, b_stats = up(sizeof(SvtAmdSaoStats) * n),
-                     b_par = up(sizeof(SvtAmdSaoLcuParams) * n), b_cost = up(16 * n);
-        size_t total = b_map + b_cbf + b_qp + 4 * b_lcu + 2 * b_bs + 3 * b_stats + b_par + b_cost + 256;
-        for (int k = 0; k < 3; k++)
-            total += 2 * up(pic->plane_bytes[k]);
-        if (hipMalloc((void **)&s->block, total) != hipSuccess) {
-            free(s);
-            svt_amd_set_error("hipMalloc (picture tail state, %zu bytes) failed", total);
-            return SVT_AMD_ERR_RESOURCES;
-        }
-        uint8_t *q = s->block;
-        auto take = [&q](size_t bytes) { uint8_t *r = q; q += bytes; return r; };
-        s->map = (uint32_t *)take(b_map), s->cbf = take(b_cbf), s->qp = take(b_qp);
-        s->edge = take(b_lcu), s->sao_edge = take(b_lcu), s->follow = take(b_lcu), s->status = take(b_lcu);
-        s->bsv = take(b_bs), s->bsh = take(b_bs);
-        for (int k = 0; k < 3; k++)
-            s->src[k] = take(up(pic->plane_bytes[k]));
-        for (int k = 0; k < 3; k++)
-            s->cmp[k] = take(up(pic->plane_bytes[k]));
-        for (int k = 0; k < 3; k++)
-            s->stats[k] = (SvtAmdSaoStats *)take(b_stats);
-        s->stats_bytes = 3 * b_stats;
-        s->par = (SvtAmdSaoLcuParams *)take(b_par), s->cost = (int64_t *)take(b_cost), s->check = (TailCheckSums *)take(256);
-        pic->tail = s;
-    }
     for (int k = 0; k < 3; k++) {
-        if (!pic->dbk[k] && hipMalloc((void **)&pic->dbk[k], pic->plane_bytes[k]) != hipSuccess) {
+        if (dbk && !pic->dbk[k] && hipMalloc((void **)&pic->dbk[k], pic->plane_bytes[k]) != hipSuccess) {
             svt_amd_set_error("hipMalloc (deblocked picture) failed");
             return SVT_AMD_ERR_RESOURCES;
         }
-        if (with_fin && !pic->fin[k] && hipMalloc((void **)&pic->fin[k], pic->plane_bytes[k]) != hipSuccess) {
+        if (fin && !pic->fin[k] && hipMalloc((void **)&pic->fin[k], pic->plane_bytes[k]) != hipSuccess) {
             svt_amd_set_error("hipMalloc (finished picture) failed");
             return SVT_AMD_ERR_RESOURCES;
         }
@@ -304,14 +273,51 @@ static int tail_state(SvtAmdEncDecPicture *pic, bool with_fin, uint32_t origin_x
             pic->refp_bytes[k] = need;
         }
     }
+    return SVT_AMD_OK;
+}
+
+static int tail_state(SvtAmdEncDecPicture *pic, bool with_fin, uint32_t origin_x, uint32_t origin_y)
+{
+    const uint32_t w = pic->d.width, h = pic->d.height;
+    if (!pic->tail) {
+        SvtAmdTailState *s = (SvtAmdTailState *)calloc(1, sizeof(*s));
+        if (!s)
+            return SVT_AMD_ERR_RESOURCES;
+        auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+        const size_t n = (size_t)pic->nlcu, cells8 = (size_t)(w / 8) * (h / 8), cells4 = (size_t)(w / 4) * (h / 4);
+        const size_t b_map = up(cells8 * sizeof(SvtAmdCuMapEntry)), b_cbf = up(cells4), b_qp = up(cells8), b_lcu = up(n), b_bs = n * 256, b_stats = up(sizeof(SvtAmdSaoStats) * n),
+                     b_par = up(sizeof(SvtAmdSaoLcuParams) * n), b_cost = up(16 * n);
+        size_t total = b_map + b_cbf + b_qp + 4 * b_lcu + 2 * b_bs + 3 * b_stats + b_par + b_cost + 256;
+        for (int k = 0; k < 3; k++)
+            total += 2 * up(pic->plane_bytes[k]);
+        if (hipMalloc((void **)&s->block, total) != hipSuccess) {
+            free(s);
+            svt_amd_set_error("hipMalloc (picture tail state, %zu bytes) failed", total);
+            return SVT_AMD_ERR_RESOURCES;
+        }
+        uint8_t *q = s->block;
+        auto take = [&q](size_t bytes) { uint8_t *r = q; q += bytes; return r; };
+        SvtAmdTailPointers &p = s->p;
+        p.map = (uint32_t *)take(b_map), p.cbf = take(b_cbf), p.qp = take(b_qp);
+        p.edge = take(b_lcu), s->sao_edge = take(b_lcu), p.follow = take(b_lcu), s->status = take(b_lcu);
+        p.bsv = take(b_bs), p.bsh = take(b_bs);
+        for (int k = 0; k < 3; k++)
+            p.src[k] = take(up(pic->plane_bytes[k]));
+        for (int k = 0; k < 3; k++)
+            p.cmp[k] = take(up(pic->plane_bytes[k]));
+        for (int k = 0; k < 3; k++)
+            p.stats[k] = (SvtAmdSaoStats *)take(b_stats);
+        p.stats_bytes = 3 * b_stats;
+        p.par = (SvtAmdSaoLcuParams *)take(b_par), p.cost = (int64_t *)take(b_cost), s->check = (TailCheckSums *)take(256);
+        pic->tail = s;
+    }
+    SVT_AMD_TRY(svt_amd_tail_stage_planes(pic, true, with_fin, origin_x, origin_y));
     if (!pic->ev_written && hipEventCreateWithFlags(&pic->ev_written, hipEventDisableTiming) != hipSuccess) {
         pic->ev_written = nullptr;
         return SVT_AMD_ERR_RESOURCES;
     }
     return SVT_AMD_OK;
 }
-
-static bool tail_origin_ok(uint32_t ox, uint32_t oy) { return ox >= 8 && oy >= 8 && !(ox & 1) && !(oy & 1) && ox <= 256 && oy <= 256; }
 
 extern "C" size_t svt_amd_picture_tail_bytes(uint16_t luma_width, uint16_t luma_height, int which)
 {
@@ -325,7 +331,7 @@ extern "C" int svt_amd_encdec_picture_tail_warmup(SvtAmdContext *ctx, SvtAmdEncD
 {
     if (!ctx || !pic)
         SVT_AMD_BAD("%s: a context and a picture object", __func__);
-    if ((origin_x || origin_y) && !tail_origin_ok(origin_x, origin_y))
+    if ((origin_x || origin_y) && !svt_amd_tail_origin_ok(origin_x, origin_y))
         SVT_AMD_BAD("%s: padding %u x %u (even, 8 to 256, or 0 x 0 for no reference planes)", __func__, origin_x, origin_y);
     HIP_TRY(hipSetDevice(ctx->device));
     return tail_state(pic, true, origin_x, origin_y);
@@ -343,12 +349,12 @@ extern "C" int svt_amd_encdec_picture_tail_launch(SvtAmdContext *ctx, SvtAmdEncD
         SVT_AMD_BAD("%s: stages 0x%x (SVT_AMD_TAIL_DEBLOCK 1, _SAO_DECIDE 2, _SAO_APPLY 4, _REFERENCE 8; pad %u is 0)", __func__, stages, job->pad);
     if (apply && !(decide && deblock))
         SVT_AMD_BAD("%s: SVT_AMD_TAIL_SAO_APPLY needs SVT_AMD_TAIL_SAO_DECIDE and SVT_AMD_TAIL_DEBLOCK in the same job (stages 0x%x)", __func__, stages);
-    if (pad && (!ref || !tail_origin_ok(job->origin_x, job->origin_y)))
+    if (pad && (!ref || !svt_amd_tail_origin_ok(job->origin_x, job->origin_y)))
         SVT_AMD_BAD("%s: SVT_AMD_TAIL_REFERENCE needs `ref` and a padding of 8 to 256, even (%u x %u)", __func__, job->origin_x, job->origin_y);
     const bool maps = deblock || decide;
     const void *d_works = job->d_works, *d_results = job->d_results;
     size_t work_stride = job->work_stride, result_stride = job->result_stride;
-    const uint32_t w = pic->d.width, h = pic->d.height, bps = pic->d.bps, wl = (w + 63) / 64, hl = (h + 63) / 64, nlcu = (uint32_t)pic->nlcu;
+    const uint32_t w = pic->d.width, h = pic->d.height, bps = pic->d.bps, wl = (w + 63) / 64, nlcu = (uint32_t)pic->nlcu;
     if (maps) {
         if (!d_works != !d_results)
             SVT_AMD_BAD("%s: work and result records come together (both device arrays, or both NULL for the records the object's last mode-decision call left)", __func__);
@@ -383,10 +389,10 @@ extern "C" int svt_amd_encdec_picture_tail_launch(SvtAmdContext *ctx, SvtAmdEncD
         TailMapsArgs A;
         A.works = (const uint8_t *)d_works, A.results = (const uint8_t *)d_results, A.work_stride = work_stride, A.result_stride = result_stride;
         A.width = (int)w, A.height = (int)h, A.lcu_cols = (int)wl, A.lcus = (int)nlcu;
-        A.map = s->map, A.cbf = s->cbf, A.qp = s->qp, A.edge = s->edge, A.sao_edge = s->sao_edge, A.follow = s->follow, A.status = s->status;
-        A.lcu_params = (uint32_t *)s->par;
+        A.map = s->p.map, A.cbf = s->p.cbf, A.qp = s->p.qp, A.edge = s->p.edge, A.sao_edge = s->sao_edge, A.follow = s->p.follow, A.status = s->status;
+        A.lcu_params = (uint32_t *)s->p.par;
         for (int k = 0; k < 3; k++)
-            A.src[k] = s->src[k];
+            A.src[k] = s->p.src[k];
         A.pitchY = pY, A.pitchC = pC;
         A.vec = !((uintptr_t)d_works % 16) && !(work_stride % 16) && !((size_t)pY * bps % 16) && !((size_t)pC * bps % 16);
         if (bps == 1)
@@ -397,64 +403,89 @@ extern "C" int svt_amd_encdec_picture_tail_launch(SvtAmdContext *ctx, SvtAmdEncD
         HIP_TRY(hipGetLastError());
         s->maps_valid = true;
     }
-    if (deblock) {
-        SVT_AMD_TRY(svt_amd_bs_picture(ctx, (const SvtAmdCuMapEntry *)s->map, s->cbf, w, h, job->deblock.slice_type, job->deblock.ref_poc[0], job->deblock.ref_poc[1], s->edge,
-                                       s->bsv, s->bsh));
-        /* the deblocked picture is a second set of planes: the picture as encoded stays (the composite below, and the next pictures' neighbours) */
-        for (int k = 0; k < 3; k++)
-            HIP_TRY(hipMemcpyAsync(pic->dbk[k], pic->d.rec[k], pic->plane_bytes[k], hipMemcpyDeviceToDevice, st));
-        SVT_AMD_TRY(svt_amd_dlf_picture(ctx, (int)bps, pic->dbk[0], pic->d.pitch[0], pic->dbk[1], pic->dbk[2], pic->d.pitch[1], w, h, s->bsv, s->bsh, s->qp, w / 8,
-                                        job->deblock.tc_offset, job->deblock.beta_offset, job->deblock.cb_qp_offset, job->deblock.cr_qp_offset));
-        pic->deblocked = true;
-    }
-    if (decide) {
-        HIP_TRY(hipMemsetAsync(s->stats[0], 0, s->stats_bytes, st));
-        TailPlanes3 P;
-        memset(&P, 0, sizeof(P));
-        if (deblock) {
-            for (int k = 0; k < 3; k++)
-                P.a[k] = pic->dbk[k], P.b[k] = pic->d.rec[k], P.out[k] = s->cmp[k];
-            P.pitchY = pY, P.pitchC = pC, P.width = (int)w, P.height = (int)h, P.lcu_cols = (int)wl, P.follow = s->follow;
-            if (bps == 1)
-                hipLaunchKernelGGL((k_tail_composite<uint8_t, 16>), dim3(((w + 15) / 16 + 255) / 256, 2 * h), dim3(256), 0, st, P);
-            else
-                hipLaunchKernelGGL((k_tail_composite<uint16_t, 8>), dim3(((w + 7) / 8 + 255) / 256, 2 * h), dim3(256), 0, st, P);
-            HIP_TRY(hipGetLastError());
-        }
-        /* GatherSaoStatisticsLcu* of the components the mode looks at (EbSampleAdaptiveOffsetGenerationDecision.c:647-760); a picture that is not deblocked in this job
-         * (allowEncDecMismatch) is its own encoder-order view */
-        const int ncomp = job->sao.mm_sao ? 3 : (job->sao.temporal_layer < 2 ? 1 : 0);
-        for (int k = 0; k < ncomp; k++)
-            SVT_AMD_TRY(svt_amd_sao_gather_picture(ctx, (int)bps, s->src[k], k ? pC : pY, deblock ? (const void *)s->cmp[k] : (const void *)pic->d.rec[k], k ? pC : pY,
-                                                   k ? w / 2 : w, k ? h / 2 : h, k ? 32 : 64, job->sao.mm_sao ? 0 : 1, s->stats[k]));
-        SVT_AMD_TRY(svt_amd_sao_decide_picture(ctx, &job->sao, s->stats[0], s->stats[1], s->stats[2], wl, hl, job->d_sao_enable, s->par, s->cost));
-        if (apply) {
-            const void *srcs[3] = {pic->dbk[0], pic->dbk[1], pic->dbk[2]};
-            void *dsts[3] = {pic->fin[0], pic->fin[1], pic->fin[2]};
-            SVT_AMD_TRY(svt_amd_sao_apply_picture(ctx, (int)bps, srcs, dsts, pic->d.pitch[0], pic->d.pitch[1], w, h, s->par, 1, 1));
-            pic->sao_done = true;
-        }
+    if (deblock)
+        SVT_AMD_TRY(svt_amd_tail_queue_deblock(ctx, pic, s->p, &job->deblock));
+    if (decide) { /* the composite is of this job's deblocking: without it the picture as encoded is looked at (allowEncDecMismatch) */
+        SVT_AMD_TRY(svt_amd_tail_queue_sao(ctx, pic, s->p, &job->sao, job->d_sao_enable, deblock, apply));
         if (d_lcu_params)
-            HIP_TRY(hipMemcpyAsync(d_lcu_params, s->par, sizeof(SvtAmdSaoLcuParams) * (size_t)nlcu, hipMemcpyDeviceToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d_lcu_params, s->p.par, sizeof(SvtAmdSaoLcuParams) * (size_t)nlcu, hipMemcpyDeviceToDevice, st));
     }
-    if (pad) {
-        uint8_t *const *stage = pic->sao_done ? pic->fin : pic->deblocked ? pic->dbk : pic->d.rec;
+    if (pad)
+        SVT_AMD_TRY(svt_amd_tail_queue_reference(ctx, pic, job->origin_x, job->origin_y, ref));
+    return ep_picture_written(ctx, pic);
+}
+
+/* ---- the device chain: what the launch above and the blocking entries (encdec_kernels.hip) queue; everything they work on is in `p` and the object's stages.  (Below the
+ * launch, so that the compiler meets the kernels in the order k_tail_maps, k_tail_check, k_tail_composite, k_tail_pad and the code object keeps its layout.) ---- */
+
+int svt_amd_tail_queue_deblock(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdTailPointers &p, const SvtAmdDeblockParams *prm)
+{
+    const uint32_t w = pic->d.width, h = pic->d.height;
+    SVT_AMD_TRY(svt_amd_bs_picture(ctx, (const SvtAmdCuMapEntry *)p.map, p.cbf, w, h, prm->slice_type, prm->ref_poc[0], prm->ref_poc[1], p.edge, p.bsv, p.bsh));
+    /* the deblocked picture is a second set of planes: the picture as encoded stays (the neighbours of LCUs still to come, and the part of the SAO statistics that the
+     * reference gathers before an LCU's right / bottom edges are filtered: k_tail_composite) */
+    for (int k = 0; k < 3; k++)
+        HIP_TRY(hipMemcpyAsync(pic->dbk[k], pic->d.rec[k], pic->plane_bytes[k], hipMemcpyDeviceToDevice, svt_amd_ctx_stream(ctx)));
+    SVT_AMD_TRY(svt_amd_dlf_picture(ctx, (int)pic->d.bps, pic->dbk[0], pic->d.pitch[0], pic->dbk[1], pic->dbk[2], pic->d.pitch[1], w, h, p.bsv, p.bsh, p.qp, w / 8, prm->tc_offset,
+                                    prm->beta_offset, prm->cb_qp_offset, prm->cr_qp_offset));
+    pic->deblocked = true;
+    return SVT_AMD_OK;
+}
+
+int svt_amd_tail_queue_sao(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdTailPointers &p, const SvtAmdSaoDecisionParams *prm, const uint8_t *d_enable, bool composite,
+                           bool apply)
+{
+    const uint32_t w = pic->d.width, h = pic->d.height, bps = pic->d.bps, wl = (w + 63) / 64, hl = (h + 63) / 64;
+    const int pY = (int)pic->d.pitch[0], pC = (int)pic->d.pitch[1];
+    hipStream_t st = svt_amd_ctx_stream(ctx);
+    HIP_TRY(hipMemsetAsync(p.stats[0], 0, p.stats_bytes, st));
+    if (composite) {
         TailPlanes3 P;
         memset(&P, 0, sizeof(P));
         for (int k = 0; k < 3; k++)
-            P.a[k] = stage[k], P.out[k] = pic->refp[k];
-        P.pitchY = pY, P.pitchC = pC, P.width = (int)w, P.height = (int)h, P.ox = (int)job->origin_x, P.oy = (int)job->origin_y;
-        const uint32_t total = (w + 2 * job->origin_x) * (h + 2 * job->origin_y), n = 16 / bps, chunks = (total + n - 1) / n;
+            P.a[k] = pic->dbk[k], P.b[k] = pic->d.rec[k], P.out[k] = p.cmp[k];
+        P.pitchY = pY, P.pitchC = pC, P.width = (int)w, P.height = (int)h, P.lcu_cols = (int)wl, P.follow = p.follow;
         if (bps == 1)
-            hipLaunchKernelGGL((k_tail_pad<uint8_t, 16>), dim3((chunks + 255) / 256, 3), dim3(256), 0, st, P);
+            hipLaunchKernelGGL((k_tail_composite<uint8_t, 16>), dim3(((w + 15) / 16 + 255) / 256, 2 * h), dim3(256), 0, st, P);
         else
-            hipLaunchKernelGGL((k_tail_pad<uint16_t, 8>), dim3((chunks + 255) / 256, 3), dim3(256), 0, st, P);
+            hipLaunchKernelGGL((k_tail_composite<uint16_t, 8>), dim3(((w + 7) / 8 + 255) / 256, 2 * h), dim3(256), 0, st, P);
         HIP_TRY(hipGetLastError());
-        ref->d_y = pic->refp[0], ref->d_cb = pic->refp[1], ref->d_cr = pic->refp[2];
-        ref->strideY = w + 2 * job->origin_x, ref->strideC = (w >> 1) + 2 * (job->origin_x >> 1), ref->originX = job->origin_x, ref->originY = job->origin_y;
-        ref->width = w, ref->height = h;
     }
-    return ep_picture_written(ctx, pic);
+    /* GatherSaoStatisticsLcu* of the components the mode looks at (EbSampleAdaptiveOffsetGenerationDecision.c:647-760); a picture without a composite (never deblocked:
+     * allowEncDecMismatch, a decide-only call) is its own encoder-order view */
+    const int ncomp = prm->mm_sao ? 3 : (prm->temporal_layer < 2 ? 1 : 0);
+    for (int k = 0; k < ncomp; k++)
+        SVT_AMD_TRY(svt_amd_sao_gather_picture(ctx, (int)bps, p.src[k], k ? pC : pY, composite ? (const void *)p.cmp[k] : (const void *)pic->d.rec[k], k ? pC : pY, k ? w / 2 : w,
+                                               k ? h / 2 : h, k ? 32 : 64, prm->mm_sao ? 0 : 1, p.stats[k]));
+    SVT_AMD_TRY(svt_amd_sao_decide_picture(ctx, prm, p.stats[0], p.stats[1], p.stats[2], wl, hl, d_enable, p.par, p.cost));
+    if (apply) {
+        const void *srcs[3] = {pic->dbk[0], pic->dbk[1], pic->dbk[2]};
+        void *dsts[3] = {pic->fin[0], pic->fin[1], pic->fin[2]};
+        SVT_AMD_TRY(svt_amd_sao_apply_picture(ctx, (int)bps, srcs, dsts, pic->d.pitch[0], pic->d.pitch[1], w, h, p.par, 1, 1));
+        pic->sao_done = true;
+    }
+    return SVT_AMD_OK;
+}
+
+int svt_amd_tail_queue_reference(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, uint32_t origin_x, uint32_t origin_y, SvtAmdRefPicture *ref)
+{
+    const uint32_t w = pic->d.width, h = pic->d.height, bps = pic->d.bps;
+    uint8_t *const *stage = pic->sao_done ? pic->fin : pic->deblocked ? pic->dbk : pic->d.rec;
+    TailPlanes3 P;
+    memset(&P, 0, sizeof(P));
+    for (int k = 0; k < 3; k++)
+        P.a[k] = stage[k], P.out[k] = pic->refp[k];
+    P.pitchY = (int)pic->d.pitch[0], P.pitchC = (int)pic->d.pitch[1], P.width = (int)w, P.height = (int)h, P.ox = (int)origin_x, P.oy = (int)origin_y;
+    const uint32_t total = (w + 2 * origin_x) * (h + 2 * origin_y), n = 16 / bps, chunks = (total + n - 1) / n;
+    if (bps == 1)
+        hipLaunchKernelGGL((k_tail_pad<uint8_t, 16>), dim3((chunks + 255) / 256, 3), dim3(256), 0, svt_amd_ctx_stream(ctx), P);
+    else
+        hipLaunchKernelGGL((k_tail_pad<uint16_t, 8>), dim3((chunks + 255) / 256, 3), dim3(256), 0, svt_amd_ctx_stream(ctx), P);
+    HIP_TRY(hipGetLastError());
+    ref->d_y = pic->refp[0], ref->d_cb = pic->refp[1], ref->d_cr = pic->refp[2];
+    ref->strideY = w + 2 * origin_x, ref->strideC = (w >> 1) + 2 * (origin_x >> 1), ref->originX = origin_x, ref->originY = origin_y;
+    ref->width = w, ref->height = h;
+    return SVT_AMD_OK;
 }
 
 /* debug / test: what the object's last tail derived from the records; every pointer HOST and optional.  lcu_bytes: [4][LCUs] - the deblocking edge byte, the SAO edge
@@ -471,12 +502,12 @@ extern "C" int svt_amd_debug_picture_tail_maps(SvtAmdContext *ctx, SvtAmdEncDecP
     const SvtAmdTailState *s = pic->tail;
     const size_t w = pic->d.width, h = pic->d.height, n = (size_t)pic->nlcu, bps = pic->d.bps;
     if (map)
-        HIP_TRY(hipMemcpy(map, s->map, (w / 8) * (h / 8) * sizeof(SvtAmdCuMapEntry), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(map, s->p.map, (w / 8) * (h / 8) * sizeof(SvtAmdCuMapEntry), hipMemcpyDeviceToHost));
     if (cbf)
-        HIP_TRY(hipMemcpy(cbf, s->cbf, (w / 4) * (h / 4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(cbf, s->p.cbf, (w / 4) * (h / 4), hipMemcpyDeviceToHost));
     if (qp)
-        HIP_TRY(hipMemcpy(qp, s->qp, (w / 8) * (h / 8), hipMemcpyDeviceToHost));
-    const uint8_t *bytes[4] = {s->edge, s->sao_edge, s->follow, s->status};
+        HIP_TRY(hipMemcpy(qp, s->p.qp, (w / 8) * (h / 8), hipMemcpyDeviceToHost));
+    const uint8_t *bytes[4] = {s->p.edge, s->sao_edge, s->p.follow, s->status};
     for (int k = 0; k < 4 && lcu_bytes; k++)
         HIP_TRY(hipMemcpy(lcu_bytes + k * n, bytes[k], n, hipMemcpyDeviceToHost));
     if (check)
@@ -485,7 +516,7 @@ extern "C" int svt_amd_debug_picture_tail_maps(SvtAmdContext *ctx, SvtAmdEncDecP
     for (int k = 0; k < 3; k++)
         if (outs[k]) {
             const size_t pw = k ? w / 2 : w, ph = k ? h / 2 : h;
-            HIP_TRY(hipMemcpy2D(outs[k], pw * bps, s->src[k], (size_t)pic->d.pitch[k] * bps, pw * bps, ph, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy2D(outs[k], pw * bps, s->p.src[k], (size_t)pic->d.pitch[k] * bps, pw * bps, ph, hipMemcpyDeviceToHost));
         }
     return SVT_AMD_OK;
 }

@@ -53,7 +53,7 @@ typedef struct TailTile {
     uint8_t status;         /* TAIL_LCU_BAD, or the number of offending units */
     uint8_t edge;           /* deblocking: tile_left | tile_top << 1 */
     uint8_t sao_edge;       /* SvtAmdSaoLcuParams.edge_flags: 1 left, 2 right, 4 top, 8 bottom */
-    uint8_t follow;         /* k_ep_sao_composite: bit 0 an LCU of the same tile follows to the right, bit 1 below */
+    uint8_t follow;         /* k_tail_composite: bit 0 an LCU of the same tile follows to the right, bit 1 below */
 } TailTile;
 
 typedef struct TailCheckSums { uint32_t bad_lcus, first_bad_lcu, bad_units, first_bad_unit_lcu; } TailCheckSums; /* = SvtAmdTailCheck */

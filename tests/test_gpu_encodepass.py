@@ -499,6 +499,132 @@ def encoded_picture(lib, ctx, pic, w, h, sdt):
     return [np.ascontiguousarray(a[(8 >> s_):(8 >> s_) + (h >> s_), (8 >> s_):(8 >> s_) + (w >> s_)]) for a, s_ in zip(padded, (0, 1, 1))]
 
 
+def written_picture(lib, ctx, oracle, w, h, wide, seed=5):
+    """a picture object that holds an encoded picture (all-intra, seeded) -> (object, work records, result records as the device returned them)"""
+    sig_picture(lib)
+    works8, _ = random_picture(oracle, w, h, 30, seed)
+    pic = C.c_void_p()
+    assert lib.svt_amd_encdec_picture_create(ctx, w, h, 2 if wide else 1, C.byref(pic)) == 0, lib.svt_amd_last_error()
+    if wide:
+        works = np.zeros(len(works8), S.LCU_WORK16_DTYPE)
+        for f in works8.dtype.names:
+            works[f] = works8[f].astype(np.uint16) * 4 if f.startswith("src_") else works8[f]
+        res = np.zeros(len(works), S.LCU_RESULT16_DTYPE)
+        assert lib.svt_amd_encode_picture16(ctx, pic, works.ctypes.data, res.ctypes.data) == 0, lib.svt_amd_last_error()
+    else:
+        works, res = works8, np.zeros(len(works8), S.LCU_RESULT_DTYPE)
+        assert lib.svt_amd_encode_picture(ctx, pic, works.ctypes.data, res.ctypes.data) == 0, lib.svt_amd_last_error()
+    return pic, works, res
+
+
+def picture_of_results(res, w, h):
+    """the three planes of the picture as encoded, assembled from the LCUs' reconstruction in the result records"""
+    wl = (w + 63) // 64
+    planes = [np.zeros((h >> s_, w >> s_), res["rec_y"].dtype) for s_ in (0, 1, 1)]
+    for k, r in enumerate(res):
+        x, y = 64 * (k % wl), 64 * (k // wl)
+        lw, lh = min(64, w - x), min(64, h - y)
+        planes[0][y:y + lh, x:x + lw] = r["rec_y"].reshape(64, 64)[:lh, :lw]
+        for p, nm in ((1, "rec_cb"), (2, "rec_cr")):
+            planes[p][y // 2:(y + lh) // 2, x // 2:(x + lw) // 2] = r[nm].reshape(32, 32)[:lh // 2, :lw // 2]
+    return planes
+
+
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("w,h,ox,oy", [(64, 64, 8, 8),        # one LCU
+                                       (200, 136, 10, 8),     # partial LCUs both ways; rows of 220 / 110 samples: no whole number of 16-byte chunks, chunks cross row ends
+                                       (136, 72, 80, 80)])    # the frame is wider than the picture
+def test_padded_reference_is_the_edge_replicated_picture(product, oracle, gpu_ctx, w, h, ox, oy, wide):
+    """svt_amd_encdec_picture_reference against a restatement that shares nothing with the padding kernel: every padded plane is numpy.pad(interior, mode="edge"), the
+    interior is the reconstruction the result records hold, `ref` holds the documented strides and origins - and svt_amd_encdec_picture_tail_launch with
+    SVT_AMD_TAIL_REFERENCE alone, on the same object and into planes overwritten in between, gives the same bytes and the same `ref`"""
+    import tail_numpy as N
+    import taillib as T
+    from pa_batch_util import SENTINEL
+    lib = T.declare(product)
+    lib.svt_amd_encdec_picture_reference.restype = C.c_int
+    lib.svt_amd_encdec_picture_reference.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    sdt = np.uint16 if wide else np.uint8
+    pic, works, res = written_picture(lib, gpu_ctx, oracle, w, h, wide)
+    try:
+        want = [np.pad(a, ((oy >> s_, oy >> s_), (ox >> s_, ox >> s_)), mode="edge") for a, s_ in zip(picture_of_results(res, w, h), (0, 1, 1))]
+        assert [a.shape for a in want] == [((h + 2 * oy) >> s_, (w + 2 * ox) >> s_) for s_ in (0, 1, 1)]
+        fields = lambda r: (r.strideY, r.strideC, r.originX, r.originY, r.width, r.height)
+        ref = S.RefPicture()
+        got = [np.zeros(a.shape, sdt) for a in want]
+        assert lib.svt_amd_encdec_picture_reference(gpu_ctx, pic, ox, oy, C.byref(ref), *[a.ctypes.data for a in got]) == 0, lib.svt_amd_last_error()
+        assert fields(ref) == (w + 2 * ox, w // 2 + 2 * (ox // 2), ox, oy, w, h) and ref.d_y and ref.d_cb and ref.d_cr
+        for p in range(3):
+            bad = np.argwhere(got[p] != want[p])
+            assert len(bad) == 0, ("blocking", p, len(bad), bad[:4].tolist())
+        # the launch writes the same planes: overwrite them first, so that what is read back is what the launch wrote
+        planes = (ref.d_y, ref.d_cb, ref.d_cr)
+        for p in range(3):
+            poison = np.full(want[p].nbytes, SENTINEL, np.uint8)
+            assert lib.svt_amd_device_upload(gpu_ctx, C.c_void_p(planes[p]), poison.ctypes.data, poison.nbytes) == 0, lib.svt_amd_last_error()
+        ref2 = S.RefPicture()
+        job = T.job(None, 0, None, 0, N.REFERENCE, origin=(ox, oy))
+        assert lib.svt_amd_encdec_picture_tail_launch(gpu_ctx, pic, C.byref(job), None, None, C.byref(ref2)) == 0, lib.svt_amd_last_error()
+        assert fields(ref2) == fields(ref) and (ref2.d_y, ref2.d_cb, ref2.d_cr) == planes
+        for p in range(3):
+            again = np.zeros(want[p].shape, sdt)
+            assert lib.svt_amd_device_download(gpu_ctx, again.ctypes.data, C.c_void_p(planes[p]), again.nbytes) == 0, lib.svt_amd_last_error()
+            bad = np.argwhere(again != want[p])
+            assert len(bad) == 0, ("launch", p, len(bad), bad[:4].tolist())
+    finally:
+        lib.svt_amd_encdec_picture_destroy(gpu_ctx, pic)
+
+
+@pytest.mark.parametrize("wide", [False, True])
+@pytest.mark.parametrize("entry", ["blocking", "launch"])
+def test_deblocking_offsets_reach_the_filter(product, oracle, gpu_ctx, entry, wide):
+    """the recorded pictures all have tc_offset = beta_offset = 0: a seeded all-intra picture deblocked with tc_offset -6 and beta_offset 6 through
+    svt_amd_encdec_picture_deblock[16], or through svt_amd_encdec_picture_tail_launch on records in HBM, equals the CPU chain (boundary strengths and picture
+    deblocking of the checker, tests/test_oracle_dlf_golden.py) - and that chain with the two offsets confused gives another picture"""
+    import tail_numpy as N
+    import taillib as T
+    from pa_batch_util import DeviceBuffer
+    from test_oracle_dlf_golden import oracle_bs, oracle_dlf
+    from test_oracle_encodepass_golden import deblock_maps
+    lib = T.declare(product)
+    w, h, tc, beta = 200, 136, -6, 6
+    sdt = np.uint16 if wide else np.uint8
+    dbk = lib.svt_amd_encdec_picture_deblock16 if wide else lib.svt_amd_encdec_picture_deblock
+    dbk.restype, dbk.argtypes = C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DeblockParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    pic, works, res = written_picture(lib, gpu_ctx, oracle, w, h, wide)
+    dw, dr = DeviceBuffer(lib, gpu_ctx, works.nbytes), DeviceBuffer(lib, gpu_ctx, res.nbytes)
+    try:
+        cumap, cbf, qp, edge = deblock_maps(works, res, w, h)
+
+        def chain(tc_offset, beta_offset):
+            hdr = dict(width=w, height=h, bytes_per_sample=2 if wide else 1, qp_stride=w // 8, tc_offset=tc_offset, beta_offset=beta_offset, cb_qp_offset=0, cr_qp_offset=0,
+                       slice_type=int(works[0]["slice_type"]))
+            p = dict(hdr=hdr, cumap=cumap.reshape(-1), cbf=cbf.reshape(-1), refpoc=np.zeros(2, np.uint64), lcu_edge=edge, bsv=np.zeros((len(works), 256), np.uint8),
+                     bsh=np.zeros((len(works), 256), np.uint8))
+            p["bsv"], p["bsh"] = oracle_bs(oracle, p)
+            p["pre"], p["qp"] = picture_of_results(res, w, h), qp.reshape(-1)
+            return oracle_dlf(oracle, p)
+        want = chain(tc, beta)
+        assert int((want[0] != chain(tc, tc)[0]).sum()) > 100 and int((want[0] != chain(beta, beta)[0]).sum()) > 100
+        if entry == "blocking":
+            prm = DeblockParams()
+            prm.tc_offset, prm.beta_offset, prm.slice_type = tc, beta, int(works[0]["slice_type"])
+            out = [np.zeros(a.shape, sdt) for a in want]
+            assert dbk(gpu_ctx, pic, works.ctypes.data, res.ctypes.data, C.byref(prm), *[a.ctypes.data for a in out]) == 0, lib.svt_amd_last_error()
+        else:
+            dw.put(works), dr.put(res)
+            job = T.job(dw.ptr.value, works.dtype.itemsize, dr.ptr.value, res.dtype.itemsize, N.DEBLOCK, int(works[0]["slice_type"]))
+            job.deblock.tc_offset, job.deblock.beta_offset = tc, beta
+            assert lib.svt_amd_encdec_picture_tail_launch(gpu_ctx, pic, C.byref(job), None, None, None) == 0, lib.svt_amd_last_error()
+            out = encoded_picture(lib, gpu_ctx, pic, w, h, sdt)
+        for p in range(3):
+            bad = np.argwhere(out[p] != want[p])
+            assert len(bad) == 0, (p, len(bad), bad[:4].tolist())
+    finally:
+        dw.free(), dr.free()
+        lib.svt_amd_encdec_picture_destroy(gpu_ctx, pic)
+
+
 @pytest.mark.parametrize("name", SAO_CASES)
 def test_encode_deblock_sao_on_the_device_matches_the_encoders_output(product, gpu_ctx, name):
     """three calls per picture - svt_amd_encode_picture, svt_amd_encdec_picture_deblock, svt_amd_encdec_picture_sao - and what is in HBM

@@ -13,7 +13,7 @@ import svtlib as S
 import tail_numpy as N
 import taillib as T
 from pa_batch_util import SENTINEL, DeviceBuffer, is_sentinel, make_context, ok, refused
-from test_gpu_encodepass import DeblockParams, device_refs, encoded_picture, random_picture, set_inter, sig_picture
+from test_gpu_encodepass import DeblockParams, device_refs, encoded_picture, set_inter, sig_picture, written_picture
 from test_gpu_tmvp import random_heads
 from test_oracle_encodepass_golden import DLF_CASES, INTER_CASES, SAO_CASES, allows_mismatch, compare_lcu, is16, load_case, sao_inputs_of_picture
 from test_oracle_saodec_golden import LCU, params_of, same_decision
@@ -203,22 +203,6 @@ def seeded_records(w, h, slice_type, seed, wide):
     return works, results
 
 
-def written_picture(lib, ctx, oracle, w, h, wide, seed=5):
-    """a picture object that holds an encoded picture (all-intra, seeded): what a tail needs before it takes any records"""
-    works8, _ = random_picture(oracle, w, h, 30, seed)
-    pic = new_picture(lib, ctx, w, h, wide)
-    if wide:
-        works = np.zeros(len(works8), S.LCU_WORK16_DTYPE)
-        for f in works8.dtype.names:
-            works[f] = works8[f].astype(np.uint16) * 4 if f.startswith("src_") else works8[f]
-        res = np.zeros(len(works), S.LCU_RESULT16_DTYPE)
-        ok(lib, lib.svt_amd_encode_picture16(ctx, pic, works.ctypes.data, res.ctypes.data))
-    else:
-        works, res = works8, np.zeros(len(works8), S.LCU_RESULT_DTYPE)
-        ok(lib, lib.svt_amd_encode_picture(ctx, pic, works.ctypes.data, res.ctypes.data))
-    return pic, works, res
-
-
 @pytest.mark.parametrize("wide", [False, True])
 @pytest.mark.parametrize("w,h,slice_type,seed", [(64, 64, 2, 3), (136, 72, 0, 5), (200, 136, 0, 7), (200, 136, 1, 11)])
 def test_maps_and_source_planes_of_seeded_records(lib, ctx, oracle, w, h, slice_type, seed, wide):
@@ -383,7 +367,13 @@ def blocking_tail(lib, ctx, pic, wide, works, got, prm, P, enable, origin, w, h)
 @pytest.mark.parametrize("name", ["sao_b_tiles_motion_512x320_m6", "sao_i_noise_200x136_m6"])
 def test_tail_equals_the_blocking_calls_with_sao_shut_off_in_places(lib, ctx, name):
     """6. a seeded enable mask with a third of the bytes zero: planes, parameters and padded reference byte for byte; a repeated tail gives the same bytes; two objects
-    on two lanes, both queued before either is synchronised; the sentinels behind the outputs stay"""
+    on two lanes, both queued before either is synchronised; the sentinels behind the outputs stay.
+    The tail and the blocking calls queue the same device chain (svt_amd_tail_queue_deblock / _sao / _reference), so their equality proves that the two derivations of
+    its inputs agree - the blocking entries' host loops against k_tail_maps, context scratch against the object's tail state - and not the chain itself.  The independent
+    proof of the chain is the reference encoder's recorded pictures, parameters and padded references: tests 3 to 5 here, and
+    test_encode_picture_then_deblock_matches_the_encoders_output, test_encode_deblock_sao_on_the_device_matches_the_encoders_output and
+    test_sequence_stays_on_the_device_from_picture_to_picture of tests/test_gpu_encodepass.py; the padding also against numpy.pad
+    (test_padded_reference_is_the_edge_replicated_picture there)."""
     g, w, h = load_case(name)
     wide, nl = is16(g), S.lcu_count(w, h)
     refs, keep = device_refs(g, wide) if "ref_pocs" in g else ({}, None)
