@@ -192,12 +192,16 @@ def random_picture(oracle, w, h, qp, seed, tile_cols=1, tile_rows=1, constrained
     return works, want
 
 
-def random_inter_picture(oracle, w, h, qp, seed, pad=80, intra_lcus=1.0, tile_cols=1):    # pad > 75: a window at a clamped position stays inside the plane
+def random_inter_picture(oracle, w, h, qp, seed, pad=80, intra_lcus=1.0, tile_cols=1, matched=False, wide=False):    # pad > 75: a window at a clamped position stays inside the plane
     """a seeded B picture: random unit trees with ~80 % inter units (L0 / L1 / bi, AMVP / merge / skip, whole-LCU 64x64 units, motion vectors
     that reach far outside the picture now and then), two reference pictures, rate tables and per-LCU lambdas spread over three decades -
-    and what the CPU oracle makes of it in raster order.  Returns works, want, (reference planes, geometry), cost."""
+    and what the CPU oracle makes of it in raster order.  Returns works, want, (reference planes, geometry), cost.
+    matched: the two reference pictures are the tap-matched worst-case planes of tests/inter_extremes.py ((2,2) luma, (4,4) chroma, + for list 0 and - for
+    list 1, phase (0,0) at the picture origin) instead of the sinusoids, and every third inter unit's vectors are half-sample ones on that phase.
+    wide (with matched): 10-bit samples, the 16-bit records and the 16-bit oracle."""
     from test_oracle_encodepass_golden import inter_oracle_fn
-    fn = inter_oracle_fn(oracle, False)
+    assert matched or not wide
+    fn = inter_oracle_fn(oracle, wide)
     rng = np.random.default_rng(seed)
     works, _ = random_picture(oracle, w, h, qp, seed, tile_cols)           # trees, intra modes, QPs, source, tile edges
     yy, xx = np.mgrid[0:h + 2 * pad, 0:w + 2 * pad]
@@ -207,6 +211,11 @@ def random_inter_picture(oracle, w, h, qp, seed, pad=80, intra_lcus=1.0, tile_co
         c = [np.clip(128 + 30 * np.sin((xx[::2, ::2] - pad) / (31.0 + 9 * k)) + rng.normal(0, 3, (yy.shape[0] // 2, yy.shape[1] // 2)), 0, 255).astype(np.uint8)
              for k in range(2)]
         refs.append([np.ascontiguousarray(a) for a in (y, c[0], c[1])])
+    if matched:
+        import inter_extremes as X
+        bps = 2 if wide else 1
+        refs = [[X.matched_plane(bps, 0, 2, 2, r == 1, h + 2 * pad, w + 2 * pad, pad, pad)] +
+                [X.matched_plane(bps, 1, 4, 4, r == 1, (h + 2 * pad) // 2, (w + 2 * pad) // 2, pad // 2, pad // 2) for _ in range(2)] for r in range(2)]
     geom = (w + 2 * pad, (w + 2 * pad) // 2, pad, pad, w, h)
     cost = np.zeros(1, np.dtype([("last", "<u4", 176), ("sig", "u1", 84), ("g1", "u1", 48), ("g2", "u1", 12), ("sigml", "u1", 8), ("g1x", "<u2", 96),
                                  ("sigv", "u1", (32, 16))]))
@@ -232,13 +241,25 @@ def random_inter_picture(oracle, w, h, qp, seed, pad=80, intra_lcus=1.0, tile_co
                 cu["inter_dir"], cu["inter_kind"] = rng.choice([0, 1, 2], p=[0.35, 0.25, 0.4]), rng.choice([0, 1, 2], p=[0.4, 0.4, 0.2])
                 far = rng.random() < 0.06
                 cu["mv"] = rng.integers(-4 * max(w, h), 4 * max(w, h), (2, 2)) if far else rng.integers(-70, 71, (2, 2))
+    if matched:
+        rng2, m = np.random.default_rng([seed, 1]), 0
+        for wk in works:
+            for i in range(int(wk["num_cus"])):
+                if int(wk["cu"][i]["pred_mode"]) == 1:
+                    if m % 3 == 0:        # units sit on multiples of 8 samples: an integer part of 8 k samples keeps them on the planes' phase
+                        wk["cu"][i]["mv"] = 32 * rng2.integers(-2, 3, (2, 2)) + 2
+                    m += 1
+        if wide:
+            works8, works = works, np.zeros(len(works), S.LCU_WORK16_DTYPE)
+            for f in works8.dtype.names:
+                works[f] = ((works8[f].astype(np.uint16) << 2) | rng2.integers(0, 4, works8[f].shape, dtype=np.uint16)) if f.startswith("src_") else works8[f]
     rs = [S.RefPicture(r[0].ctypes.data, r[1].ctypes.data, r[2].ctypes.data, *geom) for r in refs]
     pitches = (w + 32, w // 2 + 16, w // 2 + 16)
     pb = (C.c_uint32 * 3)(*pitches)
-    rec = [np.full((hh, p), 0xA5, np.uint8) for hh, p in zip((h, h // 2, h // 2), pitches)]
+    rec = [np.full((hh, p), 0xA5A5 if wide else 0xA5, np.uint16 if wide else np.uint8) for hh, p in zip((h, h // 2, h // 2), pitches)]
     mp = np.full(((h + 3) // 4, (w + 3) // 4 + 3), 0xFF, np.uint8)
     rp = (C.c_void_p * 3)(*[r.ctypes.data for r in rec])
-    want = np.zeros(len(works), S.LCU_RESULT_DTYPE)
+    want = np.zeros(len(works), S.LCU_RESULT16_DTYPE if wide else S.LCU_RESULT_DTYPE)
     for k in range(len(works)):
         fn(rp, pb, mp.ctypes.data, mp.shape[1], w, h, C.byref(rs[0]), C.byref(rs[1]), cost.ctypes.data, works[k:k + 1].ctypes.data, want[k:k + 1].ctypes.data)
     return works, want, (refs, geom), cost
@@ -248,7 +269,7 @@ def set_inter_random(lib, ctx, pic, refs_geom, cost):
     """the reference pictures of random_inter_picture into HBM + svt_amd_encdec_picture_set_inter; returns what must stay alive"""
     import torch
     refs, geom = refs_geom
-    keep = [[torch.from_numpy(a).cuda() for a in r] for r in refs]
+    keep = [[torch.from_numpy(a.view(np.int16) if a.dtype == np.uint16 else a).cuda() for a in r] for r in refs]
     torch.cuda.synchronize()
     rs = [S.RefPicture(k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(), *geom) for k in keep]
     lib.svt_amd_encdec_picture_set_inter.restype = C.c_int

@@ -91,8 +91,9 @@ def test_md_encode_picture_matches_the_reference_and_the_oracle(product, oracle,
         lib.svt_amd_context_destroy(ctx)
 
 
-def md_encode_inter(lib, ctx, pic, g, k, encode=False):
-    """svt_amd_md_encode_picture_inter on picture k of a P / B fixture: reference pictures into HBM, rate tables, inter inputs"""
+def md_encode_inter(lib, ctx, pic, g, k, encode=False, planes=None):
+    """svt_amd_md_encode_picture_inter on picture k of a P / B fixture: reference pictures into HBM, rate tables, inter inputs
+    (planes: substituted reference pictures, see test_oracle_md_golden.inter_inputs)"""
     import torch
     from test_oracle_md_golden import inter_inputs
     vp = C.c_void_p
@@ -107,7 +108,7 @@ def md_encode_inter(lib, ctx, pic, g, k, encode=False):
     cost = np.ascontiguousarray(g["cost"][k])
     src = [np.ascontiguousarray(g[n][k]) for n in ("src_y", "src_cb", "src_cr")]
     o = np.ascontiguousarray(g["ois"][k])
-    X, me, tmvp, refs, planes = inter_inputs(g, k)
+    X, me, tmvp, refs, planes = inter_inputs(g, k, planes)
     assert lib.svt_amd_md_picture_supported_inter(P.ctypes.data, X.ctypes.data) == 1
     dev = [[torch.from_numpy(a).cuda() for a in pl] for pl in planes]
     torch.cuda.synchronize()

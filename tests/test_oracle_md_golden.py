@@ -14,7 +14,8 @@ import svtlib as S
 CASES = sorted(os.path.basename(p)[3:-4] for p in glob.glob(os.path.join(S.GOLDEN_DIR, "md_*.npz")))
 
 
-def oracle_md_picture(lib, g, k):
+def oracle_md_picture(lib, g, k, planes=None):
+    """planes: see inter_inputs"""
     pic = np.ascontiguousarray(g["pic"][k:k + 1])
     lcus = np.ascontiguousarray(g["lcu"][k])
     cost = np.ascontiguousarray(g["cost"][k])
@@ -23,7 +24,7 @@ def oracle_md_picture(lib, g, k):
     out = np.zeros(len(lcus), S.MD_LCU_OUT_DTYPE)
     rec = np.zeros_like(src)
     if "inter" in g.files:
-        X, me, tmvp, refs, keep = inter_inputs(g, k)
+        X, me, tmvp, refs, keep = inter_inputs(g, k, planes)
         cb, cr = np.ascontiguousarray(g["src_cb"][k]), np.ascontiguousarray(g["src_cr"][k])
         kinds = np.zeros((len(lcus), 85), np.uint8)
         lib.svt_oracle_md_picture_inter.restype = C.c_int
@@ -43,9 +44,10 @@ def oracle_md_picture(lib, g, k):
     return out, rec
 
 
-def inter_inputs(g, k):
+def inter_inputs(g, k, planes=None):
     """the inter inputs of picture k of a P / B fixture: SvtAmdMdInter, the ME records in the contract's layout, the co-located motion field and
-    the two reference pictures (host planes) as SvtAmdRefPicture"""
+    the two reference pictures (host planes) as SvtAmdRefPicture.  planes: [[y, cb, cr], [y, cb, cr]] in place of the recorded reference pictures
+    (same shapes and geometry; tests/test_gpu_inter_extremes.py substitutes worst-case samples)"""
     X = np.ascontiguousarray(g["inter"][k:k + 1])
     nl = g["lcu"].shape[1]
     me = np.zeros(nl, S.ME_LCU_DTYPE)
@@ -54,9 +56,12 @@ def inter_inputs(g, k):
     sy, sc, ox, oy, rw, rh, _ = (int(v) for v in g["ref_geom"][k])
     keep, refs = [], []
     for l in range(2):
-        planes = [np.ascontiguousarray(g["ref%d_%s" % (l, nm)][k]) for nm in ("y", "cb", "cr")]
-        keep.append(planes)
-        refs.append(S.RefPicture(planes[0].ctypes.data, planes[1].ctypes.data, planes[2].ctypes.data, sy, sc, ox, oy, rw, rh))
+        pl = [np.ascontiguousarray(g["ref%d_%s" % (l, nm)][k]) for nm in ("y", "cb", "cr")]
+        if planes is not None:
+            assert all(a.shape == b.shape and a.dtype == b.dtype for a, b in zip(planes[l], pl))
+            pl = [np.ascontiguousarray(a) for a in planes[l]]
+        keep.append(pl)
+        refs.append(S.RefPicture(pl[0].ctypes.data, pl[1].ctypes.data, pl[2].ctypes.data, sy, sc, ox, oy, rw, rh))
     return X, me, tmvp, refs, keep
 
 
