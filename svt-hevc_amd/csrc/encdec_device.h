@@ -7,6 +7,7 @@
 #include "intra_device.h"
 #include "rate_device.h"
 #include "pmcore_device.h"
+#include "inter_position.h"
 
 struct EpRefPlanes {               /* one reference picture (SvtAmdRefPicture): device pointers to the START of the padded planes */
     const void *plane[3];
@@ -203,19 +204,6 @@ struct EpMcScratch {
  * plane around the LCU displaced by a centre vector (the mode decision: the 64x64 unit's motion-estimation vector).  A candidate whose window lies inside takes it from
  * here (an LDS copy, ~0.3 K clocks) instead of from HBM (a round trip of ~5 K clocks on the unit chain, two for a bi-predicted candidate); any other candidate reads
  * global memory as before.  Filled by ep_ref_windows_fill with the core's own clamped addressing, so the samples are the ones the core would have loaded. */
-#ifdef EP_DEBUG_WINDOW_COUNTS
-static __device__ unsigned g_ep_dbg_counts[8]; /* development aid: lookups with a valid window / an invalid one / none, and hits; [4..7]: clocks / 16 of set-up, window, horizontal, vertical */
-#define EP_DBG_CLK(k)                                                                              \
-    do {                                                                                           \
-        if (lane == 0 && !chroma) {                                                                \
-            const unsigned long long c_ = __builtin_readcyclecounter();                            \
-            atomicAdd(&g_ep_dbg_counts[k], (unsigned)((c_ - dbg_t_) >> 4));                         \
-            dbg_t_ = c_;                                                                           \
-        }                                                                                          \
-    } while (0)
-#else
-#define EP_DBG_CLK(k)
-#endif
 struct EpRefWindows {
     static constexpr int R = 8, W = 64 + 2 * R + 7, P = 88, H = W;
     int x0[2], y0[2]; /* padded-plane coordinates of the window's first sample, per list */
@@ -249,7 +237,7 @@ static __constant__ int8_t c_ep_chroma_taps[8][4] = {{0, 64, 0, 0}, {-2, 58, 10,
  * (x, y) of the unit's plane-p block goes */
 template <typename T, typename Store>
 __device__ __forceinline__ void ep_inter_predict_core(const EpPicture &P, int abs_x, int abs_y, int N, int inter_dir, const int16_t (*mv)[2], int p, int lane,
-                                                      EpMcScratch<T> &M, Store store, int tile_first = 0, int tile_step = 1, const EpRefWindows *RW = nullptr)
+                                                      EpMcScratch<T> &M, Store store)
 {
     constexpr int WP = EpMcScratch<T>::WP, TP = EpMcScratch<T>::TP;
     constexpr int s1 = sizeof(T) == 1 ? 0 : 2, maxv = sizeof(T) == 1 ? 255 : 1023;
@@ -258,12 +246,9 @@ __device__ __forceinline__ void ep_inter_predict_core(const EpPicture &P, int ab
     const int n = chroma ? N >> 1 : N, tn = n > 32 ? 32 : n, lgt = 31 - __clz(tn);
     const int ntaps = chroma ? 4 : 8, first = chroma ? -1 : -3, rows = tn + ntaps - 1;
     const bool bi = inter_dir == 2;
-#ifdef EP_DEBUG_WINDOW_COUNTS
-    unsigned long long dbg_t_ = __builtin_readcyclecounter();
-#endif
-    /* the block goes in 32x32 tiles (one for blocks up to 32x32); tile_first / tile_step let several waves share the tiles of a 64x64 block */
+    /* the block goes in 32x32 tiles (one for blocks up to 32x32) */
     const int ntile = n > 32 ? 4 : 1;
-    for (int ti = tile_first; ti < ntile; ti += tile_step) {
+    for (int ti = 0; ti < ntile; ti++) {
         {
             const int ty0 = (ti >> 1) << 5, tx0 = (ti & 1) << 5;
             bool second = false;
@@ -271,10 +256,9 @@ __device__ __forceinline__ void ep_inter_predict_core(const EpPicture &P, int ab
                 if (!(bi || inter_dir == l))
                     continue;
                 const EpRefPlanes &R = P.ref[l];
-                const int qx = min(max(((abs_x + R.originX) << 2) + mv[l][0], (R.originX - 71) << 2), (R.width + R.originX + 7) << 2);
-                const int qy = min(max(((abs_y + R.originY) << 2) + mv[l][1], (R.originY - 71) << 2), (R.height + R.originY + 7) << 2);
-                const int ix = (chroma ? qx >> 3 : qx >> 2) + tx0, iy = (chroma ? qy >> 3 : qy >> 2) + ty0;
-                const int fx = __builtin_amdgcn_readfirstlane(chroma ? qx & 7 : qx & 3), fy = __builtin_amdgcn_readfirstlane(chroma ? qy & 7 : qy & 3);
+                const int qx = INTER_POS_CLAMP(abs_x, R.originX, mv[l][0], R.width), qy = INTER_POS_CLAMP(abs_y, R.originY, mv[l][1], R.height);
+                const int ix = inter_pos_int(qx, chroma) + tx0, iy = inter_pos_int(qy, chroma) + ty0;
+                const int fx = __builtin_amdgcn_readfirstlane(inter_pos_frac(qx, chroma)), fy = __builtin_amdgcn_readfirstlane(inter_pos_frac(qy, chroma));
                 const int stride = (int)R.stride[chroma], last = R.size[chroma] - 1;
                 const T *plane = (const T *)R.plane[p];
                 int tx[8], tv[8];
@@ -285,36 +269,7 @@ __device__ __forceinline__ void ep_inter_predict_core(const EpPicture &P, int ab
                 }
                 /* window: 8-byte chunks of the rows, a lane per chunk, every load issued before the first store (one memory latency per window, not one per row).
                  * The chunks are not aligned (global memory takes that); one that leaves the plane is read sample by sample from clamped addresses. */
-                EP_DBG_CLK(4);
-                bool staged = false;
-#ifdef EP_DEBUG_WINDOW_COUNTS
-                if (lane == 0 && !chroma)
-                    atomicAdd(&g_ep_dbg_counts[RW ? (RW->valid[l] ? 0 : 1) : 2], 1u);
-#endif
-                if constexpr (sizeof(T) == 1) {
-                    /* the LCU's staged reference samples (EpRefWindows), when the tile's window lies inside: chunks of 8 bytes at any byte offset - three aligned words
-                     * and two v_alignbyte each */
-                    if (RW && !chroma && RW->valid[l]) {
-                        const int cpr = (rows + 7) >> 3, rx = ix + first - RW->x0[l], ry = iy + first - RW->y0[l];
-                        if (rx >= 0 && ry >= 0 && rx + cpr * 8 <= EpRefWindows::P && ry + rows <= EpRefWindows::H) {
-                            staged = true;
-#ifdef EP_DEBUG_WINDOW_COUNTS
-                            if (lane == 0)
-                                atomicAdd(&g_ep_dbg_counts[3], 1u);
-#endif
-                            const int nchunk = rows * cpr, inv = (65536 + cpr - 1) / cpr;
-                            for (int i = lane; i < nchunk; i += 64) {
-                                const int j = (i * inv) >> 16, m = i - j * cpr, o = (ry + j) * EpRefWindows::P + rx + m * 8, sh = o & 3;
-                                const uint32_t *wp = reinterpret_cast<const uint32_t *>(&RW->pix[l][o & ~3]);
-                                const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
-                                uint2 v;
-                                v.x = __builtin_amdgcn_alignbyte(w1, w0, sh), v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
-                                *reinterpret_cast<uint2 *>(&M.win[j * WP + m * 8]) = v;
-                            }
-                        }
-                    }
-                }
-                if (!staged) {
+                {
                     constexpr int SPC = 8 / (int)sizeof(T); /* samples per chunk */
                     const int cpr = (rows + SPC - 1) / SPC, nchunk = rows * cpr, inv = (65536 + cpr - 1) / cpr;
                     const int base0 = (iy + first) * stride + ix + first;
@@ -347,7 +302,6 @@ __device__ __forceinline__ void ep_inter_predict_core(const EpPicture &P, int ab
                     }
                 }
                 EP_WAVE_SYNC();
-                EP_DBG_CLK(5);
                 /* horizontal pass of every window row: a lane slides the taps over a run of seg outputs (seg + taps - 1 samples, read as whole words) */
                 const int seg = tn < 8 ? tn : 8, lgs = tn < 8 ? lgt : 3, spr = tn >> lgs; /* runs per row */
                 for (int i = lane; i < rows * spr; i += 64) {
@@ -374,7 +328,6 @@ __device__ __forceinline__ void ep_inter_predict_core(const EpPicture &P, int ab
                         }
                 }
                 EP_WAVE_SYNC();
-                EP_DBG_CLK(6);
                 /* vertical pass: a lane owns a column and a run of rpl rows (rpl + taps - 1 reads: one stretch of the transposed rows) */
                 const int rpl = tn >= 8 ? (tn * tn) >> 6 : 1, run = rpl < 1 ? 1 : rpl; /* 32: 16, 16: 4, 8: 1, 4: 1 */
                 {
@@ -424,7 +377,6 @@ __device__ __forceinline__ void ep_inter_predict_core(const EpPicture &P, int ab
                     }
                 }
                 EP_WAVE_SYNC();
-                EP_DBG_CLK(7);
                 second = true;
             }
         }
@@ -470,13 +422,12 @@ __device__ __forceinline__ int ep_sdot2(uint32_t a, uint32_t b, int c)
     return __builtin_amdgcn_sdot2(x, y, c, false);
 }
 /* both passes of one tile of TN x TN samples of one list: window in M.win -> dst / M.raw.  mode: 0 uni-prediction, 1 first list of a bi-predicted tile, 2 its second list */
-/* DIRECT: the window is read where it lies - dwin + doff, rows dpitch bytes apart (dwin 4-byte aligned, dpitch a multiple of 4: the byte misalignment is the same for every
- * row and segment, one v_alignbyte per word) - instead of from an 8-byte-aligned copy in M.win: a staged reference window (EpRefWindows) needs no copy pass */
-template <int TN, bool CHROMA, bool DIRECT = false>
-__device__ __forceinline__ void ep_mc8_tile(EpMcScratch<uint8_t> &M, int lane, int fx, int fy, int mode, uint8_t *dst, int pitch, const uint8_t *dwin = nullptr, int doff = 0,
-                                            int dpitch = 0)
+/* The window is read where it lies - dwin + doff, rows dpitch bytes apart (dwin 4-byte aligned, dpitch a multiple of 4: the byte misalignment is the same for every
+ * row and segment, one v_alignbyte per word): a staged reference window (EpRefWindows) needs no copy pass, and a window loaded from the plane lies in M.win */
+template <int TN, bool CHROMA>
+__device__ __forceinline__ void ep_mc8_tile(EpMcScratch<uint8_t> &M, int lane, int fx, int fy, int mode, uint8_t *dst, int pitch, const uint8_t *dwin, int doff, int dpitch)
 {
-    constexpr int WP = EpMcScratch<uint8_t>::WP, TP = EpMcScratch<uint8_t>::TP;
+    constexpr int TP = EpMcScratch<uint8_t>::TP;
     constexpr int NT = CHROMA ? 4 : 8, ROWS = TN + NT - 1, SEG = TN < 8 ? TN : 8, SPR = TN / SEG, ITEMS = ROWS * SPR;
     constexpr int LGT = TN == 32 ? 5 : TN == 16 ? 4 : TN == 8 ? 3 : 2;
     uint32_t hx[2], vx[4], hy[2], vy[4];
@@ -489,22 +440,15 @@ __device__ __forceinline__ void ep_mc8_tile(EpMcScratch<uint8_t> &M, int lane, i
         if (i < ITEMS) {
             const int j = SPR == 1 ? i : i / SPR, x0 = SPR == 1 ? 0 : (i - j * SPR) * SEG;
             uint32_t w[4];
-            if (DIRECT) {
-                const int sh = __builtin_amdgcn_readfirstlane(doff & 3);
-                const uint32_t *wp = reinterpret_cast<const uint32_t *>(dwin + (doff & ~3) + j * dpitch + x0);
-                uint32_t r[5];
+            const int sh = __builtin_amdgcn_readfirstlane(doff & 3);
+            const uint32_t *wp = reinterpret_cast<const uint32_t *>(dwin + (doff & ~3) + j * dpitch + x0);
+            uint32_t r[5];
 #pragma unroll
-                for (int k = 0; k < 5; k++)
-                    r[k] = (k - 1) * 4 < SEG + NT - 1 ? wp[k] : 0u;
+            for (int k = 0; k < 5; k++)
+                r[k] = (k - 1) * 4 < SEG + NT - 1 ? wp[k] : 0u;
 #pragma unroll
-                for (int k = 0; k < 4; k++)
-                    w[k] = (k * 4 < SEG + NT - 1 ? __builtin_amdgcn_alignbyte(r[k + 1], r[k], sh) : 0u) ^ 0x80808080u;
-            } else {
-                const uint32_t *wp = reinterpret_cast<const uint32_t *>(&M.win[j * WP + x0]);
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    w[k] = (k * 4 < SEG + NT - 1 ? wp[k] : 0u) ^ 0x80808080u;
-            }
+            for (int k = 0; k < 4; k++)
+                w[k] = (k * 4 < SEG + NT - 1 ? __builtin_amdgcn_alignbyte(r[k + 1], r[k], sh) : 0u) ^ 0x80808080u;
 #pragma unroll
             for (int o = 0; o < SEG; o++) {
                 const uint32_t lo = (o & 3) ? __builtin_amdgcn_alignbyte(w[(o >> 2) + 1], w[o >> 2], o & 3) : w[o >> 2];
@@ -553,112 +497,6 @@ __device__ __forceinline__ void ep_mc8_tile(EpMcScratch<uint8_t> &M, int lane, i
     }
     EP_WAVE_SYNC();
 }
-/* the core for 8-bit planes: dst = the block's first sample, pitch in samples (plane p of the 2Nx2N unit at (abs_x, abs_y)) */
-__device__ __forceinline__ void ep_inter_predict_core8(const EpRefPlanes *refs /* [2]: P.ref, or the caller's copy of it in LDS */, int abs_x, int abs_y, int N, int inter_dir,
-                                                       const int16_t (*mv)[2], int p, int lane, EpMcScratch<uint8_t> &M, uint8_t *dst, int pitch, int tile_first, int tile_step,
-                                                       const EpRefWindows *RW)
-{
-    constexpr int WP = EpMcScratch<uint8_t>::WP;
-    const bool chroma = p != 0;
-    const int n = chroma ? N >> 1 : N, tn = n > 32 ? 32 : n;
-    const int ntaps = chroma ? 4 : 8, first = chroma ? -1 : -3, rows = tn + ntaps - 1;
-    const bool bi = inter_dir == 2;
-    const int ntile = n > 32 ? 4 : 1;
-#ifdef EP_DEBUG_WINDOW_COUNTS
-    unsigned long long dbg_t_ = __builtin_readcyclecounter();
-#endif
-    for (int ti = tile_first; ti < ntile; ti += tile_step) {
-        const int ty0 = (ti >> 1) << 5, tx0 = (ti & 1) << 5;
-        bool second = false;
-        for (int l = 0; l < 2; l++) {
-            if (!(bi || inter_dir == l))
-                continue;
-            MD_TR(40);
-            const EpRefPlanes R = refs[l]; /* one read of the whole record */
-            const int qx = min(max(((abs_x + R.originX) << 2) + mv[l][0], (R.originX - 71) << 2), (R.width + R.originX + 7) << 2);
-            const int qy = min(max(((abs_y + R.originY) << 2) + mv[l][1], (R.originY - 71) << 2), (R.height + R.originY + 7) << 2);
-            const int ix = (chroma ? qx >> 3 : qx >> 2) + tx0, iy = (chroma ? qy >> 3 : qy >> 2) + ty0;
-            const int fx = __builtin_amdgcn_readfirstlane(chroma ? qx & 7 : qx & 3), fy = __builtin_amdgcn_readfirstlane(chroma ? qy & 7 : qy & 3);
-            const int cpr = (rows + 7) >> 3, nchunk = rows * cpr, inv = (65536 + cpr - 1) / cpr;
-            bool staged = false;
-            MD_TR(41);
-            EP_DBG_CLK(4);
-#ifdef EP_DEBUG_WINDOW_COUNTS
-            if (lane == 0 && !chroma)
-                atomicAdd(&g_ep_dbg_counts[0], 1u);
-#endif
-            if (RW && !chroma && RW->valid[l]) {
-                const int rx = ix + first - RW->x0[l], ry = iy + first - RW->y0[l];
-                if (rx >= 0 && ry >= 0 && rx + cpr * 8 <= EpRefWindows::P && ry + rows <= EpRefWindows::H) {
-                    staged = true;
-                    for (int i = lane; i < nchunk; i += 64) {
-                        const int j = (i * inv) >> 16, m = i - j * cpr, o = (ry + j) * EpRefWindows::P + rx + m * 8, sh = o & 3;
-                        const uint32_t *wp = reinterpret_cast<const uint32_t *>(&RW->pix[l][o & ~3]);
-                        const uint32_t w0 = wp[0], w1 = wp[1], w2 = wp[2];
-                        uint2 v;
-                        v.x = __builtin_amdgcn_alignbyte(w1, w0, sh), v.y = __builtin_amdgcn_alignbyte(w2, w1, sh);
-                        *reinterpret_cast<uint2 *>(&M.win[j * WP + m * 8]) = v;
-                    }
-                }
-            }
-            if (!staged) {
-                const int stride = (int)R.stride[chroma], last = R.size[chroma] - 1;
-                const uint8_t *plane = (const uint8_t *)R.plane[p];
-                const int base0 = (iy + first) * stride + ix + first;
-                for (int i0 = 0; i0 < nchunk; i0 += 256) {
-                    uint2 v[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int i = i0 + u * 64 + lane;
-                        if (i < nchunk) {
-                            const int j = (i * inv) >> 16, m = i - j * cpr, idx = base0 + j * stride + m * 8;
-                            if (idx >= 0 && idx + 8 <= last + 1) {
-                                __builtin_memcpy(&v[u], plane + idx, 8);
-                            } else {
-                                uint8_t e[8];
-#pragma unroll
-                                for (int q = 0; q < 8; q++)
-                                    e[q] = plane[min(max(idx + q, 0), last)];
-                                __builtin_memcpy(&v[u], e, 8);
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const int i = i0 + u * 64 + lane;
-                        if (i < nchunk) {
-                            const int j = (i * inv) >> 16, m = i - j * cpr;
-                            *reinterpret_cast<uint2 *>(&M.win[j * WP + m * 8]) = v[u];
-                        }
-                    }
-                }
-            }
-            EP_WAVE_SYNC();
-            MD_TR(staged ? 42 : 46);
-            EP_DBG_CLK(5);
-            const int mode = !bi ? 0 : (second ? 2 : 1);
-            uint8_t *td = dst + ty0 * pitch + tx0;
-            if (!chroma) {
-                switch (tn) {
-                case 32: ep_mc8_tile<32, false>(M, lane, fx, fy, mode, td, pitch); break;
-                case 16: ep_mc8_tile<16, false>(M, lane, fx, fy, mode, td, pitch); break;
-                default: ep_mc8_tile<8, false>(M, lane, fx, fy, mode, td, pitch); break;
-                }
-            } else {
-                switch (tn) {
-                case 32: ep_mc8_tile<32, true>(M, lane, fx, fy, mode, td, pitch); break;
-                case 16: ep_mc8_tile<16, true>(M, lane, fx, fy, mode, td, pitch); break;
-                case 8: ep_mc8_tile<8, true>(M, lane, fx, fy, mode, td, pitch); break;
-                default: ep_mc8_tile<4, true>(M, lane, fx, fy, mode, td, pitch); break;
-                }
-            }
-            MD_TR(44);
-            EP_DBG_CLK(6);
-            second = true;
-        }
-    }
-}
-
 __device__ __forceinline__ void ep_ref_windows_fill(const EpRefPlanes *refs, int lcu_x, int lcu_y, const bool use[2], const int16_t (*mv)[2], EpRefWindows &RW, int t)
 {
     for (int l = 0; l < 2; l++) {
@@ -668,10 +506,9 @@ __device__ __forceinline__ void ep_ref_windows_fill(const EpRefPlanes *refs, int
             continue;
         }
         const EpRefPlanes &R = refs[l];
-        /* the position clamp of the core (Codec/EbInterPrediction.c:802-812) applied to the LCU's origin displaced by the centre vector */
-        const int qx = min(max(((lcu_x + R.originX) << 2) + mv[l][0], (R.originX - 71) << 2), (R.width + R.originX + 7) << 2);
-        const int qy = min(max(((lcu_y + R.originY) << 2) + mv[l][1], (R.originY - 71) << 2), (R.height + R.originY + 7) << 2);
-        const int x0 = (qx >> 2) - 3 - EpRefWindows::R, y0 = (qy >> 2) - 3 - EpRefWindows::R;
+        /* the position clamp of the core (inter_position.h) applied to the LCU's origin displaced by the centre vector */
+        const int qx = INTER_POS_CLAMP(lcu_x, R.originX, mv[l][0], R.width), qy = INTER_POS_CLAMP(lcu_y, R.originY, mv[l][1], R.height);
+        const int x0 = inter_pos_int(qx, 0) - 3 - EpRefWindows::R, y0 = inter_pos_int(qy, 0) - 3 - EpRefWindows::R;
         const int stride = (int)R.stride[0], last = R.size[0] - 1;
         const uint8_t *plane = (const uint8_t *)R.plane[0];
         constexpr int CPR = EpRefWindows::P / 8, NCH = EpRefWindows::H * CPR, NU = (NCH + 255) / 256;
@@ -716,9 +553,8 @@ __device__ __forceinline__ void ep_ref_windows_fill_chroma(const EpRefPlanes *re
             continue;
         }
         const EpRefPlanes &R = refs[l];
-        const int qx = min(max(((lcu_x + R.originX) << 2) + mv[l][0], (R.originX - 71) << 2), (R.width + R.originX + 7) << 2);
-        const int qy = min(max(((lcu_y + R.originY) << 2) + mv[l][1], (R.originY - 71) << 2), (R.height + R.originY + 7) << 2);
-        const int x0 = (qx >> 3) - 1 - EpRefWindowsC::R, y0 = (qy >> 3) - 1 - EpRefWindowsC::R;
+        const int qx = INTER_POS_CLAMP(lcu_x, R.originX, mv[l][0], R.width), qy = INTER_POS_CLAMP(lcu_y, R.originY, mv[l][1], R.height);
+        const int x0 = inter_pos_int(qx, 1) - 1 - EpRefWindowsC::R, y0 = inter_pos_int(qy, 1) - 1 - EpRefWindowsC::R;
         const int stride = (int)R.stride[1], last = R.size[1] - 1;
         constexpr int WPR = EpRefWindowsC::P / 4, NW = EpRefWindowsC::H * WPR;
         for (int i = t; i < 2 * NW; i += 256) {

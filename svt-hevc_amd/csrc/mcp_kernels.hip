@@ -347,8 +347,7 @@ extern "C" void svt_amd_BiPredClipping16bit(uint32_t puWidth, uint32_t puHeight,
  * launch for the uni-predicted units (straight into the prediction planes), one for the 14-bit intermediates of the
  * bi-predicted ones, then one averaging launch per plane. */
 #include <vector>
-
-static inline int clampi(int lo, int hi, int v) { return v < lo ? lo : v > hi ? hi : v; }
+#include "inter_position.h"
 
 template <typename T, typename TS = T>
 static int inter_pu_batch(SvtAmdContext *ctx, const SvtAmdInterPuJob *jobs, uint32_t njobs, const SvtAmdRefPicture *ref0,
@@ -371,14 +370,13 @@ static int inter_pu_batch(SvtAmdContext *ctx, const SvtAmdInterPuJob *jobs, uint
             const SvtAmdRefPicture *R = refs[l];
             if (!R || !R->d_y || !R->d_cb || !R->d_cr)
                 return SVT_AMD_ERR_BAD_PARAM;
-            const int px = clampi(((int)R->originX - 71) << 2, (int)(R->width + R->originX + 7) << 2, (((int)J.pu_x + (int)R->originX) << 2) + J.mv[l][0]);
-            const int py = clampi(((int)R->originY - 71) << 2, (int)(R->height + R->originY + 7) << 2, (((int)J.pu_y + (int)R->originY) << 2) + J.mv[l][1]);
+            const int qx = INTER_POS_CLAMP((int)J.pu_x, (int)R->originX, J.mv[l][0], (int)R->width), qy = INTER_POS_CLAMP((int)J.pu_y, (int)R->originY, J.mv[l][1], (int)R->height);
             for (int p = 0; p < 3; p++) {
                 const int sh = p ? 1 : 0;
                 McpBlock b;
                 b.w = (uint16_t)(J.pu_w >> sh), b.h = (uint16_t)(J.pu_h >> sh), b.pad[0] = b.pad[1] = 0;
-                b.fx = (uint8_t)(p ? px & 7 : px & 3), b.fy = (uint8_t)(p ? py & 7 : py & 3);
-                b.ref_off = (int32_t)((p ? py >> 3 : py >> 2) * (int)(p ? R->strideC : R->strideY) + (p ? px >> 3 : px >> 2));
+                b.fx = (uint8_t)inter_pos_frac(qx, p), b.fy = (uint8_t)inter_pos_frac(qy, p);
+                b.ref_off = (int32_t)(inter_pos_int(qy, p) * (int)(p ? R->strideC : R->strideY) + inter_pos_int(qx, p));
                 if (is_bi) {
                     b.dst_off = (int32_t)raw_len[p]; /* same offset in both lists' intermediate buffers */
                     raw[l][p].push_back(b);

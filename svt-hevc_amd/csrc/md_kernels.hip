@@ -21,7 +21,7 @@
  *                 the packed list of candidates that really need a prediction, prediction slots
  *   wave 0        (I pictures) intra reference of the unit: availability by ballot, substitution, [1 2 1] / strong smoothing   (8.4.4.2.2-3)
  *   4 waves       fast loop: ONE list of tasks (candidate, plane, tile) dealt to the waves - luma blocks (64x64 units: four 32x32 tiles), then, in CHROMA_MODE_FULL LCUs,
- *                 the Cb and Cr blocks of every evaluated candidate; inter prediction through ep_inter_predict_core8 (encdec_device.h: LDS-staged reference windows,
+ *                 the Cb and Cr blocks of every evaluated candidate; inter prediction through md_predict_tile / ep_mc8_tile (encdec_device.h: LDS-staged reference windows,
  *                 v_dot4 / v_dot2 filters), intra prediction evaluated per sample in closed form (intra_device.h), SAD by v_sad_u8 on words, added to the candidate's
  *                 LDS accumulator
  *   wave 0        fast costs a lane per candidate (with the chroma distortion and the noise-class rule where the LCU has it), the candidate-buffer replay with the
@@ -843,7 +843,7 @@ __device__ __noinline__ void md_window_from_plane(const uint8_t *plane, int stri
     }
 }
 /* Inter2Nx2NPuPredictionHevc (Codec/EbInterPrediction.c:468) of ONE TILE (TN x TN samples: the whole block of a unit up to 32x32 / its chroma block, a quarter of a 64x64
- * unit's luma) of plane p of a candidate, by one wave, both lists: ep_inter_predict_core8 (encdec_device.h) with the tile size and the tap count decided at compile time -
+ * unit's luma) of plane p of a candidate, by one wave, both lists: the position clamp and the window, then ep_mc8_tile (encdec_device.h) with the tile size and the tap count decided at compile time -
  * a function per size (the 16x16 and 8x8 blocks most units have need a fraction of the registers of the 32x32 form: no callee-saved register, so no private-segment traffic
  * around the call), everything passed BY VALUE (a candidate passed by reference went through the private segment: a memory round trip of ~1.5 K clocks per call on the unit
  * chain).  mv0 / mv1: x | y << 16.  td: the tile's first sample in the destination, pitch in samples. */
@@ -864,10 +864,9 @@ __device__ MD_LEAF_CALL void md_predict_tile(const EpRefPlanes *refs, int abs_x,
         const EpRefPlanes R = refs[l]; /* one read of the whole record */
         const uint32_t mvw = l ? mv1 : mv0;
         const int mvx = (int)(int16_t)(mvw & 0xFFFF), mvy = (int)(int16_t)(mvw >> 16);
-        const int qx = min(max(((abs_x + R.originX) << 2) + mvx, (R.originX - 71) << 2), (R.width + R.originX + 7) << 2);
-        const int qy = min(max(((abs_y + R.originY) << 2) + mvy, (R.originY - 71) << 2), (R.height + R.originY + 7) << 2);
-        const int ix = (CHROMA ? qx >> 3 : qx >> 2) + tx0, iy = (CHROMA ? qy >> 3 : qy >> 2) + ty0;
-        const int fx = __builtin_amdgcn_readfirstlane(CHROMA ? qx & 7 : qx & 3), fy = __builtin_amdgcn_readfirstlane(CHROMA ? qy & 7 : qy & 3);
+        const int qx = INTER_POS_CLAMP(abs_x, R.originX, mvx, R.width), qy = INTER_POS_CLAMP(abs_y, R.originY, mvy, R.height);
+        const int ix = inter_pos_int(qx, CHROMA) + tx0, iy = inter_pos_int(qy, CHROMA) + ty0;
+        const int fx = __builtin_amdgcn_readfirstlane(inter_pos_frac(qx, CHROMA)), fy = __builtin_amdgcn_readfirstlane(inter_pos_frac(qy, CHROMA));
         MD_TR(41);
         /* where the filter reads the window: a staged one where it lies (EpRefWindows / EpRefWindowsC), any other from the scratch copy the fall-back below makes - ONE
          * instance of the filter per tile size either way (two were ~1 K instructions more per function, in a loop whose code does not fit the instruction cache) */
@@ -892,7 +891,7 @@ __device__ MD_LEAF_CALL void md_predict_tile(const EpRefPlanes *refs, int abs_x,
             EP_WAVE_SYNC();
         }
         MD_TR(42);
-        ep_mc8_tile<TN, CHROMA, true>(M, lane, fx, fy, !bi ? 0 : (second ? 2 : 1), td, pitch, M.win + dbase, doff, dpitch);
+        ep_mc8_tile<TN, CHROMA>(M, lane, fx, fy, !bi ? 0 : (second ? 2 : 1), td, pitch, M.win + dbase, doff, dpitch);
         MD_TR(44);
         second = true;
     }
@@ -1293,7 +1292,7 @@ __device__ __forceinline__ void md_units_inter(const MdPictureDev &D, int lcu, i
     const int pf = md_pf_mode(&Ph);
     /* what the picture and the LCU fix, read once */
     constexpr bool cfull = CFULL; /* CHROMA_MODE_FULL (Lh.chroma_encode_mode == 1): chroma in both loops of every candidate */
-    const bool tile_l = Lh.tile_left != 0, tile_t = Lh.tile_top != 0, tile_r = Lh.tile_right != 0;
+    const bool tile_l = Lh.tile_left != 0, tile_t = Lh.tile_top != 0;
     const MdListConsts K = md_list_consts(Ph, M.V.X);
     const uint32_t sfb0 = P.rates.splitFlagBits[0], sfb1 = P.rates.splitFlagBits[1], sfb2 = P.rates.splitFlagBits[2]; /* SplitFlagRate of an unsplit unit, by context */
     const bool tmvp_on = M.V.X.tmvp_enable != 0;
@@ -2611,7 +2610,6 @@ __device__ __forceinline__ void md_ep_kinds(const MdPictureDev &D, const SvtAmdM
     const SvtAmdMdPicture &P = M.pic;
     (void)Pg;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const int lw = min(64, (int)P.width - lcu_x), lh = min(64, (int)P.height - lcu_y);
     if (t == 0) {
         int n = 0, it = 0;
         while (it < SVT_AMD_MD_LEAVES) {
@@ -3850,15 +3848,6 @@ extern "C" int svt_amd_debug_md_profile_depth(SvtAmdContext *ctx, SvtAmdEncDecPi
     HIP_TRY(hipMemcpy(out, pic->md->d_prof + 32 * (size_t)pic->nlcu, sizeof(unsigned long long) * 128 * (size_t)pic->nlcu, hipMemcpyDeviceToHost));
     return SVT_AMD_OK;
 }
-
-#ifdef EP_DEBUG_WINDOW_COUNTS
-extern "C" __attribute__((visibility("default"))) int svt_amd_debug_window_counts(unsigned *out)
-{
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ep_dbg_counts), sizeof(unsigned) * 8));
-    return SVT_AMD_OK;
-}
-#endif
 
 extern "C" int svt_amd_md_picture_set_controls(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const SvtAmdMdLcu *d_lcus)
 {

@@ -40,7 +40,6 @@
  * LDS admits six as well: static + pool = 5,200 + 11,776 B at BASELINE configs[2] (me_pool_bytes). */
 #define ME_HME_WAVES_PER_SIMD 6
 #endif
-#define MAX_SAD_VALUE (64 * 64 * 255)
 #define COST_PRECISION 8
 #define MD_SHIFT 23
 #define MD_OFFSET (1u << 22)
@@ -236,23 +235,7 @@ __device__ __forceinline__ int load_window(LWin &w, int off, const uint8_t *plan
     return off + rows * wa;
 }
 
-/* Window whose first column is the plane column x0 ITSELF (any alignment): unaligned 16-byte global loads, 16-byte LDS stores */
 typedef uint4 __attribute__((aligned(1))) u128u_w;
-__device__ __forceinline__ int load_window_at(LWin &w, int off, const uint8_t *plane, int pitch, int x0, int y0, int x1, int y1, int t,
-                                              int odd = 0)
-{
-    int wa = ((x1 - x0) + 15) & ~15;
-    if (odd && !((wa >> 4) & 1))
-        wa += 16;
-    const int n16 = wa >> 4, rows = y1 - y0;
-    uint8_t *dst = g_pool + off;
-    w.p = dst, w.x0 = x0, w.y0 = y0, w.stride = wa;
-    for (int i = t; i < rows * n16; i += NT) {
-        const int r = i / n16, c = i - r * n16;
-        *(uint4 *)(dst + r * wa + c * 16) = *(const u128u_w *)(plane + (ptrdiff_t)(y0 + r) * pitch + x0 + c * 16);
-    }
-    return off + rows * wa;
-}
 __device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < b ? a : b; }
 __device__ __forceinline__ uint4 ldu16(const uint8_t *p) /* one unaligned 16-byte global load */
 {

@@ -483,7 +483,7 @@ static int rate_tables_once(int device)
     return SVT_AMD_OK;
 }
 /* per call: the caller's CabacCost_t into the context's own buffer, stream-ordered before the kernels that read it */
-static int rate_upload_tables(SvtAmdContext *ctx, const SvtAmdCabacCost *cost)
+static inline int rate_upload_tables(SvtAmdContext *ctx, const SvtAmdCabacCost *cost)
 {
     int rc = rate_tables_once(ctx->device);
     if (rc)

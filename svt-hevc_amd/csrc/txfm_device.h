@@ -1,5 +1,5 @@
 /* Device code shared by the transform kernels (txfm_kernels.hip) and the fused full-loop kernel
- * (fullloop_kernels.hip): HEVC core matrix, LDS working set, one 1-D forward pass.  Each translation unit gets its own
+ * (fullloop_kernels.hip): HEVC core matrix, register-resident 1-D forward pass.  Each translation unit gets its own
  * copy of the constant table (statically initialised, no upload needed). */
 #ifndef SVT_AMD_TXFM_DEVICE_H
 #define SVT_AMD_TXFM_DEVICE_H
@@ -49,72 +49,11 @@ static __device__ const int8_t d_T32[32][32] = SVT_T32_INIT;
 __device__ __forceinline__ int clip16i(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
 /* ------------------------------------------------------------------------- */
-/* forward / inverse transforms: one workgroup per group of GB blocks         */
-/* ------------------------------------------------------------------------- */
-
-template <int N, int G = ((N >= 16) ? 1 : (N == 8 ? 4 : 16))>
-struct TxShared {
-    static constexpr int GB = G; /* blocks per workgroup */
-    int8_t T[32][32];
-    int16_t io[GB][N * N];  /* input, later the transposed first-pass output */
-    int32_t E[GB][N][N + 1]; /* running even vector, levels evaluated in place; +1: the dot-product stage walks  */
-    int32_t D[GB][N][N + 1]; /* rows with the row index fastest, unpadded rows would all hit one LDS bank.       */
-                             /* D: [h..2h) = odd vector of length h */
-};
-
-/* one 1-D forward pass over all rows of the GB blocks held in S.io; output transposed into dst */
-template <int N, bool TO_GLOBAL, int NT = TX_THREADS, int G = ((N >= 16) ? 1 : (N == 8 ? 4 : 16))>
-__device__ void fwd_pass(TxShared<N, G> &S, int shift, int wrap_levels, int16_t *gdst, int nvalid, int t)
-{
-    constexpr int GB = G;
-    constexpr int LOG = N == 32 ? 5 : N == 16 ? 4 : N == 8 ? 3 : 2;
-    for (int i = t; i < GB * N * N; i += NT)
-        S.E[i / (N * N)][(i / N) % N][i % N] = (&S.io[0][0])[i];
-    __syncthreads();
-#pragma unroll
-    for (int m = 0; m < LOG - 1; m++) {
-        const int half = N >> (m + 1);
-        for (int i = t; i < GB * N * half; i += NT) {
-            const int j = i % half, r = (i / half) % N, b = i / (half * N);
-            int s = S.E[b][r][j] + S.E[b][r][2 * half - 1 - j], d = S.E[b][r][j] - S.E[b][r][2 * half - 1 - j];
-            if (m < wrap_levels)
-                s = (int16_t)s, d = (int16_t)d;
-            S.D[b][r][half + j] = d;
-            S.E[b][r][j] = s; /* indices >= half are only read in this level: no hazard */
-        }
-        __syncthreads();
-    }
-    const int offset = (int16_t)(1 << (shift - 1));
-    for (int i = t; i < GB * N * N; i += NT) {
-        const int r = i % N, k = (i / N) % N, b = i / (N * N);
-        int acc = 0;
-        if ((k & (N / 2 - 1)) == 0) { /* k == 0 or N/2: last even pair */
-            acc = S.T[k * (32 / N)][0] * S.E[b][r][0] + S.T[k * (32 / N)][1] * S.E[b][r][1];
-        } else {
-            const int m = __ffs(k) - 1, len = N >> (m + 1);
-            const int8_t *c = S.T[k * (32 / N)];
-            const int32_t *dv = &S.D[b][r][len];
-            for (int j = 0; j < len; j++)
-                acc += c[j] * dv[j];
-        }
-        const int16_t v = (int16_t)((acc + offset) >> shift);
-        if (TO_GLOBAL) {
-            if (b < nvalid)
-                gdst[(size_t)b * N * N + k * N + r] = v;
-        } else {
-            S.io[b][k * N + r] = v;
-        }
-    }
-    __syncthreads();
-}
-
-
-/* ------------------------------------------------------------------------- */
 /* register-resident forward transform: one lane = one row                   */
 /* ------------------------------------------------------------------------- */
 /* One 1-D N-point forward pass of the partial-butterfly transforms (C_DEFAULT/EbTransforms_C.c:1602-1861) on a row held
- * in registers: e[] = the row (destroyed), emit(k, v) receives output k.  Same arithmetic as fwd_pass above (even / odd
- * split per level, the low-precision "Estimate" variants wrap the first `wrap_levels` levels to 16 bits); loops are
+ * in registers: e[] = the row (destroyed), emit(k, v) receives output k.  Even / odd split per level, the last even pair
+ * and the odd vectors as dot products (the low-precision "Estimate" variants wrap the first `wrap_levels` levels to 16 bits); loops are
  * fully unrolled so every matrix entry is an immediate and no coefficient is ever read from memory. */
 template <int N, typename Emit>
 __device__ __forceinline__ void fwd_1d_regs(int (&e)[N], int shift, int wrap_levels, Emit emit)

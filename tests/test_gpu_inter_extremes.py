@@ -419,7 +419,7 @@ def test_encode_picture_predicts_from_matched_reference_pictures(product, oracle
 @pytest.mark.parametrize("butterflies", [0, 1])
 @pytest.mark.parametrize("name,k,signs", X.MD_CASES)
 def test_md_decides_on_matched_reference_pictures(product, oracle, name, k, signs, butterflies):
-    """ep_inter_predict_core8 / ep_mc8_tile (and its DIRECT form on the staged window): a recorded P / B picture's source, ME records and controls with both
+    """md_predict_tile / ep_mc8_tile (on the staged window where it lies and on the scratch copy md_window_from_plane makes of any other): a recorded P / B picture's source, ME records and controls with both
     reference pictures replaced by matched planes (the signs of the two lists' planes: inter_extremes.MD_CASES); every tested leaf's decisions AND costs against the oracle's on the same inputs, so one wrong prediction
     sample in a tested leaf shows.  Once more with every forward transform on the register butterflies: the full-loop residuals are the largest there.
     Nothing pins the oracle's mode decision to the reference on substituted inputs: its interpolation is pinned at these ends by tests/test_oracle_mcp.py,
