@@ -1853,6 +1853,63 @@ typedef struct SvtAmdCoeffScanLcu {
 SVT_AMD_API int svt_amd_coeff_scan_picture(SvtAmdContext *ctx, const void *works, size_t work_stride, const void *results, size_t result_stride,
                                            int device_arrays, int n_lcus, SvtAmdCoeffScanLcu *lcus, SvtAmdCoeffScanGroup *groups,
                                            uint32_t group_capacity, uint16_t *levels, uint32_t level_capacity, uint32_t totals[2]);
+/* The same hand-off as a STREAM-ORDERED LAUNCH on the records in HBM, the last stage of the per-picture chain (svt_amd_md_encode_picture_launch,
+ * svt_amd_encdec_picture_tail_launch, then this): everything is queued on ctx's stream and the call returns.  It synchronises nothing, copies nothing from or to
+ * host memory and waits for no event.  It has no working memory: it never touches the context's scratch, and everything it needs between its three kernels lies in
+ * the caller's output arrays (the per-LCU counts are fields of SvtAmdCoeffScanLcu), so launches into different output arrays may be in flight together.  The only
+ * thing the first call on a device does that later calls do not is the upload of the immutable scan tables.  svt_amd_coeff_scan_picture above is unchanged.
+ *   Outputs (every pointer DEVICE memory; nothing behind n_lcus records or behind either capacity is ever written).  On well-formed records lcus[] with its
+ *   bases, groups[0 .. head.groups), levels[0 .. head.levels) and {head.groups, head.levels} are byte for byte what svt_amd_coeff_scan_picture returns: the same
+ *   lists packed in LCU order.  work_heads / result_heads (optional) receive the first 1584 / 768 bytes of every record - head and unit list, cbf and count
+ *   records: what the entropy coder reads besides the lists - of refused LCUs too: a copy, not a judgement.
+ *   Overflow is no failure the host could see - the call has returned by then: head carries the totals the picture NEEDS and the overflow bits; an LCU whose
+ *   group range [group_base, group_base + groups) fits the capacity has its groups written, one whose level range fits has its levels written, each list judged on
+ *   its own; lcus[] is complete in either case, so the caller can launch again with the capacities head names.
+ *   The records are not validated on the host; what a host loop would refuse is COUNTED in head, as SvtAmdTailCheck counts (first_* 0xFFFFFFFF: none).
+ *     A bad LCU: num_cus > 64, or its well-formed units cover more than 64x64 samples together (they overlap: the lists of an LCU hold 384 sub-blocks).  It has no
+ *     block: groups = levels = 0 and every tu says "nothing to code" (last_scan_set -1, everything else 0).  Its units are not counted.
+ *     A bad unit: its size is not 8 / 16 / 32 / 64, or x or y is not a multiple of 8, or it leaves the LCU, or it is a 64x64 unit that is not the only unit of its
+ *     LCU at (0, 0).  None of its three blocks is scanned; its slots read "nothing to code".
+ *     No access leaves the record arrays, whatever the records hold.
+ *   Everything the host can judge is checked before anything is queued: NULL required pointers, alignment, strides, n_lcus, non-zero pads, a picture object of
+ *   another device.  A refusal names the entry in svt_amd_last_error and queues nothing. */
+typedef struct SvtAmdEntropyHandoffHead {      /* 32 bytes, written once per launch */
+    uint32_t groups, levels;                   /* what the picture NEEDS (whether or not it fitted) */
+    uint32_t overflow;                         /* bit 0: groups > group_capacity, bit 1: levels > level_capacity */
+    uint32_t bad_lcus, first_bad_lcu;          /* as SvtAmdTailCheck: 0xFFFFFFFF = none */
+    uint32_t bad_units, first_bad_unit_lcu;
+    uint32_t pad;                              /* written as 0 */
+} SvtAmdEntropyHandoffHead;
+typedef struct SvtAmdEntropyHandoffJob {
+    const void *d_works;  size_t work_stride;  /* DEVICE SvtAmdLcuWork[16], 4-byte aligned; stride a multiple of 4, >= the head + unit list (1584) */
+    const void *d_results; size_t result_stride;/* DEVICE SvtAmdLcuResult[16], 4-byte aligned; stride a multiple of 4, >= offsetof(rec_y) */
+    uint32_t n_lcus;                           /* 1 .. SVT_AMD_MDCTL_MAX_LCUS */
+    uint32_t group_capacity, level_capacity;   /* elements of out.groups / out.levels */
+    uint32_t pad;                              /* 0 */
+} SvtAmdEntropyHandoffJob;
+typedef struct SvtAmdEntropyHandoffOut {       /* every pointer DEVICE memory */
+    SvtAmdEntropyHandoffHead *head;            /* required, 4-byte aligned */
+    SvtAmdCoeffScanLcu *lcus;                  /* required, [n_lcus], 4-byte aligned */
+    SvtAmdCoeffScanGroup *groups;              /* required, [group_capacity], 8-byte aligned */
+    uint16_t *levels;                          /* required, [level_capacity] */
+    void *work_heads;                          /* optional: [n_lcus][1584], the head and unit list of every work record, tight; 4-byte aligned */
+    SvtAmdLcuCuResult *result_heads;           /* optional: [n_lcus][SVT_AMD_LCU_MAX_CUS], tight; 4-byte aligned */
+} SvtAmdEntropyHandoffOut;
+#define SVT_AMD_ENTROPY_HANDOFF_HEAD 0
+#define SVT_AMD_ENTROPY_HANDOFF_LCUS 1
+#define SVT_AMD_ENTROPY_HANDOFF_GROUPS 2
+#define SVT_AMD_ENTROPY_HANDOFF_LEVELS 3
+#define SVT_AMD_ENTROPY_HANDOFF_WORK_HEADS 4
+#define SVT_AMD_ENTROPY_HANDOFF_RESULT_HEADS 5
+/* bytes of the output arrays of a picture: _HEAD 32, _LCUS LCUs * sizeof(SvtAmdCoeffScanLcu), _GROUPS the worst case of 384 groups an LCU, _LEVELS the worst
+ * case of 6144 levels an LCU, _WORK_HEADS LCUs * 1584, _RESULT_HEADS LCUs * 768; 0 for anything else.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_entropy_handoff_bytes(uint16_t luma_width, uint16_t luma_height, int which);
+SVT_AMD_API int svt_amd_entropy_handoff_launch(SvtAmdContext *ctx, const SvtAmdEntropyHandoffJob *job, const SvtAmdEntropyHandoffOut *out);
+/* The object form: the records the LAST svt_amd_md_encode_picture[_inter][16] call or launch left on `pic`, and the object's number of LCUs.  Refused exactly where
+ * svt_amd_encdec_picture_motion_field is refused - no completed call, a P / B call that decided only, an object with a rank rectangle
+ * (svt_amd_encdec_picture_set_rect) - and on a picture object of another device.  Queued on ctx's stream: on the context that call ran on, stream order suffices. */
+SVT_AMD_API int svt_amd_encdec_picture_entropy_handoff(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, uint32_t group_capacity, uint32_t level_capacity,
+                                                       const SvtAmdEntropyHandoffOut *out);
 
 /* Deblocking behind the encode pass: when every LCU of the picture is encoded, a copy of the device picture (a second set of planes of
  * the picture object; the un-deblocked planes stay as they are) goes through the
