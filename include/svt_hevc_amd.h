@@ -1849,7 +1849,15 @@ typedef struct SvtAmdCoeffScanLcu {
  * (device_arrays 1: what svt_amd_encode_picture_device / svt_amd_md_encode_picture left in HBM); work_stride / result_stride: sizeof the record
  * type (the 8- and 16-bit records share their heads, coefficients are s16 in both).  Outputs (HOST): lcus[n_lcus]; groups / levels: the
  * picture's lists, compacted in LCU order - capacities in elements (worst case 384 / 6144 per LCU); totals[2] = {groups, levels} written.
- * SVT_AMD_ERR_RESOURCES when a capacity is too small (totals then tell what is needed).  Blocking. */
+ * SVT_AMD_ERR_RESOURCES when a capacity is too small (totals then tell what is needed).  Blocking.
+ * HOST arrays may lie at any address and stride; only the first 1584 bytes of a work record and the offsetof(rec_y) bytes in front of a result record's
+ * reconstruction are uploaded.  DEVICE arrays are read in place, by words: both arrays 4-byte aligned, both strides multiples of 4 (and, as for host arrays, at
+ * least 1584 / offsetof(rec_y)) - every sizeof of the record types and every hipMalloc pointer keeps that rule; anything else is SVT_AMD_ERR_BAD_PARAM.
+ * The call runs the kernels of the stream-ordered launch below into the context's scratch (head, lcus, the lists up to min(capacity, worst case), the uploaded
+ * heads) and keeps what is its own: these checks, the upload, the downloads, the waits, the return codes.  n_lcus has no upper limit here.
+ * Malformed records (a bad LCU or a bad unit as the launch below counts them) are refused: SVT_AMD_ERR_BAD_PARAM, judged before the capacities;
+ * svt_amd_last_error names this entry, both counts, the first bad LCU and the first LCU with a bad unit (-1: none).  As with SVT_AMD_ERR_RESOURCES, totals and
+ * lcus[] are written (a refused LCU or unit reads "nothing to code") and groups / levels are not touched. */
 SVT_AMD_API int svt_amd_coeff_scan_picture(SvtAmdContext *ctx, const void *works, size_t work_stride, const void *results, size_t result_stride,
                                            int device_arrays, int n_lcus, SvtAmdCoeffScanLcu *lcus, SvtAmdCoeffScanGroup *groups,
                                            uint32_t group_capacity, uint16_t *levels, uint32_t level_capacity, uint32_t totals[2]);
@@ -1857,7 +1865,7 @@ SVT_AMD_API int svt_amd_coeff_scan_picture(SvtAmdContext *ctx, const void *works
  * svt_amd_encdec_picture_tail_launch, then this): everything is queued on ctx's stream and the call returns.  It synchronises nothing, copies nothing from or to
  * host memory and waits for no event.  It has no working memory: it never touches the context's scratch, and everything it needs between its three kernels lies in
  * the caller's output arrays (the per-LCU counts are fields of SvtAmdCoeffScanLcu), so launches into different output arrays may be in flight together.  The only
- * thing the first call on a device does that later calls do not is the upload of the immutable scan tables.  svt_amd_coeff_scan_picture above is unchanged.
+ * thing the first call on a device does that later calls do not is the upload of the immutable scan tables.  svt_amd_coeff_scan_picture above runs these kernels too.
  *   Outputs (every pointer DEVICE memory; nothing behind n_lcus records or behind either capacity is ever written).  On well-formed records lcus[] with its
  *   bases, groups[0 .. head.groups), levels[0 .. head.levels) and {head.groups, head.levels} are byte for byte what svt_amd_coeff_scan_picture returns: the same
  *   lists packed in LCU order.  work_heads / result_heads (optional) receive the first 1584 / 768 bytes of every record - head and unit list, cbf and count

@@ -1,7 +1,7 @@
-/* coeffscan_device.h - the per-LCU digest of the entropy hand-off pre-scan as device functions, shared by its blocking entry (coeffscan_kernels.hip:
- * per-LCU pools, compacted) and its stream-ordered launch (handoff_kernels.hip: counted, then written in place): the block table of an LCU's units, the
- * workgroup scan, the 4x4 scans, the digest of a sub-block's 16 values in registers and the per-block lists (last sub-block, groups, levels, the
- * SvtAmdCoeffScanTu record).  What each step restates of EncodeQuantizedCoefficients (Codec/EbEntropyCoding.c:1172) is said where it stands. */
+/* coeffscan_device.h - the per-LCU digest of the entropy hand-off pre-scan as device functions, for the kernels of handoff_kernels.hip (counted, then written in
+ * place): the block table of an LCU's units, the workgroup scan, the 4x4 scans, the digest of a sub-block's 16 values in registers and the per-block lists (last
+ * sub-block, groups, levels, the SvtAmdCoeffScanTu record).  What each step restates of EncodeQuantizedCoefficients (Codec/EbEntropyCoding.c:1172) is said where it
+ * stands. */
 #ifndef SVT_AMD_COEFFSCAN_DEVICE_H
 #define SVT_AMD_COEFFSCAN_DEVICE_H
 #include <stddef.h>

@@ -1,20 +1,23 @@
 /*
- * handoff_kernels.hip - the entropy hand-off pre-scan as the last stream-ordered stage of the picture chain (include/svt_hevc_amd.h "Entropy hand-off pre-scan":
- * svt_amd_entropy_handoff_launch, svt_amd_encdec_picture_entropy_handoff).  The same lists as svt_amd_coeff_scan_picture (coeffscan_kernels.hip),
- * byte for byte, from the records where they lie in HBM into DEVICE arrays of the caller - no synchronisation, no host memory, no working memory of the context:
- * what the kernels pass to one another lies in the caller's output arrays (the per-LCU counts are fields of SvtAmdCoeffScanLcu; the LCU's check status travels
- * in its pad[0] from the count kernel to the base kernel, which reads it and writes the 0 the contract asks for).  The per-LCU digest is coeffscan_device.h, the
- * text the blocking entry compiles too.
+ * handoff_kernels.hip - the entropy hand-off pre-scan (include/svt_hevc_amd.h "Entropy hand-off pre-scan"): one device chain behind two
+ * kinds of caller.  What EncodeQuantizedCoefficients (Codec/EbEntropyCoding.c:1172) does with a transform block before its first bin, for every transform block of
+ * a picture, from the records where they lie in HBM: per block 8 bytes, per coded sub-block 8, per non-zero coefficient 2, packed in LCU order.
+ *   svt_amd_entropy_handoff_launch, svt_amd_encdec_picture_entropy_handoff: the last stream-ordered stage of the picture chain, into DEVICE arrays of the caller - no
+ *                         synchronisation, no host memory, no working memory of the context.
+ *   svt_amd_coeff_scan_picture: the blocking call, into arrays carved from the context's scratch; it uploads host records, waits and downloads.
+ * What the kernels pass to one another lies in the output arrays (the per-LCU counts are fields of SvtAmdCoeffScanLcu; the LCU's check status travels in its pad[0]
+ * from the count kernel to the base kernel, which reads it and writes the 0 the contract asks for).  The per-LCU digest is coeffscan_device.h.
  *   k_handoff_lcu<false>  count: a 256-thread workgroup per LCU.  Validates the record, builds the block table, reads every coded sub-block (four 8-byte loads,
  *                         the 16 values in registers) for its significance map, and writes the complete SvtAmdCoeffScanLcu - every tu, groups, levels - and
  *                         the optional copies of the record heads.
- *   k_handoff_bases       one workgroup: exclusive sums of the counts over up to 16384 LCUs in chunks of 1024 -> group_base / level_base, the totals, the overflow
- *                         bits and the check sums in `head`.
+ *   k_handoff_bases       one workgroup: exclusive sums of the counts over the LCUs in chunks of 1024, as many as there are -> group_base / level_base, the
+ *                         totals, the overflow bits and the check sums in `head`.
  *   k_handoff_lcu<true>   write: a workgroup per LCU again; LCUs without a group, or whose lists both do not fit, leave at once.  Reads the sub-blocks a second
- *                         time, digests them as the blocking kernel does and stores group and levels at their picture offsets.
+ *                         time, digests them (signs, greater-1 flags, levels) and stores group and levels at their picture offsets.
  * No workgroup waits for another one: the order between the three kernels is stream order.  Every store is guarded by n_lcus and by the capacities, every load of a
  * unit or a coefficient by the validity rules (hf_unit_ok and the area rule below), whatever the records hold.
- * Bound: HBM - the s16 planes of the coded blocks are read twice (at most 2 * 3 * W * H bytes at 4:2:0) against the pools the blocking entry writes and reads.
+ * Bound: HBM - the s16 planes of the coded blocks are read twice (at most 2 * 3 * W * H bytes at 4:2:0); the output is a few percent of that and is written once,
+ * where it belongs.
  */
 #include <string.h>
 #include "coeffscan_device.h"
@@ -264,6 +267,19 @@ static int handoff_out_ok(const char *entry, const SvtAmdEntropyHandoffOut *out)
     return SVT_AMD_OK;
 }
 
+/* the one device chain of the hand-off: the scan tables once a device, then the three kernels on the context's stream.  What a caller has to check of its
+ * parameters it has checked, and the device is the context's. */
+static int handoff_run(SvtAmdContext *ctx, const HandoffArgs &A)
+{
+    SVT_AMD_TRY(rate_tables_once(ctx->device));
+    hipStream_t st = svt_amd_ctx_stream(ctx);
+    hipLaunchKernelGGL(k_handoff_lcu<false>, dim3(A.n_lcus), dim3(256), 0, st, A);
+    hipLaunchKernelGGL(k_handoff_bases, dim3(1), dim3(1024), 0, st, A);
+    hipLaunchKernelGGL(k_handoff_lcu<true>, dim3(A.n_lcus), dim3(256), 0, st, A);
+    HIP_TRY(hipGetLastError());
+    return SVT_AMD_OK;
+}
+
 static int handoff_queue(const char *entry, SvtAmdContext *ctx, const SvtAmdEntropyHandoffJob *job, const SvtAmdEntropyHandoffOut *out)
 {
     /* ---- everything is checked before anything is queued ---- */
@@ -281,18 +297,12 @@ static int handoff_queue(const char *entry, SvtAmdContext *ctx, const SvtAmdEntr
     SVT_AMD_TRY(handoff_out_ok(entry, out));
 
     HIP_TRY(hipSetDevice(ctx->device));
-    SVT_AMD_TRY(rate_tables_once(ctx->device));
     HandoffArgs A;
     A.works = (const uint8_t *)job->d_works, A.results = (const uint8_t *)job->d_results, A.work_stride = job->work_stride, A.result_stride = job->result_stride;
     A.n_lcus = job->n_lcus, A.group_capacity = job->group_capacity, A.level_capacity = job->level_capacity;
     A.head = out->head, A.lcus = out->lcus, A.groups = out->groups, A.levels = out->levels;
     A.work_heads = (uint32_t *)out->work_heads, A.result_heads = (uint32_t *)out->result_heads;
-    hipStream_t st = svt_amd_ctx_stream(ctx);
-    hipLaunchKernelGGL(k_handoff_lcu<false>, dim3(job->n_lcus), dim3(256), 0, st, A);
-    hipLaunchKernelGGL(k_handoff_bases, dim3(1), dim3(1024), 0, st, A);
-    hipLaunchKernelGGL(k_handoff_lcu<true>, dim3(job->n_lcus), dim3(256), 0, st, A);
-    HIP_TRY(hipGetLastError());
-    return SVT_AMD_OK;
+    return handoff_run(ctx, A);
 }
 
 extern "C" int svt_amd_entropy_handoff_launch(SvtAmdContext *ctx, const SvtAmdEntropyHandoffJob *job, const SvtAmdEntropyHandoffOut *out)
@@ -319,4 +329,59 @@ extern "C" int svt_amd_encdec_picture_entropy_handoff(SvtAmdContext *ctx, SvtAmd
         SVT_AMD_BAD("%s: no svt_amd_md_encode_picture* call that writes work records has completed on the picture object", __func__);
     job.n_lcus = (uint32_t)pic->nlcu, job.group_capacity = group_capacity, job.level_capacity = level_capacity;
     return handoff_queue(__func__, ctx, &job, out);
+}
+
+/* The blocking entry: the same chain into arrays carved from the context's scratch, and what is this entry's own - its parameter checks, the upload of host
+ * records, the downloads, the two waits and the return codes. */
+extern "C" int svt_amd_coeff_scan_picture(SvtAmdContext *ctx, const void *works, size_t work_stride, const void *results, size_t result_stride,
+                                          int device_arrays, int n_lcus, SvtAmdCoeffScanLcu *lcus, SvtAmdCoeffScanGroup *groups, uint32_t group_capacity,
+                                          uint16_t *levels, uint32_t level_capacity, uint32_t totals[2])
+{
+    if (!ctx || !works || !results || !lcus || !groups || !levels || !totals || n_lcus < 1 || work_stride < HF_WORK_HEAD || result_stride < HF_RESULT_MIN) {
+        svt_amd_set_error("svt_amd_coeff_scan_picture: bad parameter");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    if (device_arrays && ((uintptr_t)works % 4 || (uintptr_t)results % 4 || work_stride % 4 || result_stride % 4)) /* the kernels read the records in place, by words */
+        SVT_AMD_BAD("%s: device records at %p / %p, %zu / %zu bytes apart (4-byte aligned, strides multiples of 4)", __func__, works, results, work_stride, result_stride);
+    HIP_TRY(hipSetDevice(ctx->device));
+    const auto up256 = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t n = (size_t)n_lcus;
+    /* a capacity above the worst case can never overflow: the scratch holds no more than that */
+    const size_t gcap = group_capacity < n * CS_MAX_SUBS ? group_capacity : n * CS_MAX_SUBS, lcap = level_capacity < n * CS_MAX_LEVELS ? level_capacity : n * CS_MAX_LEVELS;
+    const size_t b_lcus = up256(n * sizeof(SvtAmdCoeffScanLcu)), b_groups = up256(gcap * sizeof(SvtAmdCoeffScanGroup)), b_levels = up256(lcap * sizeof(uint16_t));
+    const size_t b_works = device_arrays ? 0 : up256(n * HF_WORK_HEAD), b_results = device_arrays ? 0 : up256(n * HF_RESULT_MIN);
+    uint8_t *d = nullptr;
+    SVT_AMD_TRY(svt_amd_ctx_scratch(ctx, 256 + b_lcus + b_groups + b_levels + b_works + b_results, &d));
+    hipStream_t st = svt_amd_ctx_stream(ctx);
+    HandoffArgs A;
+    A.works = (const uint8_t *)works, A.results = (const uint8_t *)results, A.work_stride = work_stride, A.result_stride = result_stride;
+    A.n_lcus = (uint32_t)n_lcus, A.group_capacity = (uint32_t)gcap, A.level_capacity = (uint32_t)lcap;
+    A.head = (SvtAmdEntropyHandoffHead *)d, A.lcus = (SvtAmdCoeffScanLcu *)(d + 256);
+    A.groups = (SvtAmdCoeffScanGroup *)((uint8_t *)A.lcus + b_lcus), A.levels = (uint16_t *)((uint8_t *)A.groups + b_groups);
+    A.work_heads = nullptr, A.result_heads = nullptr;
+    if (!device_arrays) { /* only the heads travel: unit lists without the source samples, flags + coefficients without the reconstruction */
+        uint8_t *dw = (uint8_t *)A.levels + b_levels, *dr = dw + b_works;
+        HIP_TRY(hipMemcpy2DAsync(dw, HF_WORK_HEAD, works, work_stride, HF_WORK_HEAD, n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpy2DAsync(dr, HF_RESULT_MIN, results, result_stride, HF_RESULT_MIN, n, hipMemcpyHostToDevice, st));
+        A.works = dw, A.results = dr, A.work_stride = HF_WORK_HEAD, A.result_stride = HF_RESULT_MIN;
+    }
+    SVT_AMD_TRY(handoff_run(ctx, A));
+    SvtAmdEntropyHandoffHead head;
+    HIP_TRY(hipMemcpyAsync(&head, A.head, sizeof(head), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(lcus, A.lcus, n * sizeof(SvtAmdCoeffScanLcu), hipMemcpyDeviceToHost, st));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
+    totals[0] = head.groups, totals[1] = head.levels;
+    if (head.bad_lcus || head.bad_units) /* lcus[] says which: a refused LCU or unit reads "nothing to code" */
+        SVT_AMD_BAD("%s: malformed records: %u bad LCUs (first %d), %u bad units (first in LCU %d); no list is returned", __func__, head.bad_lcus, (int)head.first_bad_lcu,
+                    head.bad_units, (int)head.first_bad_unit_lcu);
+    if (head.overflow) {
+        svt_amd_set_error("svt_amd_coeff_scan_picture: %u groups / %u levels do not fit the capacities %u / %u", totals[0], totals[1], group_capacity, level_capacity);
+        return SVT_AMD_ERR_RESOURCES;
+    }
+    if (totals[0])
+        HIP_TRY(hipMemcpyAsync(groups, A.groups, (size_t)totals[0] * sizeof(SvtAmdCoeffScanGroup), hipMemcpyDeviceToHost, st));
+    if (totals[1])
+        HIP_TRY(hipMemcpyAsync(levels, A.levels, (size_t)totals[1] * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(svt_amd_ctx_sync(ctx));
+    return SVT_AMD_OK;
 }

@@ -77,3 +77,33 @@ def head_copies(works, results):
 def exclusive_sums(counts):
     c = np.asarray(counts, np.int64)
     return np.concatenate([[0], np.cumsum(c)[:-1]])
+
+
+MALFORMED_CHECK = {"bad_lcus": 2, "first_bad_lcu": 2, "bad_units": 5, "first_bad_unit_lcu": 7}
+
+
+def malformed(works, results):
+    """copies of a picture's records (20 LCUs or more, two units or more each) with seven of them rewritten, each refused unit with cbf 1 in all three planes, so that
+    a forgotten guard would scan it: (works, results, the rewritten LCUs); check() of them is MALFORMED_CHECK"""
+    works, results = works.copy(), results.copy()
+    assert len(works) >= 20 and int(works["num_cus"].min()) >= 2
+
+    def unit(k, c, **fields):
+        for f, v in fields.items():
+            works[k]["cu"][c][f] = v
+        results[k]["cu"][c]["cbf"], results[k]["cu"][c]["nz"] = 1, 3
+
+    works[2]["num_cus"] = 65
+    works[5]["num_cus"] = 255
+    unit(7, 0, size=12)
+    unit(9, 1, x=60, y=0, size=16)
+    unit(11, 0, y=4)
+    works[13]["num_cus"] = 2                                                   # a 64x64 unit in a two-unit LCU
+    unit(13, 0, x=0, y=0, size=64)
+    works[13]["cu"][1]["x"], works[13]["cu"][1]["y"], works[13]["cu"][1]["size"] = 0, 0, 8
+    works[16]["num_cus"] = 1                                                   # a lone 64x64 unit at (32, 0)
+    unit(16, 0, x=32, y=0, size=64)
+    for c in range(1, 5):
+        results[16]["cu"][c]["cbf"] = 1
+    assert check(works) == MALFORMED_CHECK
+    return works, results, (2, 5, 7, 9, 11, 13, 16)

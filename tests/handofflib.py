@@ -1,15 +1,19 @@
 """ctypes views, numpy layouts and prototypes of the stream-ordered entropy hand-off (include/svt_hevc_amd.h "Entropy hand-off pre-scan":
-svt_amd_entropy_handoff_bytes, svt_amd_entropy_handoff_launch, svt_amd_encdec_picture_entropy_handoff); tests/test_handoff_abi.py holds them against the header.
-Outputs: one launch's output arrays in device memory, each with sentinel bytes behind it."""
+svt_amd_entropy_handoff_bytes, svt_amd_entropy_handoff_launch, svt_amd_encdec_picture_entropy_handoff) and of the blocking svt_amd_coeff_scan_picture;
+tests/test_handoff_abi.py holds them against the header.  Outputs: one launch's output arrays in device memory, each with sentinel bytes behind it.  scan_picture:
+the blocking entry into host arrays, sentinel behind the capacities."""
 import ctypes as C
 
 import numpy as np
 
 import svtlib as S
-from pa_batch_util import DeviceBuffer, is_sentinel, round_up
+from pa_batch_util import SENTINEL, DeviceBuffer, is_sentinel, round_up
 
 ENTRY = "svt_amd_entropy_handoff_launch"
 PICTURE_ENTRY = "svt_amd_encdec_picture_entropy_handoff"
+BLOCKING_ENTRY = "svt_amd_coeff_scan_picture"
+ERR_RESOURCES = -2                 # SVT_AMD_ERR_RESOURCES
+SLACK = 64                         # sentinel elements the host lists of scan_picture keep behind their capacity
 HEAD, LCUS, GROUPS, LEVELS, WORK_HEADS, RESULT_HEADS = range(6)   # SVT_AMD_ENTROPY_HANDOFF_*
 MAX_LCUS = 16384                   # SVT_AMD_MDCTL_MAX_LCUS
 MAX_GROUPS, MAX_LEVELS = 384, 6144  # an LCU's worst case
@@ -97,3 +101,15 @@ class Outputs:
 
     def free(self):
         self.dev.free()
+
+
+def scan_picture(lib, ctx, works, work_stride, results, result_stride, device_arrays, n, gcap, lcap):
+    """svt_amd_coeff_scan_picture on record arrays given by address, into host arrays filled with the sentinel, the lists SLACK elements longer than the
+    capacities the call is told: (return code, {lcus, groups, levels: the whole arrays; totals})"""
+    lcus = np.full(n * LCU_BYTES, SENTINEL, np.uint8).view(S.COEFF_SCAN_LCU_DTYPE)
+    groups = np.full(8 * (gcap + SLACK), SENTINEL, np.uint8).view(S.COEFF_SCAN_GROUP_DTYPE)
+    levels = np.full(2 * (lcap + SLACK), SENTINEL, np.uint8).view(np.uint16)
+    totals = (u32 * 2)(NONE, NONE)
+    rc = lib.svt_amd_coeff_scan_picture(ctx, vp(works), work_stride, vp(results), result_stride, device_arrays, n, lcus.ctypes.data, groups.ctypes.data, gcap,
+                                        levels.ctypes.data, lcap, C.byref(totals))
+    return rc, {"lcus": lcus, "groups": groups, "levels": levels, "totals": (int(totals[0]), int(totals[1]))}

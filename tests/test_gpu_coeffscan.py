@@ -1,12 +1,18 @@
-"""Entropy hand-off pre-scan on the device (svt-hevc_amd/csrc/coeffscan_kernels.hip) through the C-ABI: svt_amd_coeff_scan_picture against the
-CPU checker (pinned on the reference's coder by tests/test_oracle_coeffscan.py) - block records, sub-block groups and levels bit for bit - on the
-recorded encodes, on a seeded 4K picture from device arrays, and, where oracle/_ref travels with the snapshot, straight against the reference's coder."""
+"""Entropy hand-off pre-scan on the device (svt-hevc_amd/csrc/handoff_kernels.hip) through the C-ABI: the blocking svt_amd_coeff_scan_picture against
+the CPU checker (pinned on the reference's coder by tests/test_oracle_coeffscan.py) - block records, sub-block groups and levels bit for bit - on the
+recorded encodes, on a seeded 4K picture from device arrays, and, where oracle/_ref travels with the snapshot, straight against the reference's coder.  Then
+what is the blocking entry's own around the kernels it shares with the stream-ordered launch (tests/test_gpu_entropy_handoff.py): host against device arrays,
+capacities that do not fit, malformed records, more LCUs than a launch takes."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import handoff_numpy as N
+import handofflib as H
 import svtlib as S
+import test_gpu_entropy_handoff as E
+from pa_batch_util import is_sentinel, make_context, refused
 from test_oracle_encodepass_golden import ALL, is16, load_case
 
 pytestmark = pytest.mark.gpu
@@ -177,3 +183,133 @@ def test_device_records_code_the_reference_bytes(product, gpu_ctx):
             assert blocks > 20 and np.array_equal(sa, sb), (name, blocks)
         finally:
             ref.svt_ref_cabac_free(a), ref.svt_ref_cabac_free(b)
+
+
+# ---- what is the blocking entry's own: the kernels are the launch's (tests/test_gpu_entropy_handoff.py) ------------------------------------------------------
+
+def host_bytes(a, stride, at=1):
+    """the records of `a` as a byte array in which they lie `stride` bytes apart from the odd offset `at` on: (keep-alive, address)"""
+    rows = np.ascontiguousarray(a).view(np.uint8).reshape(len(a), -1)
+    buf = np.zeros(at + len(a) * stride, np.uint8)
+    buf[at:].reshape(len(a), stride)[:, :rows.shape[1]] = rows
+    return buf, buf.ctypes.data + at
+
+
+def lists_untouched(got, groups=0, levels=0):
+    """nothing at or behind `groups` / `levels` elements of the host lists was written"""
+    return is_sentinel(got["groups"][groups:]) and is_sentinel(got["levels"][levels:])
+
+
+@pytest.mark.parametrize("name", ["i_noise_200x136_m6", "sao_p_noise_320x256_m8"])
+def test_host_and_device_arrays_give_the_same_bytes(product, oracle, gpu_ctx, name):
+    """the same records as device arrays and as host arrays - these at an odd address and an odd stride, which only an upload can take - at the worst-case capacities
+    and at the exact fit: the checker's lists, the same bytes either way, nothing at or behind the totals written"""
+    lib = H.declare(product)
+    works, results, exp = E.fixture(oracle, name)
+    n, totals = len(works), E.totals_of(exp)
+    assert (name, n) == ("i_noise_200x136_m6", 12) or (name, totals) == ("sao_p_noise_320x256_m8", (16001, 159356))
+    recs = E.Records(lib, gpu_ctx, works, results)
+    ws, rs = works.dtype.itemsize + 3, results.dtype.itemsize + 1
+    keep_w, h_works = host_bytes(works, ws)
+    keep_r, h_results = host_bytes(results, rs)
+    try:
+        for gcap, lcap in ((H.MAX_GROUPS * n, H.MAX_LEVELS * n), totals):
+            rc, dev = H.scan_picture(lib, gpu_ctx, recs.d_works, recs.work_stride, recs.d_results, recs.result_stride, 1, n, gcap, lcap)
+            assert rc == 0, lib.svt_amd_last_error()
+            rc, host = H.scan_picture(lib, gpu_ctx, h_works, ws, h_results, rs, 0, n, gcap, lcap)
+            assert rc == 0, lib.svt_amd_last_error()
+            for got in (dev, host):
+                assert got["totals"] == totals, (name, gcap)
+                E.compare((name, gcap), exp, got)
+                assert lists_untouched(got, *totals), (name, gcap)
+            assert dev["lcus"].tobytes() == host["lcus"].tobytes() and dev["groups"].tobytes() == host["groups"].tobytes(), (name, gcap)
+            assert dev["levels"].tobytes() == host["levels"].tobytes(), (name, gcap)
+    finally:
+        recs.free()
+    del keep_w, keep_r
+
+
+def test_capacities_that_do_not_fit_are_refused_with_the_need(product, oracle, gpu_ctx):
+    """groups one short, levels one short, both 0, from device and from host arrays: SVT_AMD_ERR_RESOURCES, totals what the picture needs, lcus[] the fitting
+    run's, neither host list touched"""
+    lib = H.declare(product)
+    name = "sao_p_noise_320x256_m8"
+    works, results, exp = E.fixture(oracle, name)
+    n, totals = len(works), E.totals_of(exp)
+    assert totals == (16001, 159356)
+    recs = E.Records(lib, gpu_ctx, works, results)
+    arrays = ((recs.d_works, recs.work_stride, recs.d_results, recs.result_stride, 1), (works.ctypes.data, works.dtype.itemsize, results.ctypes.data, results.dtype.itemsize, 0))
+    try:
+        rc, fit = H.scan_picture(lib, gpu_ctx, *arrays[0], n, *totals)
+        assert rc == 0, lib.svt_amd_last_error()
+        E.compare(name, exp, fit)
+        for gcap, lcap in ((totals[0] - 1, totals[1]), (totals[0], totals[1] - 1), (0, 0)):
+            for a in arrays:
+                rc, got = H.scan_picture(lib, gpu_ctx, *a, n, gcap, lcap)
+                assert rc == H.ERR_RESOURCES, (gcap, lcap, rc, lib.svt_amd_last_error())
+                assert lib.svt_amd_last_error() == b"svt_amd_coeff_scan_picture: %d groups / %d levels do not fit the capacities %d / %d" % (totals + (gcap, lcap))
+                assert got["totals"] == totals and got["lcus"].tobytes() == fit["lcus"].tobytes(), (gcap, lcap)
+                assert lists_untouched(got), (gcap, lcap)
+    finally:
+        recs.free()
+
+
+def test_malformed_records_are_refused_and_the_context_goes_on(product, oracle, gpu_ctx):
+    """the seven rewritten records of the launch's test (handoff_numpy.malformed; the launch runs them safely), as device arrays with 128 KB of the test's own memory
+    around each and as host arrays - these at capacities of 0, since malformed records are judged before the capacities: SVT_AMD_ERR_BAD_PARAM with both counts and
+    both first LCUs in the text, totals and lcus[] what the checker gives on records in which the refused slots are not coded, neither host list touched; then the
+    good records on the same context"""
+    lib = H.declare(product)
+    name = "sao_p_noise_320x256_m8"
+    good_w, good_r, exp_good = E.fixture(oracle, name)
+    works, results, rewritten = N.malformed(good_w, good_r)
+    n = len(works)
+    exp = E.expected_of(oracle, *N.sanitized(works, results))
+    totals = E.totals_of(exp)
+    recs = E.Records(lib, gpu_ctx, works, results, margin=E.MARGIN)
+    try:
+        for a, gcap, lcap in (((recs.d_works, recs.work_stride, recs.d_results, recs.result_stride, 1), H.MAX_GROUPS * n, H.MAX_LEVELS * n),
+                              ((works.ctypes.data, works.dtype.itemsize, results.ctypes.data, results.dtype.itemsize, 0), 0, 0)):
+            rc, got = H.scan_picture(lib, gpu_ctx, *a, n, gcap, lcap)
+            refused(lib, rc, H.BLOCKING_ENTRY, a[4])
+            assert b"2 bad LCUs (first 2), 5 bad units (first in LCU 7)" in lib.svt_amd_last_error(), lib.svt_amd_last_error()
+            assert got["totals"] == totals, a[4]
+            E.compare(name, exp, got, lists=(False, False))
+            for k in rewritten:
+                assert (got["lcus"][k]["tu"][:, N.bad_slots(works[k])] == E.NOTHING).all(), k
+            assert lists_untouched(got), a[4]
+        good_totals = E.totals_of(exp_good)
+        rc, got = H.scan_picture(lib, gpu_ctx, good_w.ctypes.data, good_w.dtype.itemsize, good_r.ctypes.data, good_r.dtype.itemsize, 0, n, *good_totals)
+        assert rc == 0, lib.svt_amd_last_error()
+        assert got["totals"] == good_totals and lists_untouched(got, *good_totals)
+        E.compare(name, exp_good, got)
+    finally:
+        recs.free()
+
+
+@pytest.mark.parametrize("n", [1025, H.MAX_LCUS + 1])
+def test_more_lcus_than_a_launch_takes(product, oracle, n):
+    """the 12 records of one picture repeated as host arrays at the smallest strides, at the exact fit, in a context of its own (its scratch grows with the picture):
+    bases = exclusive sums of the checker's counts, the totals, the lists of the first, the last and every 997th LCU; the launch entry still refuses 16385 LCUs"""
+    lib = H.declare(product)
+    works, results, exp12 = E.fixture(oracle, "i_noise_200x136_m6")
+    assert len(works) == 12
+    idx = np.arange(n) % 12
+    exp = [exp12[k] for k in idx]
+    totals = E.totals_of(exp)
+    wb = np.ascontiguousarray(works.view(np.uint8).reshape(12, -1)[:, :H.WORK_HEAD_BYTES][idx])
+    rb = np.ascontiguousarray(results.view(np.uint8).reshape(12, -1)[:, :H.RESULT_MIN_BYTES][idx])
+    if n > H.MAX_LCUS:                          # refused on the host, before the job's arrays or the outputs are read: host memory stands for them
+        out = H.Out()
+        out.head, out.lcus, out.groups, out.levels = (wb.ctypes.data + 64 * i for i in range(4))
+        job = H.job(wb.ctypes.data, H.WORK_HEAD_BYTES, rb.ctypes.data, H.RESULT_MIN_BYTES, n, *totals)
+    ctx = make_context(lib, 640, 384, 1)
+    try:
+        if n > H.MAX_LCUS:
+            refused(lib, lib.svt_amd_entropy_handoff_launch(ctx, C.byref(job), C.byref(out)), H.ENTRY, n)
+        rc, got = H.scan_picture(lib, ctx, wb.ctypes.data, H.WORK_HEAD_BYTES, rb.ctypes.data, H.RESULT_MIN_BYTES, 0, n, *totals)
+        assert rc == 0, lib.svt_amd_last_error()
+        assert got["totals"] == totals and lists_untouched(got, *totals), n
+        E.compare(n, exp, got, sorted(set(range(0, n, 997)) | {0, n - 1}))
+    finally:
+        lib.svt_amd_context_destroy(ctx)

@@ -1,6 +1,6 @@
 """CPU-only: the C-ABI of the stream-ordered entropy hand-off (include/svt_hevc_amd.h "Entropy hand-off pre-scan") - the entries are exported, the header and the
 ctypes views (tests/handofflib.py) agree on sizes and on every offset, svt_amd_entropy_handoff_bytes is the documented arithmetic and the checks that need no
-device answer without one."""
+device answer without one - those of the blocking svt_amd_coeff_scan_picture, which runs the same kernels, among them."""
 import ctypes as C
 
 import numpy as np
@@ -95,6 +95,30 @@ def test_bad_calls_are_refused_without_a_device(lib):
     refused(lib, lib.svt_amd_encdec_picture_entropy_handoff(None, fake, 16, 16, C.byref(o)), H.PICTURE_ENTRY, "no context")
     refused(lib, lib.svt_amd_encdec_picture_entropy_handoff(fake, None, 16, 16, C.byref(o)), H.PICTURE_ENTRY, "no picture object")
     refused(lib, lib.svt_amd_encdec_picture_entropy_handoff(fake, fake, 16, 16, None), H.PICTURE_ENTRY, "no outputs")
+
+
+def test_the_blocking_entry_refuses_bad_calls_without_a_device(lib):
+    """the first check keeps its text, whichever parameter it meets; device arrays the kernels could not read by words are refused in a text that names the entry"""
+    fake = C.create_string_buffer(1 << 16)        # stands for the context, the records and the outputs: refused before any of them is read
+    base = (C.addressof(fake) + 63) & ~63
+    good = dict(ctx=base, works=base + 64, work_stride=S.LCU_WORK_DTYPE.itemsize, results=base + 128, result_stride=S.LCU_RESULT_DTYPE.itemsize, device_arrays=0,
+                n_lcus=4, lcus=base + 192, groups=base + 256, group_capacity=16, levels=base + 320, level_capacity=16, totals=C.cast(base + 384, C.POINTER(H.u32 * 2)))
+
+    def call(**kw):
+        return lib.svt_amd_coeff_scan_picture(*{**good, **kw}.values())
+
+    bad = [(p, {p: None}) for p in ("ctx", "works", "results", "lcus", "groups", "levels", "totals")]
+    bad += [("no LCU", dict(n_lcus=0)), ("work stride below the unit list", dict(work_stride=H.WORK_HEAD_BYTES - 1)),
+            ("result stride below the coefficients", dict(result_stride=H.RESULT_MIN_BYTES - 1))]
+    for device_arrays in (0, 1):
+        for tag, kw in bad:
+            rc = call(device_arrays=device_arrays, **kw)
+            assert rc == -1 and lib.svt_amd_last_error() == b"svt_amd_coeff_scan_picture: bad parameter", (tag, rc, lib.svt_amd_last_error())
+    for tag, kw in (("works at an odd byte", dict(works=base + 65)), ("results at an odd byte", dict(results=base + 129)), ("results off a word", dict(results=base + 130)),
+                    ("work stride no multiple of 4", dict(work_stride=S.LCU_WORK_DTYPE.itemsize + 2)),
+                    ("result stride no multiple of 4", dict(result_stride=S.LCU_RESULT_DTYPE.itemsize + 2))):
+        refused(lib, call(device_arrays=1, **kw), H.BLOCKING_ENTRY, tag)
+        assert b"4-byte aligned" in lib.svt_amd_last_error(), tag
 
 
 def works_of(units):

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Measurement of the stream-ordered entropy hand-off (svt_amd_entropy_handoff_launch) beside the blocking entry it follows (svt_amd_coeff_scan_picture), on the seeded
+"""Measurement of the stream-ordered entropy hand-off (svt_amd_entropy_handoff_launch) beside the blocking caller of the same kernels (svt_amd_coeff_scan_picture), on the seeded
 3840x2160 records of tests/test_gpu_coeffscan.py::random_records at coefficient densities 0.5 and 0.9, resident in HBM.
 Per density, after two warm-up calls of each kind, 21 rounds that alternate the two entries in one process:
   launch    host time of the call (perf_counter around it, the lane idle before) and device time of its three kernels (svt_amd_timer_begin / _end around the call),
             exact-fit capacities;
-  blocking  time from call to return on the same device arrays, worst-case capacities as its callers pass them, and the bytes it downloads.
-The launch's lists are compared with the blocking entry's (byte for byte) before a number is printed.  Algorithmic bytes of the launch, from the shapes: the
+  blocking  time from call to return on the same device arrays, worst-case capacities as its callers pass them, the bytes it downloads and the context scratch
+            it asks for (from its carve: head, lcus and the two lists at the worst case; not measured).
+Both entries run one chain of kernels; their lists are compared (byte for byte) before a number is printed, which holds the two host halves against each other.  Algorithmic bytes of the launch, from the shapes: the
 coefficients of the coded blocks once, the record heads (1584 + 768 bytes an LCU), and the outputs (head, lcus, head copies, used lists); the share is of the
 8 TB/s HBM peak, with the 6.3 TB/s copy rate of DESIGN 3.16 beside it.  Hand-off bytes: what a caller downloads per picture with the launch, against the full records.
 Reported, not gated.  usage: entropy_handoff_time.py [output.txt]"""
@@ -95,19 +96,20 @@ def measure(lib, ctx, density, seed, lines):
     outputs = 32 + n * H.LCU_BYTES + heads_in + 8 * ng + 2 * nl
     algorithmic = coeff + heads_in + outputs
     download = outputs
-    blocking_download = 8 + n * H.LCU_BYTES + 8 * ng + 2 * nl
+    blocking_download = 32 + n * H.LCU_BYTES + 8 * ng + 2 * nl
+    blocking_scratch = 256 + H.round_up(n * H.LCU_BYTES) + n * (H.MAX_GROUPS * 8 + H.MAX_LEVELS * 2)
     full_records = n * (ws + rs)
     med = float(np.median(dev))
     lines += [
-        "density %.1f (seed %d): %d LCUs, %d units, %d groups, %d levels; lists byte-identical to the blocking entry's: %s" % (
+        "density %.1f (seed %d): %d LCUs, %d units, %d groups, %d levels; the two callers of the one chain return byte-identical lists: %s" % (
             density, seed, n, int(works["num_cus"].sum()), ng, nl, identical),
         "  launch    host time of the call   median %7.1f us  min %7.1f  max %7.1f" % (1e6 * float(np.median(host)), 1e6 * min(host), 1e6 * max(host)),
         "  launch    device time (3 kernels) median %7.1f us  min %7.1f  max %7.1f   (%d rounds after %d warm-ups)" % (1e6 * med, 1e6 * min(dev), 1e6 * max(dev), ROUNDS, WARMUP),
         "  launch    algorithmic bytes %.2f MB (coded coefficients once %.2f, heads in %.2f, outputs %.2f) -> %.2f TB/s = %.0f %% of the 8 TB/s HBM peak "
         "(%.0f %% of the 6.3 TB/s copy rate)" % (algorithmic / 1e6, coeff / 1e6, heads_in / 1e6, outputs / 1e6, algorithmic / med / 1e12, 100 * algorithmic / med / HBM_PEAK,
                                                 100 * algorithmic / med / COPY_RATE),
-        "  blocking  call to return          median %7.1f us  min %7.1f  max %7.1f   downloads %.2f MB (lcus + used lists), works in %.1f MB of context scratch" % (
-            1e6 * float(np.median(blk)), 1e6 * min(blk), 1e6 * max(blk), blocking_download / 1e6, 2 * n * (H.MAX_GROUPS * 8 + H.MAX_LEVELS * 2) / 1e6),
+        "  blocking  call to return          median %7.1f us  min %7.1f  max %7.1f   downloads %.2f MB (head, lcus, used lists), works in %.1f MB of context scratch" % (
+            1e6 * float(np.median(blk)), 1e6 * min(blk), 1e6 * max(blk), blocking_download / 1e6, blocking_scratch / 1e6),
         "  hand-off  a caller downloads %.2f MB a picture (head 32 B, lcus %.2f, head copies %.2f, used lists %.2f) against %.1f MB of full 8-bit records (%.1f MB at 10 bit)"
         % (download / 1e6, n * H.LCU_BYTES / 1e6, heads_in / 1e6, (8 * ng + 2 * nl) / 1e6, full_records / 1e6,
            n * (S.LCU_WORK16_DTYPE.itemsize + S.LCU_RESULT16_DTYPE.itemsize) / 1e6)]
