@@ -2622,6 +2622,50 @@ SVT_AMD_API int svt_amd_debug_md_flights(int *in_flight, int *workgroups_held, i
 SVT_AMD_API int svt_amd_md_picture_warmup(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic);
 /* measurement: dynamic LDS bytes a workgroup of k_md_encode_picture<inter, sample bytes> is launched with (the whole LCU state: one workgroup per CU) */
 SVT_AMD_API int svt_amd_debug_md_kernel_lds_bytes(int inter, int bytes_per_sample);
+/* test: the motion-vector candidate lists of the P / B unit loop (md_kernels.hip: the register form of GenerateL0L1AmvpMergeLists + ChooseMVPIdx_V2) on single
+ * units, a lane per job - the __device__ functions the unit loop calls, on inputs no recorded picture holds (tests/test_gpu_md_lists.py against the reference's
+ * own outputs, tests/golden/mvlists_seeded.npz).  Nothing of the product calls it. */
+typedef struct SvtAmdMdListNb {            /* a spatial neighbour: MvUnit_t + whether the derivation may use it (the caller derives that)                     */
+    int16_t mv[2][2];                      /* [list]{x, y}                                                                                                    */
+    uint8_t dir, avail, pad[2];            /* 0 list 0, 1 list 1, 2 both                                                                                      */
+} SvtAmdMdListNb;
+typedef struct SvtAmdMdListJob {
+    uint16_t width, height;                /* the picture, luma                                                                                               */
+    uint16_t ox, oy;                       /* the unit's origin in the picture (a multiple of size)                                                           */
+    uint8_t size;                          /* 8, 16, 32, 64                                                                                                   */
+    uint8_t slice_type;                    /* 0 B, 1 P                                                                                                        */
+    uint8_t colocated_pu_ref_list, is_low_delay;
+    uint8_t has_field;                     /* a co-located motion field exists (SvtAmdMdInter.tmvp_enable)                                                    */
+    uint8_t total_merge;                   /* the merge candidates wanted: 2, 3 or 5 (md_nmm)                                                                 */
+    uint8_t tile_left, tile_top, tile_right; /* the LCU's tile-edge flags: what `avail` was derived with; the device and the CPU checker do not read them    */
+    uint8_t me_dir;                        /* the motion-estimation candidate: direction ...                                                                  */
+    uint16_t pool[2];                      /* the co-located field of this LCU and of the LCU to its right: indices into the pool of SvtAmdTmvpLcu records    */
+    int16_t me_mv[2][2];                   /* ... and vectors [list]{x, y}                                                                                    */
+    uint8_t pad[2];
+    uint64_t picture_number, ref_poc[2], colocated_poc;
+    SvtAmdMdListNb nb[5];                  /* A0, A1, B0, B1, B2                                                                                              */
+    uint8_t pad2[4];
+} SvtAmdMdListJob;
+typedef struct SvtAmdMdListOut {
+    int16_t amvp[2][2][2];                 /* [list][index]{x, y}: entries below amvp_count[list] are meaningful                                             */
+    uint8_t amvp_count[2];
+    uint8_t merge_count;
+    uint8_t mvp_idx[2];                    /* of the lists me_dir uses                                                                                        */
+    uint8_t merge_dir[5];
+    int16_t merge_mv[5][2][2];             /* [candidate][list]{x, y}: the lists merge_dir uses are meaningful                                                */
+    int16_t cand_mv[2][2];                 /* me_mv after ClipMV, of the lists me_dir uses                                                                    */
+    int16_t mvp[2][2];                     /* the chosen predictors                                                                                           */
+    uint8_t pad[14];
+} SvtAmdMdListOut;
+#ifdef __cplusplus
+static_assert(sizeof(SvtAmdMdListNb) == 12 && sizeof(SvtAmdMdListJob) == 128 && sizeof(SvtAmdMdListOut) == 96, "tests mirror these layouts as numpy dtypes");
+#else
+_Static_assert(sizeof(SvtAmdMdListNb) == 12 && sizeof(SvtAmdMdListJob) == 128 && sizeof(SvtAmdMdListOut) == 96, "tests mirror these layouts as numpy dtypes");
+#endif
+/* d_jobs, d_pool, d_outs: DEVICE arrays (n jobs, the pool the jobs index, n outs).  One launch on the context's stream; the caller synchronises.  A NULL pointer or
+ * n == 0: SVT_AMD_ERR_BAD_PARAM, nothing queued.  Every byte of outs [0, n) is written, nothing behind them.  The jobs live on the device, so their pool indices are
+ * NOT checked: both of every job must lie inside d_pool (also where has_field is 0). */
+SVT_AMD_API int svt_amd_debug_md_lists_batch(SvtAmdContext *ctx, const SvtAmdMdListJob *d_jobs, const SvtAmdTmvpLcu *d_pool, SvtAmdMdListOut *d_outs, uint32_t n);
 /* measurement: LDS bytes (static + dynamic) a workgroup of the motion-estimation kernel of `phase` (0 = HME, 1 = search) is launched with for a job with
  * these controls; params == NULL: what the last svt_amd_me_* launch of the process requested (compiler's static size + the launcher's pool) */
 SVT_AMD_API int svt_amd_debug_me_kernel_lds_bytes(const SvtAmdMeParams *params, int phase);

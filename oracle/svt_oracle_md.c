@@ -570,3 +570,42 @@ int svt_oracle_md_picture(const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus, con
 
 /* md_mv_bits (md_logic.h) for the table test (tests/test_oracle_md.py::test_mv_bit_table) */
 uint32_t svt_oracle_md_mv_bits(int dx, int dy) { return md_mv_bits(dx, dy); }
+
+/* The motion-vector candidate lists of single units (tests/test_oracle_mvlists.py): md_amvp_merge_lists, then md_choose_mvp for the job's motion-estimation candidate -
+ * md_logic.h's text and nothing else - on jobs whose reference outputs tests/golden/mvlists_seeded.npz holds (oracle/ref_harness_mvlists.c). */
+void svt_oracle_md_lists(const SvtAmdMdListJob *jobs, const SvtAmdTmvpLcu *pool, SvtAmdMdListOut *outs, int n)
+{
+    for (int i = 0; i < n; i++) {
+        const SvtAmdMdListJob *J = &jobs[i];
+        SvtAmdMdListOut *o = &outs[i];
+        SvtAmdMdPicture P;
+        SvtAmdMdInter X;
+        SvtAmdTmvpLcu field[2];
+        MdMvUnit nb[5];
+        MdInterLists T;
+        MdCand c;
+        memset(&P, 0, sizeof(P)), memset(&X, 0, sizeof(X)), memset(&T, 0, sizeof(T)), memset(&c, 0, sizeof(c)), memset(o, 0, sizeof(*o));
+        P.width = J->width, P.height = J->height, P.slice_type = J->slice_type;
+        X.picture_number = J->picture_number, X.ref_poc[0] = J->ref_poc[0], X.ref_poc[1] = J->ref_poc[1], X.colocated_poc = J->colocated_poc;
+        X.colocated_pu_ref_list = J->colocated_pu_ref_list, X.is_low_delay = J->is_low_delay, X.tmvp_enable = J->has_field;
+        field[0] = pool[J->pool[0]], field[1] = pool[J->pool[1]];
+        memcpy(nb, J->nb, sizeof(nb));
+        md_amvp_merge_lists(&P, &X, nb, J->has_field ? field : NULL, J->ox, J->oy, J->size, J->total_merge, &T);
+        c.type = MD_INTER, c.dir = J->me_dir;
+        for (int l = 0; l < 2; l++)
+            c.mv[l].x = J->me_mv[l][0], c.mv[l].y = J->me_mv[l][1];
+        md_choose_mvp(&P, J->ox, J->oy, &T, &c);
+        for (int l = 0; l < 2; l++) {
+            for (int k = 0; k < 2; k++)
+                o->amvp[l][k][0] = T.amvp[l][k].x, o->amvp[l][k][1] = T.amvp[l][k].y;
+            o->amvp_count[l] = T.amvp_count[l], o->mvp_idx[l] = c.mvp_idx[l];
+            o->cand_mv[l][0] = c.mv[l].x, o->cand_mv[l][1] = c.mv[l].y, o->mvp[l][0] = c.mvp[l].x, o->mvp[l][1] = c.mvp[l].y;
+        }
+        o->merge_count = T.merge_count;
+        for (int k = 0; k < 5; k++) {
+            o->merge_dir[k] = T.merge[k].dir;
+            for (int l = 0; l < 2; l++)
+                o->merge_mv[k][l][0] = T.merge[k].mv[l].x, o->merge_mv[k][l][1] = T.merge[k].mv[l].y;
+        }
+    }
+}

@@ -3782,6 +3782,93 @@ extern "C" int svt_amd_debug_md_kernel_lds_bytes(int inter, int bytes_per_sample
     return (int)(inter ? sizeof(MdShared<true>) : sizeof(MdShared<false>)) + (int)sizeof(MdPictureDev);
 }
 
+/* test (svt_amd_debug_md_lists_batch): the unit loop's motion-vector lists on single units, a lane per job.  The lists, the temporal candidate, the scale factors and the
+ * predictor choice are md_units_inter's own __device__ functions (md_list_consts, md_tmvp_position, md_amvp_one_list, md_temporal_mvp_dev, md_merge_list_regs,
+ * md_choose_mvp_one) on the neighbours packed as wave 1 / wave 2 pack them; what is written here is only what carries a job to them and their results out.  The two
+ * motion-field records of a job (this LCU, the LCU to its right) are gathered into a private pair: the functions index them as one array. */
+static_assert(sizeof(SvtAmdMdListNb) == sizeof(MdMvUnit) && offsetof(SvtAmdMdListNb, dir) == offsetof(MdMvUnit, dir) && offsetof(SvtAmdMdListNb, avail) == offsetof(MdMvUnit, avail),
+              "a job's neighbour is an MdMvUnit");
+#define MD_NB_VALS(w0, w1, w2) w0[MD_A0], w1[MD_A0], w2[MD_A0], w0[MD_A1], w1[MD_A1], w2[MD_A1], w0[MD_B0], w1[MD_B0], w2[MD_B0], w0[MD_B1], w1[MD_B1], w2[MD_B1], w0[MD_B2], w1[MD_B2], w2[MD_B2]
+__global__ __launch_bounds__(64) void k_md_lists_batch(const SvtAmdMdListJob *__restrict__ jobs, const SvtAmdTmvpLcu *__restrict__ pool, SvtAmdMdListOut *__restrict__ outs, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= n)
+        return;
+    const SvtAmdMdListJob J = jobs[i];
+    SvtAmdMdPicture P; /* (the functions read width, height and slice_type of it) */
+    P.width = J.width, P.height = J.height, P.slice_type = J.slice_type;
+    SvtAmdMdInter X;
+    __builtin_memset(&X, 0, sizeof(X));
+    X.picture_number = J.picture_number, X.ref_poc[0] = J.ref_poc[0], X.ref_poc[1] = J.ref_poc[1], X.colocated_poc = J.colocated_poc;
+    X.colocated_pu_ref_list = J.colocated_pu_ref_list, X.is_low_delay = J.is_low_delay, X.tmvp_enable = J.has_field;
+    SvtAmdTmvpLcu field[2];
+    field[0] = pool[J.pool[0]], field[1] = pool[J.pool[1]];
+    const SvtAmdTmvpLcu *map = J.has_field ? field : nullptr;
+    const int x0 = J.ox, y0 = J.oy, N = J.size, totalMerge = J.total_merge;
+    const MdListConsts K = md_list_consts(P, X);
+    MdTmvpPos tp;
+    tp.bottom_right = 0, tp.lcu_offset = 0, tp.unit = 0, tp.pad = 0;
+    if (map)
+        tp = md_tmvp_position(&P, map, x0, y0, N);
+    uint32_t w0[5], w1[5], w2[5]; /* mv[0], mv[1], dir | avail << 8: zero when the neighbour is not available */
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        const SvtAmdMdListNb &u = J.nb[k];
+        MdMv m0, m1;
+        m0.x = u.mv[0][0], m0.y = u.mv[0][1], m1.x = u.mv[1][0], m1.y = u.mv[1][1];
+        w0[k] = u.avail ? md_pack_mv(m0) : 0u, w1[k] = u.avail ? md_pack_mv(m1) : 0u, w2[k] = u.avail ? (uint32_t)u.dir | 0x100u : 0u;
+    }
+    SvtAmdMdListOut o;
+    __builtin_memset(&o, 0, sizeof(o));
+    MdMv tv[2];
+    bool tok[2] = {false, false};
+    MdMv cmv[2];
+#pragma unroll
+    for (int l = 0; l < 2; l++) {
+        uint32_t pa0, pa1;
+        const int num = md_amvp_one_list(K, X, MD_NB_VALS(w0, w1, w2), map, tp, l, &pa0, &pa1);
+        MdMv al[3];
+        al[0] = md_unpack_mv(pa0), al[1] = md_unpack_mv(pa1), al[2] = al[1];
+        o.amvp[l][0][0] = al[0].x, o.amvp[l][0][1] = al[0].y, o.amvp[l][1][0] = al[1].x, o.amvp[l][1][1] = al[1].y;
+        o.amvp_count[l] = (uint8_t)num;
+        cmv[l].x = J.me_mv[l][0], cmv[l].y = J.me_mv[l][1];
+        if (J.me_dir == MD_BI || J.me_dir == l) {
+            MdMv mvp;
+            mvp.x = mvp.y = 0;
+            md_choose_mvp_one(P, (uint32_t)x0, (uint32_t)y0, al, num, &cmv[l], &o.mvp_idx[l], &mvp);
+            o.cand_mv[l][0] = cmv[l].x, o.cand_mv[l][1] = cmv[l].y, o.mvp[l][0] = mvp.x, o.mvp[l][1] = mvp.y;
+        }
+        tv[l].x = tv[l].y = 0;
+        if (map && (l == 0 || K.bslice)) {
+            tok[l] = md_temporal_mvp_dev(X, map, tp, l, &tv[l]);
+            if (!tok[l])
+                tv[l].x = tv[l].y = 0;
+        }
+    }
+    MdMerge5 mg;
+    md_merge_list_regs(K, MD_NB_VALS(w0, w1, w2), map != nullptr, tok[0], md_pack_mv(tv[0]), md_pack_mv(tv[1]), totalMerge, mg);
+    o.merge_count = (uint8_t)totalMerge; /* (the list is always filled up to the count wanted) */
+#pragma unroll
+    for (int k = 0; k < 5; k++) {
+        const MdMv v0 = md_unpack_mv(mg.g0[k]), v1 = md_unpack_mv(mg.g1[k]);
+        o.merge_dir[k] = (uint8_t)mg.gd[k];
+        o.merge_mv[k][0][0] = v0.x, o.merge_mv[k][0][1] = v0.y, o.merge_mv[k][1][0] = v1.x, o.merge_mv[k][1][1] = v1.y;
+    }
+    outs[i] = o;
+}
+#undef MD_NB_VALS
+extern "C" int svt_amd_debug_md_lists_batch(SvtAmdContext *ctx, const SvtAmdMdListJob *d_jobs, const SvtAmdTmvpLcu *d_pool, SvtAmdMdListOut *d_outs, uint32_t n)
+{
+    if (!ctx || !d_jobs || !d_pool || !d_outs || n == 0) {
+        svt_amd_set_error("svt_amd_debug_md_lists_batch: a context, three device arrays and at least one job");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(k_md_lists_batch, dim3((n + 63u) / 64u), dim3(64), 0, svt_amd_ctx_stream(ctx), d_jobs, d_pool, d_outs, n);
+    HIP_TRY(hipGetLastError());
+    return SVT_AMD_OK;
+}
+
 /* debug: the finer marks of the mode-decision kernel (MD_SUB): 16 sums per LCU, collected together with svt_amd_debug_md_profile's (which switches the collection on) */
 extern "C" int svt_amd_debug_md_profile_sub(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, unsigned long long *out)
 {
