@@ -2331,7 +2331,9 @@ SVT_AMD_API void svt_amd_BiPredClipping16bit(uint32_t puWidth, uint32_t puHeight
  * quantiser, no delta-QP tools, 8-bit:
  *   I pictures (PICT_FULL84_DEPTH_MODE), closed-loop intra (intraMdOpenLoopFlag == 0) = the I pictures of encMode 8..10 at every
  *   resolution and of encMode 7 in 4K (BASELINE configs[0], and the I pictures of configs[1] / [2] / [3]);
- *   P / B pictures (SvtAmdMdInter below) with open-loop intra candidates, sub-sample motion, unrestricted motion vectors, the AMVP
+ *   P / B pictures (SvtAmdMdInter below) with open-loop intra candidates, with or - 8-bit pictures only - without sub-sample search
+ *   (use_subpel 0: the candidates of the motion estimation rounded to whole samples, the merge candidates predicted at the rounded
+ *   position, prediction through the reference's interpolation-free path), unrestricted motion vectors, the AMVP
  *   table generated in the mode decision and partial-frequency level 0 / 1 whose LCUs are all decided by ModeDecisionLcu (no
  *   branch-and-depth-pillar LCUs) = the non-reference B pictures of encMode 7..8 (half the pictures of a random-access encode).
  * svt_amd_md_picture_supported() says so; everything else stays with the reference code.
@@ -2398,7 +2400,7 @@ typedef struct SvtAmdMdInter {
     uint64_t colocated_poc;                /* refPOC of the co-located picture (list pcs->colocatedPuRefList; list 0 in P pictures) */
     uint8_t colocated_pu_ref_list, is_low_delay; /* pcs->colocatedPuRefList, ->isLowDelay                                        */
     uint8_t tmvp_enable;                   /* !ppcs->disableTmvpFlag && the co-located reference object's tmvpEnableFlag         */
-    uint8_t use_subpel;                    /* ppcs->useSubpelFlag                                                                */
+    uint8_t use_subpel;                    /* ppcs->useSubpelFlag (0: encMode 9 at the 4K input class, layers above 0; 8-bit calls) */
     uint8_t unrestricted_mv;               /* scs->staticConfig.unrestrictedMotionVector                                         */
     uint8_t generate_amvp_table_md;        /* ModeDecisionContext_t.generateAmvpTableMd                                          */
     uint8_t extra_injection;               /* .amvpInjection | .unipred3x3Injection | .bipred3x3Injection (encMode 0..1)         */
@@ -2469,6 +2471,9 @@ SVT_AMD_API int svt_amd_md_encode_picture_inter16(SvtAmdContext *ctx, SvtAmdEncD
                                                   const SvtAmdMeLcuResult *me, int me_slot, const SvtAmdTmvpLcu *tmvp, SvtAmdMdLcuOut *md_out,
                                                   SvtAmdLcuWork16 *works, SvtAmdLcuResult16 *results);
 SVT_AMD_API int svt_amd_md_picture_supported_inter(const SvtAmdMdPicture *P, const SvtAmdMdInter *X);
+/* ... by the 16-bit entry (svt_amd_md_encode_picture_inter16, the launch on a 16-bit picture object): the same pictures except those coded without sub-sample search
+ * (use_subpel 0), whose prediction from 10-bit reference pictures (UnpackUniPredRef10Bit / UnpackBiPredRef10Bit) is a path of its own this revision does not hold */
+SVT_AMD_API int svt_amd_md_picture_supported_inter16(const SvtAmdMdPicture *P, const SvtAmdMdInter *X);
 /* 1 when every one of the n LCUs is decided by ModeDecisionLcu with luma-only candidates (the per-LCU half of the two checks above) */
 SVT_AMD_API int svt_amd_md_lcus_supported(const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus, int n);
 /* Binds a DEVICE array of the picture object's LCU count (svt_amd_md_controls_batch_launch's output, or any array of that layout) as the controls of the NEXT

@@ -1198,7 +1198,11 @@ static int md_picture_level_ok(SequenceControlSet_t *scs, PictureControlSet_t *p
     const int inter = pcs->sliceType != EB_I_PICTURE;
     if (inter)
         svt_md_fill_inter(X, scs, pcs, md);
-    return !(tools || (!inter && g_md_skip_intra) || !(inter ? svt_amd_md_picture_supported_inter(P, X) : svt_amd_md_picture_supported(P)));
+    /* (a 10-bit P / B picture asks the 16-bit entry's predicate: one coded without sub-sample search - useSubpelFlag 0, encMode 9 at the 4K input class, layers above 0 -
+     * is the device's in 8 bits and the reference code's in 10) */
+    const int wide = scs->staticConfig.encoderBitDepth > EB_8BIT;
+    return !(tools || (!inter && g_md_skip_intra) ||
+             !(inter ? (wide ? svt_amd_md_picture_supported_inter16(P, X) : svt_amd_md_picture_supported_inter(P, X)) : svt_amd_md_picture_supported(P)));
 }
 static void md_picture(SvtAmdContext *lane, EpPictureEntry *e, SequenceControlSet_t *scs, PictureControlSet_t *pcs, ModeDecisionContext_t *md)
 {

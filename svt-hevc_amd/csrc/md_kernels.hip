@@ -847,7 +847,16 @@ __device__ __noinline__ void md_window_from_plane(const uint8_t *plane, int stri
  * a function per size (the 16x16 and 8x8 blocks most units have need a fraction of the registers of the 32x32 form: no callee-saved register, so no private-segment traffic
  * around the call), everything passed BY VALUE (a candidate passed by reference went through the private segment: a memory round trip of ~1.5 K clocks per call on the unit
  * chain).  mv0 / mv1: x | y << 16.  td: the tile's first sample in the destination, pitch in samples. */
-template <int TN, bool CHROMA>
+/* IFREE: the picture is coded without sub-sample search (SvtAmdMdInter.use_subpel == 0) - Inter2Nx2NPuPredictionInterpolationFree (Codec/EbInterPrediction.c:57) with
+ * roundMvToInteger: the vector goes to whole samples first (RoundMvOnTheFly, :46: what the reference does to a merge candidate's vector, Codec/EbProductCodingLoop.c:2009 /
+ * :4239; the candidates of the motion estimation were rounded at their injection and stay what they are), then UniPredIFreeRef8Bit / BiPredIFreeRef8Bit
+ * (Codec/EbAvcStyleMcp.c:172 / :321) COPY whole samples - luma from the interpolation-free position, chroma from the NEAREST sample instead of through the 4-tap filter - and
+ * average the two lists' copies, (a + b + 1) / 2.  The copy and the average are ep_mc8_tile at the fraction 0, passed as a constant: with the identity taps its two passes
+ * reduce to sample s exactly (luma: 64 (64 (s - 128)) + 8192 * 64 + 2048 >> 12 = s; chroma: 64 (64 s) + 2048 >> 12 = s), and BiPredClipping of two such intermediates to
+ * ((64 a - 8192) + (64 b - 8192) + 16448) >> 7 = (64 (a + b) + 64) >> 7 = (a + b + 1) >> 1 (chroma: (64 a + 64 b + 64) >> 7, the same).  The window is the filter's
+ * (the staged samples, or md_window_from_plane's clamped addressing): the copy reads its middle.  A template parameter: the instances of pictures with sub-sample search
+ * hold none of this. */
+template <int TN, bool CHROMA, bool IFREE = false>
 __device__ MD_LEAF_CALL void md_predict_tile(const EpRefPlanes *refs, int abs_x, int abs_y, int inter_dir, uint32_t mv0, uint32_t mv1, int p, int lane, EpMcScratch<uint8_t> *Mp,
                                              uint8_t *td, int pitch, int tx0, int ty0, const EpRefWindows *RW, const EpRefWindowsC *RWC)
 {
@@ -862,11 +871,12 @@ __device__ MD_LEAF_CALL void md_predict_tile(const EpRefPlanes *refs, int abs_x,
             continue;
         MD_TR(40);
         const EpRefPlanes R = refs[l]; /* one read of the whole record */
-        const uint32_t mvw = l ? mv1 : mv0;
+        const uint32_t mvw = IFREE ? inter_mv_round2(l ? mv1 : mv0) : (l ? mv1 : mv0);
         const int mvx = (int)(int16_t)(mvw & 0xFFFF), mvy = (int)(int16_t)(mvw >> 16);
         const int qx = INTER_POS_CLAMP(abs_x, R.originX, mvx, R.width), qy = INTER_POS_CLAMP(abs_y, R.originY, mvy, R.height);
-        const int ix = inter_pos_int(qx, CHROMA) + tx0, iy = inter_pos_int(qy, CHROMA) + ty0;
-        const int fx = __builtin_amdgcn_readfirstlane(inter_pos_frac(qx, CHROMA)), fy = __builtin_amdgcn_readfirstlane(inter_pos_frac(qy, CHROMA));
+        const int ix = (IFREE ? (CHROMA ? inter_ifree_chroma(qx) : inter_ifree_luma_x(qx, qy)) : inter_pos_int(qx, CHROMA)) + tx0;
+        const int iy = (IFREE ? (CHROMA ? inter_ifree_chroma(qy) : inter_ifree_luma_y(qx, qy)) : inter_pos_int(qy, CHROMA)) + ty0;
+        const int fx = IFREE ? 0 : __builtin_amdgcn_readfirstlane(inter_pos_frac(qx, CHROMA)), fy = IFREE ? 0 : __builtin_amdgcn_readfirstlane(inter_pos_frac(qy, CHROMA));
         MD_TR(41);
         /* where the filter reads the window: a staged one where it lies (EpRefWindows / EpRefWindowsC), any other from the scratch copy the fall-back below makes - ONE
          * instance of the filter per tile size either way (two were ~1 K instructions more per function, in a loop whose code does not fit the instruction cache) */
@@ -898,6 +908,7 @@ __device__ MD_LEAF_CALL void md_predict_tile(const EpRefPlanes *refs, int abs_x,
 }
 /* ... of plane p (0 luma: N x N, 1 / 2 chroma: N/2 x N/2) of a candidate (direction, vectors x | y << 16) into dst with pitch = the block's width; tile_first / tile_step
  * let several waves share the four 32x32 tiles of a 64x64 unit's luma */
+template <bool IFREE = false>
 __device__ __forceinline__ void md_predict_inter_plane(const EpRefPlanes *refs, int dir, uint32_t mv0, uint32_t mv1, int x0, int y0, int N, int p, int lane, EpMcScratch<uint8_t> &mc,
                                                        uint8_t *dst, int tile_first, int tile_step, const EpRefWindows *rw, const EpRefWindowsC *rwc = nullptr)
 {
@@ -907,27 +918,28 @@ __device__ __forceinline__ void md_predict_inter_plane(const EpRefPlanes *refs, 
         case 64:
             for (int ti = tile_first; ti < 4; ti += tile_step) {
                 const int ty0 = (ti >> 1) << 5, tx0 = (ti & 1) << 5;
-                md_predict_tile<32, false>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst + ty0 * pitch + tx0, pitch, tx0, ty0, rw, rwc);
+                md_predict_tile<32, false, IFREE>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst + ty0 * pitch + tx0, pitch, tx0, ty0, rw, rwc);
             }
             break;
-        case 32: md_predict_tile<32, false>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
-        case 16: md_predict_tile<16, false>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
-        default: md_predict_tile<8, false>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
+        case 32: md_predict_tile<32, false, IFREE>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
+        case 16: md_predict_tile<16, false, IFREE>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
+        default: md_predict_tile<8, false, IFREE>(refs, x0, y0, dir, mv0, mv1, 0, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
         }
     } else {
         switch (n) {
-        case 32: md_predict_tile<32, true>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
-        case 16: md_predict_tile<16, true>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
-        case 8: md_predict_tile<8, true>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
-        default: md_predict_tile<4, true>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
+        case 32: md_predict_tile<32, true, IFREE>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
+        case 16: md_predict_tile<16, true, IFREE>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
+        case 8: md_predict_tile<8, true, IFREE>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
+        default: md_predict_tile<4, true, IFREE>(refs, x0, y0, dir, mv0, mv1, p, lane, &mc, dst, pitch, 0, 0, rw, rwc); break;
         }
     }
 }
 __device__ __forceinline__ uint32_t md_pack_mv(MdMv v) { return (uint32_t)(uint16_t)v.x | ((uint32_t)(uint16_t)v.y << 16); }
+template <bool IFREE = false>
 __device__ __forceinline__ void md_predict_inter_plane(const EpRefPlanes *refs, const MdCand &c, int x0, int y0, int N, int p, int lane, EpMcScratch<uint8_t> &mc, uint8_t *dst,
                                                        int tile_first, int tile_step, const EpRefWindows *rw, const EpRefWindowsC *rwc = nullptr)
 {
-    md_predict_inter_plane(refs, (int)c.dir, md_pack_mv(c.mv[0]), md_pack_mv(c.mv[1]), x0, y0, N, p, lane, mc, dst, tile_first, tile_step, rw, rwc);
+    md_predict_inter_plane<IFREE>(refs, (int)c.dir, md_pack_mv(c.mv[0]), md_pack_mv(c.mv[1]), x0, y0, N, p, lane, mc, dst, tile_first, tile_step, rw, rwc);
 }
 /* IntraPredictionOl's chroma references of the unit (Codec/EbIntraPrediction.c:5065 UpdateChromaNeighborSamplesArrayOL): SOURCE chroma samples around the
  * unit, mid-grey beyond the picture.  By one wave; ref[p] in pu_predict's layout (n = N/2). */
@@ -1270,7 +1282,9 @@ static_assert(sizeof(MdCand) == 32, "a candidate is eight words: type | intra_mo
  * thirty tests of a flag per unit and wave, and their branches between the stages, are not on the product's path */
 /* CFULL: the LCU is CHROMA_MODE_FULL (chroma in both loops of every candidate) - an instance of the loop per chroma mode, chosen per LCU: the luma-only LCUs' instance carries
  * none of the chroma tasks' code between its stages */
-template <bool PROF, bool CFULL>
+/* IFREE: the picture is coded without sub-sample search - the motion-estimation candidates are rounded to whole samples at their injection, every prediction is
+ * md_predict_tile's interpolation-free form (which rounds the merge candidates' vectors on the fly); the candidates, the records and the encode pass keep the merge vectors */
+template <bool PROF, bool CFULL, bool IFREE = false>
 __device__ __forceinline__ void md_units_inter(const MdPictureDev &D, int lcu, int lcu_x, int lcu_y, MdShared<true> &M)
 {
     const bool prof_on = PROF && __builtin_amdgcn_readfirstlane((int)(D.prof != nullptr)) != 0;
@@ -1375,7 +1389,8 @@ __device__ __forceinline__ void md_units_inter(const MdPictureDev &D, int lcu, i
                     if (!(dir == MD_BI && Ph.depth_mode == 0 && Lh.lcu_md_mode == 10)) {
                         keep = true;
                         cw.w[0] = MD_INTER | (1u << 24); /* type | dist_ready << 24 */
-                        cw.w[1] = me_dist, cw.w[2] = (uint32_t)dir, cw.w[4] = me_v0, cw.w[5] = me_v1;
+                        /* RoundMv (Codec/EbModeDecision.c:200, called at :481): all four components, BEFORE the predictor choice below */
+                        cw.w[1] = me_dist, cw.w[2] = (uint32_t)dir, cw.w[4] = IFREE ? inter_mv_round2(me_v0) : me_v0, cw.w[5] = IFREE ? inter_mv_round2(me_v1) : me_v1;
                     }
                 }
 #pragma unroll
@@ -1547,7 +1562,7 @@ __device__ __forceinline__ void md_units_inter(const MdPictureDev &D, int lcu, i
                     const int sl = (int)md_rl((uint32_t)slot, ci), n = luma ? N : N >> 1, lgn = luma ? lgN : lgN - 1;
                     uint8_t *pr = luma ? (sl >= 0 ? M.V.cpred[sl] : M.V.wpred[wave]) : (sl >= 0 ? M.V.cpred_c[sl][pl - 1] : M.V.wpred_c(wave, pl - 1));
                     MD_TR(21);
-                    md_predict_inter_plane(M.V.refs, (int)(cw2 & 0xFF), md_rl(cw.w[4], ci), md_rl(cw.w[5], ci), x0, y0, N, pl, lane, M.V.mc[wave], pr, tiled64 && luma ? ti : 0,
+                    md_predict_inter_plane<IFREE>(M.V.refs, (int)(cw2 & 0xFF), md_rl(cw.w[4], ci), md_rl(cw.w[5], ci), x0, y0, N, pl, lane, M.V.mc[wave], pr, tiled64 && luma ? ti : 0,
                                            tiled64 && luma ? 4 : 1, &M.V.rw, &M.V.rwc);
                     MD_TR(22);
                     MD_SUB(7);
@@ -1694,7 +1709,7 @@ __device__ __forceinline__ void md_units_inter(const MdPictureDev &D, int lcu, i
                 if (!kept_pred(pci)) {
                     fresh64 = true;
                     if (wave == f)
-                        md_predict_inter_plane(M.V.refs, (int)(md_rl(cw.w[2], pci) & 0xFF), md_rl(cw.w[4], pci), md_rl(cw.w[5], pci), x0, y0, N, 0, lane, M.V.mc[wave], M.V.wpred[f], 0, 1,
+                        md_predict_inter_plane<IFREE>(M.V.refs, (int)(md_rl(cw.w[2], pci) & 0xFF), md_rl(cw.w[4], pci), md_rl(cw.w[5], pci), x0, y0, N, 0, lane, M.V.mc[wave], M.V.wpred[f], 0, 1,
                                                &M.V.rw, &M.V.rwc);
                 }
             }
@@ -1726,7 +1741,7 @@ __device__ __forceinline__ void md_units_inter(const MdPictureDev &D, int lcu, i
                 if (kept_pred(pci))
                     pred = M.V.cpred[(int)md_rl((uint32_t)slot, pci)]; /* the fast loop's prediction of this candidate is still there */
                 else
-                    md_predict_inter_plane(M.V.refs, (int)(md_rl(cw.w[2], pci) & 0xFF), md_rl(cw.w[4], pci), md_rl(cw.w[5], pci), x0, y0, N, 0, lane, M.V.mc[wave], pred, 0, 1, &M.V.rw, &M.V.rwc);
+                    md_predict_inter_plane<IFREE>(M.V.refs, (int)(md_rl(cw.w[2], pci) & 0xFF), md_rl(cw.w[4], pci), md_rl(cw.w[5], pci), x0, y0, N, 0, lane, M.V.mc[wave], pred, 0, 1, &M.V.rw, &M.V.rwc);
             } else {
                 md_intra_block((int)((p0 >> 8) & 0xFF), N, lgN, M.ref, 1, lane, nullptr, 0, pred);
                 EP_WAVE_SYNC();
@@ -1765,7 +1780,7 @@ __device__ __forceinline__ void md_units_inter(const MdPictureDev &D, int lcu, i
                     for (int pl = pl0; pl < pl1; pl++) {
                         uint8_t *pw = pw0 + pl * 1024;
                         if (cdtype == MD_INTER) {
-                            md_predict_inter_plane(M.V.refs, (int)(md_rl(cw.w[2], ci) & 0xFF), md_rl(cw.w[4], ci), md_rl(cw.w[5], ci), x0, y0, N, 1 + pl, lane, M.V.mc[wave], pw, 0, 1, &M.V.rw,
+                            md_predict_inter_plane<IFREE>(M.V.refs, (int)(md_rl(cw.w[2], ci) & 0xFF), md_rl(cw.w[4], ci), md_rl(cw.w[5], ci), x0, y0, N, 1 + pl, lane, M.V.mc[wave], pw, 0, 1, &M.V.rw,
                                                    &M.V.rwc);
                         } else {
                             md_intra_block(cdmode, Cn, lgc, M.V.refc[pl], 0, lane, nullptr, 0, pw);
@@ -2081,7 +2096,7 @@ __device__ __forceinline__ void md_lcu_inputs(const MdPictureDev &D, const SvtAm
 }
 
 /* ModeDecisionLcu of one LCU (its inputs are in LDS: md_lcu_inputs): on return M.S holds the decisions, the picture's maps the LCU's final neighbour state */
-template <bool INTER, bool PROF>
+template <bool INTER, bool PROF, bool IFREE = false>
 __device__ __forceinline__ void md_lcu(const MdPictureDev &D, const SvtAmdMdPicture &Pg, int lcu, int lcu_x, int lcu_y, MdShared<INTER> &M)
 {
     /* the picture's controls as the unit loop reads them: the copies md_lcu_inputs left beside the LCU in LDS, not the records in HBM (a unit's scalar stages read dozens
@@ -2163,9 +2178,9 @@ __device__ __forceinline__ void md_lcu(const MdPictureDev &D, const SvtAmdMdPict
     /* ---- the LCU's units, one after the other: P / B pictures run md_units_inter, the loop below is the I pictures' alone ---- */
     if constexpr (INTER) {
         if (M.lcu.chroma_encode_mode == 1)
-            md_units_inter<PROF, true>(D, lcu, lcu_x, lcu_y, M);
+            md_units_inter<PROF, true, IFREE>(D, lcu, lcu_x, lcu_y, M);
         else
-            md_units_inter<PROF, false>(D, lcu, lcu_x, lcu_y, M);
+            md_units_inter<PROF, false, IFREE>(D, lcu, lcu_x, lcu_y, M);
     } else {
         for (;;) {
             MD_TR(10);
@@ -2605,6 +2620,8 @@ __device__ __forceinline__ void md_lcu(const MdPictureDev &D, const SvtAmdMdPict
 /* what EncodePass will do with the inter units of the LCU's final tree (Codec/EbCodingLoop.c:3838-3882): AMVP units as they are; merge units by the
  * merge / skip costs completed with chroma (AddChromaEncDec, Codec/EbProductCodingLoop.c:4158-4349: chroma prediction + chroma full loop +
  * MergeSkipFullCost), a wave per unit.  -> M.V.ep_kind[leaf] */
+/* (IFREE: the chroma of the winning merge candidate is predicted at the rounded position, Codec/EbProductCodingLoop.c:4239) */
+template <bool IFREE = false>
 __device__ __forceinline__ void md_ep_kinds(const MdPictureDev &D, const SvtAmdMdPicture &Pg, MdShared<true> &M, int lcu_x, int lcu_y)
 {
     const SvtAmdMdPicture &P = M.pic;
@@ -2642,7 +2659,7 @@ __device__ __forceinline__ void md_ep_kinds(const MdPictureDev &D, const SvtAmdM
         cd.type = MD_INTER, cd.dir = u.inter_dir, cd.mv[0] = u.mv[0], cd.mv[1] = u.mv[1];
         for (int p = 0; p < 2; p++) {
             uint8_t *pred = M.V.wpred[wave] + p * 1024;
-            md_predict_inter_plane(M.V.refs, cd, lcu_x + st.x, lcu_y + st.y, N, 1 + p, lane, M.V.mc[wave], pred, 0, 1, &M.V.rw, &M.V.rwc);
+            md_predict_inter_plane<IFREE>(M.V.refs, cd, lcu_x + st.x, lcu_y + st.y, N, 1 + p, lane, M.V.mc[wave], pred, 0, 1, &M.V.rw, &M.V.rwc);
             for (int tu = 0; tu < ntu; tu++) {
                 const int ox = ntu == 1 ? 0 : (tu & 1) << 4, oy = ntu == 1 ? 0 : (tu >> 1) << 4;
                 uint32_t nz;
@@ -2733,7 +2750,7 @@ __device__ __forceinline__ void md_make_work(const MdPictureDev &D, const SvtAmd
  * time, for work that is off the picture's critical path and runs 2040 LCUs wide in ~1.5 ms when it is launched on its own).
  * The picture's descriptor (MdPictureDev) comes by POINTER and is copied to LDS once per workgroup: passed by value, its run-time-indexed arrays (src[1 + p], mref[l])
  * forced the whole record into the private segment (110 scratch stores in the prologue, a memory round trip at every use). */
-template <bool INTER, typename T, bool PROF>
+template <bool INTER, typename T, bool PROF, bool IFREE = false>
 __global__ __launch_bounds__(256) void k_md_picture(const MdPictureDev *__restrict__ Dp, typename EpTypes<T>::Work *__restrict__ works, int nlcu, int wl, unsigned *ticket,
                                                     unsigned *md_done, const unsigned *__restrict__ order, unsigned epoch)
 {
@@ -2791,7 +2808,7 @@ __global__ __launch_bounds__(256) void k_md_picture(const MdPictureDev *__restri
             g_md_trace_on = D.trace && lcu == D.trace_lcu && D.trace_unit == 0;
         __syncthreads();
 #endif
-        md_lcu<INTER, PROF>(D, P, lcu, lx * 64, ly * 64, M);
+        md_lcu<INTER, PROF, IFREE>(D, P, lcu, lx * 64, ly * 64, M);
         __syncthreads();
 #ifdef MD_TRACE
         if (D.trace && lcu == D.trace_lcu) {
@@ -2824,7 +2841,7 @@ __global__ __launch_bounds__(256) void k_md_picture(const MdPictureDev *__restri
         }
         if (D.encode) {
             if constexpr (INTER)
-                md_ep_kinds(D, P, M, lx * 64, ly * 64);
+                md_ep_kinds<IFREE>(D, P, M, lx * 64, ly * 64);
             md_make_work<INTER, T>(D, P, M, lx * 64, ly * 64, works[lcu]);
             if (PROF && D.prof && threadIdx.x == 0)
                 D.prof[16 * (size_t)lcu + 10] += __builtin_readcyclecounter() - c_md; /* merge / skip decisions with chroma + the work record */
@@ -2846,6 +2863,7 @@ static_assert(sizeof(MdShared<true>) + MD_LDS_BESIDE <= 160 * 1024 && sizeof(MdS
 /* ---- host side ------------------------------------------------------------------------------------------------------------- */
 extern "C" int svt_amd_md_picture_supported(const SvtAmdMdPicture *P) { return P ? md_picture_supported(P) : 0; }
 extern "C" int svt_amd_md_picture_supported_inter(const SvtAmdMdPicture *P, const SvtAmdMdInter *X) { return P && X ? md_picture_supported_inter(P, X) : 0; }
+extern "C" int svt_amd_md_picture_supported_inter16(const SvtAmdMdPicture *P, const SvtAmdMdInter *X) { return P && X ? md_picture_supported_inter16(P, X) : 0; }
 extern "C" int svt_amd_md_lcus_supported(const SvtAmdMdPicture *P, const SvtAmdMdLcu *lcus, int n)
 {
     if (!P || !lcus)
@@ -2880,6 +2898,7 @@ struct SvtAmdMdState {
     MdPictureDev *d_D;             /* the descriptor the kernel reads (d, copied per call) */
     hipEvent_t ev_k0, ev_k1, ev_k2; /* around the last launch of k_md_picture on the call's stream (svt_amd_debug_md_kernel_ms), and behind the encode pass that follows it */
     int grid;                      /* its workgroups */
+    bool ifree;                    /* the call's picture is a P / B picture coded without sub-sample search (!SvtAmdMdInter.use_subpel): md_launch_kernel's instance */
     /* P / B pictures */
     SvtAmdMdInter *d_X;
     SvtAmdMeLcuResult *d_me;
@@ -3155,7 +3174,13 @@ static MdWidths md_launch_widths(int wl, int hl, int tiles, int n_active)
 static int md_launch_kernel(hipStream_t st, SvtAmdEncDecPicture *pic, SvtAmdMdState *m, bool inter, uint32_t bps, int grid, int n_active, int wl, const unsigned *d_order)
 {
     const bool profiled = m->d.prof != nullptr;
-    if (inter && bps == 1 && !profiled)
+    if (inter && bps == 1 && m->ifree && !profiled) /* a picture coded without sub-sample search: the interpolation-free instances (8-bit pictures only, the entries see to it) */
+        hipLaunchKernelGGL((k_md_picture<true, uint8_t, false, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter && bps == 1 && m->ifree)
+        hipLaunchKernelGGL((k_md_picture<true, uint8_t, true, true>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
+                           m->d_md_done, d_order, pic->epoch);
+    else if (inter && bps == 1 && !profiled)
         hipLaunchKernelGGL((k_md_picture<true, uint8_t, false>), dim3((unsigned)grid), dim3(256), 0, st, m->d_D, (SvtAmdLcuWork *)m->d_works, n_active, wl, m->d_md_ticket,
                            m->d_md_done, d_order, pic->epoch);
     else if (inter && bps == 1)
@@ -3317,6 +3342,11 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
         return SVT_AMD_ERR_BAD_PARAM;
     if ((X ? !md_picture_supported_inter(P, X) : !md_picture_supported(P)) || P->width != pic->d.width || P->height != pic->d.height || pic->d.bps != bps) {
         svt_amd_set_error("svt_amd_md_encode_picture: picture outside what this revision covers (svt_amd_md_picture_supported[_inter]), or not the picture object's size / sample width");
+        return SVT_AMD_ERR_BAD_PARAM;
+    }
+    if (X && bps != 1 && !md_picture_supported_inter16(P, X)) {
+        svt_amd_set_error("svt_amd_md_encode_picture_inter16: use_subpel 0 - a picture coded without sub-sample search predicts through the reference's interpolation-free path, "
+                          "which this revision covers for 8-bit pictures only");
         return SVT_AMD_ERR_BAD_PARAM;
     }
     if (X && (!pic->has_cost || !pic->has_ref[0] || (P->slice_type == 0 && !pic->has_ref[1]) || (X->tmvp_enable && !tmvp && !bound_tmvp))) {
@@ -3504,6 +3534,7 @@ static int md_encode_picture(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const
     /* the inputs first (a call that waits for its place holds no CU and no copy engine meanwhile) */
     HIP_TRY(hipStreamSynchronize(st));
     const int grid = flight.acquire(ctx->device, md_wg_budget(ctx->device), width.lone, width.wide, width.narrow, (int)P->temporal_layer);
+    m->ifree = X && !X->use_subpel;
     if ((rc = md_queue_picture(ctx, pic, m, rec, X != nullptr, grid, n_active, d_order, tiles)) != 0)
         return rc;
     if (timing) {
@@ -3604,6 +3635,9 @@ extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDec
     if ((X ? !md_picture_supported_inter(P, X) : !md_picture_supported(P)) || P->width != pic->d.width || P->height != pic->d.height)
         MDL_BAD("picture outside what this revision covers (svt_amd_md_picture_supported[_inter]), or not the picture object's size");
     const uint32_t bps = pic->d.bps;
+    if (X && bps != 1 && !md_picture_supported_inter16(P, X))
+        MDL_BAD("use_subpel 0 on a 16-bit picture object - a picture coded without sub-sample search predicts through the reference's interpolation-free path, which this "
+                "revision covers for 8-bit pictures only");
     if ((job->src_pitch_y * bps) % 4 || (job->src_pitch_c * bps) % 4)
         MDL_BAD("source pitches of %u / %u samples of %u bytes: rows have to start 4-byte aligned", job->src_pitch_y, job->src_pitch_c, bps);
     const int n = pic->nlcu, wl = (pic->d.width + 63) / 64, hl = (pic->d.height + 63) / 64;
@@ -3686,6 +3720,7 @@ extern "C" int svt_amd_md_encode_picture_launch(SvtAmdContext *ctx, SvtAmdEncDec
         std::lock_guard<std::mutex> l(g_flight_mu);
         flights = g_flight_dev[ctx->device & 63].flights;
     }
+    m->ifree = X && !X->use_subpel;
     if ((rc = md_queue_picture(ctx, pic, m, rec, X != nullptr, flights == 0 ? width.lone : width.narrow, n, pic->d_sync + 1 + n, (int)job->tiles)) != 0)
         return rc;
     pic->md_works_whole = m->d.encode != 0; /* at queue time: the tail and the motion field queue behind this launch in stream order */

@@ -13,6 +13,7 @@
 #define SVT_AMD_MD_LOGIC_H
 #include <stdint.h>
 #include "../../include/svt_hevc_amd.h"
+#include "inter_position.h" /* inter_mv_round: the whole-sample rounding of pictures coded without sub-sample search */
 
 #ifndef MD_FN
 #define MD_FN static inline
@@ -817,10 +818,14 @@ MD_FN void md_choose_mvp(const SvtAmdMdPicture *P, uint32_t ox, uint32_t oy, con
     }
 }
 
-/* Me2Nx2NCandidatesInjection (Codec/EbModeDecision.c:446-566) with sub-sample motion and unrestricted motion vectors (neither RoundMv
- * nor LimitMvOverBound), then ProductMergeSkip2Nx2NCandidatesInjection (:1608-1700).  Returns the new candidate count. */
-MD_FN int md_inter_candidates(const SvtAmdMdPicture *P, const SvtAmdMdLcu *L, const SvtAmdMeCuResult *me, const MdInterLists *T, uint32_t ox,
-                              uint32_t oy, int totalMerge, MdCand *cand, int n)
+/* Me2Nx2NCandidatesInjection (Codec/EbModeDecision.c:446-566) with unrestricted motion vectors (no LimitMvOverBound), then ProductMergeSkip2Nx2NCandidatesInjection
+ * (:1608-1700).  Returns the new candidate count.  roundMv = the picture is coded without sub-sample search (!SvtAmdMdInter.use_subpel): RoundMv (:200, called at :481)
+ * takes all four components of a motion-estimation candidate to whole samples BEFORE the predictor choice, so the vector difference and its rate are the rounded vector's
+ * (the same order as at :695 for the AMVP candidate of the extra injections, which the device call refuses).  A merge candidate KEEPS its vector - in the candidate, in the
+ * records and for the encode pass; only the mode decision's prediction of it is made at the rounded position (roundMvToInteger, Codec/EbProductCodingLoop.c:2009 / :4239;
+ * inter_mv_round of inter_position.h in the kernel's md_predict_tile). */
+MD_FN int md_inter_candidates_r(const SvtAmdMdPicture *P, const SvtAmdMdLcu *L, const SvtAmdMeCuResult *me, const MdInterLists *T, uint32_t ox,
+                                uint32_t oy, int totalMerge, MdCand *cand, int n, int roundMv)
 {
     for (int i = 0; i < me->total_me_candidate_index; i++) {
         const int dir = me->direction[i];
@@ -830,6 +835,9 @@ MD_FN int md_inter_candidates(const SvtAmdMdPicture *P, const SvtAmdMdLcu *L, co
         c->type = MD_INTER, c->intra_mode = 0, c->mpm = 0, c->dist_ready = 1, c->me_dist = me->distortion[i];
         c->dir = (uint8_t)dir, c->merge_flag = 0, c->merge_index = 0;
         c->mv[0].x = me->x_mv_l0, c->mv[0].y = me->y_mv_l0, c->mv[1].x = me->x_mv_l1, c->mv[1].y = me->y_mv_l1;
+        if (roundMv)
+            for (int l = 0; l < 2; l++)
+                c->mv[l].x = (int16_t)inter_mv_round(c->mv[l].x), c->mv[l].y = (int16_t)inter_mv_round(c->mv[l].y);
         c->mvp_idx[0] = c->mvp_idx[1] = 0, c->mvp[0].x = c->mvp[0].y = c->mvp[1].x = c->mvp[1].y = 0;
         md_choose_mvp(P, ox, oy, T, c);
         n++;
@@ -856,6 +864,12 @@ MD_FN int md_inter_candidates(const SvtAmdMdPicture *P, const SvtAmdMdLcu *L, co
         n++;
     }
     return n;
+}
+/* ... of a picture coded with sub-sample search */
+MD_FN int md_inter_candidates(const SvtAmdMdPicture *P, const SvtAmdMdLcu *L, const SvtAmdMeCuResult *me, const MdInterLists *T, uint32_t ox,
+                              uint32_t oy, int totalMerge, MdCand *cand, int n)
+{
+    return md_inter_candidates_r(P, L, me, T, ox, oy, totalMerge, cand, n, 0);
 }
 
 /* mvBitTable (Codec/EbModeDecisionConfiguration.h:108): the 500 x 500 table is a 3 x 3 core plus 2 bits (1 << 16) per doubling of
@@ -1117,14 +1131,17 @@ MD_FN int md_picture_supported(const SvtAmdMdPicture *P)
            P->intra4x4_level == 2 && !P->rdoq_pmcore_method && !P->single_fast_loop && !P->spatial_sse_full_loop && P->pf_md_level == 0 &&
            P->nfl_level_md != 3 && P->intra_injection_method <= 2 && !(P->width & 7) && !(P->height & 7);
 }
-/* P / B pictures; the LCUs must in addition all be decided by ModeDecisionLcu (md_lcu_supported) */
+/* P / B pictures; the LCUs must in addition all be decided by ModeDecisionLcu (md_lcu_supported).  use_subpel is free: a picture coded without sub-sample search takes
+ * the interpolation-free instance of the kernel (8-bit pictures; the 16-bit entries refuse it by themselves) */
 MD_FN int md_picture_supported_inter(const SvtAmdMdPicture *P, const SvtAmdMdInter *X)
 {
     return P->slice_type != 2 && P->intra_md_open_loop && !P->coeff_cabac_update && P->intra4x4_level == 2 &&
            !P->rdoq_pmcore_method && !P->single_fast_loop && !P->spatial_sse_full_loop && P->pf_md_level <= 1 && P->nfl_level_md != 3 &&
            P->intra_injection_method <= 1 && !P->limit_ois_to_dc_mode && !P->mpm_search && P->enc_mode < 10 && !(P->width & 7) && !(P->height & 7) &&
-           X->use_subpel && X->unrestricted_mv && X->generate_amvp_table_md && !X->extra_injection && !X->improve_sharpness;
+           X->unrestricted_mv && X->generate_amvp_table_md && !X->extra_injection && !X->improve_sharpness;
 }
+/* ... by the 16-bit entries: UnpackUniPredRef10Bit / UnpackBiPredRef10Bit, the interpolation-free prediction from 10-bit reference pictures, is a second path */
+MD_FN int md_picture_supported_inter16(const SvtAmdMdPicture *P, const SvtAmdMdInter *X) { return md_picture_supported_inter(P, X) && X->use_subpel; }
 MD_FN int md_lcu_supported(const SvtAmdMdPicture *P, const SvtAmdMdLcu *L)
 {
     if (L->chroma_encode_mode != 2 /* CHROMA_MODE_BEST */ && L->chroma_encode_mode != 1 /* CHROMA_MODE_FULL: chroma in both loops of every candidate */)
