@@ -2620,12 +2620,12 @@ SVT_AMD_API int svt_amd_debug_md_trace(SvtAmdContext *ctx, SvtAmdEncDecPicture *
 SVT_AMD_API int svt_amd_debug_md_kernel_ms(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, float *ms, int *workgroups);
 /* ... and of the encode-pass kernel queued behind it by the same call */
 SVT_AMD_API int svt_amd_debug_md_ep_ms(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, float *ms);
-/* diagnosis: the mode-decision launches that hold (or wait for) workgroups of the device budget right now (md_kernels.hip: MdFlight) */
+/* diagnosis: the mode-decision launches that hold (or wait for) workgroups of the device budget right now (md_picture.hip: MdFlight) */
 SVT_AMD_API int svt_amd_debug_md_flights(int *in_flight, int *workgroups_held, int *waiting);
 /* Everything the first svt_amd_md_encode_picture[_inter / 16] call on a picture object would allocate (device state, page-locked staging, events), made NOW: for hosts that
  * build their picture objects before their clock starts (the encoder binding at EbInitEncoder time) - allocations made while other pictures' kernels run wait for them. */
 SVT_AMD_API int svt_amd_md_picture_warmup(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic);
-/* measurement: dynamic LDS bytes a workgroup of k_md_encode_picture<inter, sample bytes> is launched with (the whole LCU state: one workgroup per CU) */
+/* measurement: dynamic LDS bytes a workgroup of k_md_picture<inter, sample bytes> is launched with (the whole LCU state: one workgroup per CU) */
 SVT_AMD_API int svt_amd_debug_md_kernel_lds_bytes(int inter, int bytes_per_sample);
 /* test: the motion-vector candidate lists of the P / B unit loop (md_kernels.hip: the register form of GenerateL0L1AmvpMergeLists + ChooseMVPIdx_V2) on single
  * units, a lane per job - the __device__ functions the unit loop calls, on inputs no recorded picture holds (tests/test_gpu_md_lists.py against the reference's

@@ -49,7 +49,7 @@ struct SvtAmdEncDecPicture {
     /* the finished picture with its padding: a reference picture of later pictures (svt_amd_encdec_picture_reference) */
     uint8_t *refp[3];
     size_t refp_bytes[3];
-    /* the mode decision's part (md_kernels.hip): neighbour maps, source planes, per-LCU arrays; allocated by the first svt_amd_md_encode_picture */
+    /* the mode decision's part (md_picture.hip): neighbour maps, source planes, per-LCU arrays; allocated by the first svt_amd_md_encode_picture */
     struct SvtAmdMdState *md;
     /* svt_amd_md_picture_set_controls: the DEVICE SvtAmdMdLcu array the next mode-decision call on the object reads in place; that call clears it */
     const SvtAmdMdLcu *md_bound_lcus;
@@ -76,9 +76,9 @@ static inline int ep_picture_written(SvtAmdContext *ctx, SvtAmdEncDecPicture *pi
     pic->written = true;
     return SVT_AMD_OK;
 }
-void svt_amd_md_state_free(SvtAmdEncDecPicture *pic); /* md_kernels.hip */
+void svt_amd_md_state_free(SvtAmdEncDecPicture *pic); /* md_picture.hip */
 void svt_amd_tail_state_free(SvtAmdEncDecPicture *pic); /* tail_kernels.hip */
-/* md_kernels.hip: the DEVICE records of the object's mode-decision state and their strides; 0 when the object has none */
+/* md_picture.hip: the DEVICE records of the object's mode-decision state and their strides; 0 when the object has none */
 int svt_amd_md_picture_records(const SvtAmdEncDecPicture *pic, const void **d_works, size_t *work_stride, const void **d_results, size_t *result_stride);
 /* encdec_kernels.hip: the encode pass of every LCU of the picture from work records the mode-decision kernel left in HBM, queued on ctx's stream behind it */
 int svt_amd_ep_launch_behind_md(SvtAmdContext *ctx, SvtAmdEncDecPicture *pic, const void *d_works, void *d_results, int n_active, const unsigned *d_order, int inter, int tiles);

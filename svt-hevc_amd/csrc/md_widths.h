@@ -1,6 +1,6 @@
 /* md_widths.h - the launch widths of k_md_picture (md_kernels.hip): how many workgroups a picture's mode-decision launch gets.  One text for the blocking entries
  * (svt_amd_md_encode_picture*: MdFlight grants `lone`, `wide` or `narrow`) and for svt_amd_md_encode_picture_launch (`lone` or `narrow`), and for the host
- * (tools/md_widths_check.c: a plain C program, tests/test_md_widths_cpu.py pins the widths).  Plain C: no HIP, no environment - md_launch_widths (md_kernels.hip) reads
+ * (tools/md_widths_check.c: a plain C program, tests/test_md_widths_cpu.py pins the widths).  Plain C: no HIP, no environment - md_launch_widths (md_picture.hip) reads
  * the measurement overrides and passes them in. */
 #ifndef SVT_AMD_MD_WIDTHS_H
 #define SVT_AMD_MD_WIDTHS_H

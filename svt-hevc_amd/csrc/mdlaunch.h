@@ -1,4 +1,4 @@
-/* mdlaunch.h - what md_kernels.hip:svt_amd_md_encode_picture_launch calls in mdlaunch_kernels.hip and mdctl_kernels.hip (not part of the C-ABI).  Each of them
+/* mdlaunch.h - what md_picture.hip:svt_amd_md_encode_picture_launch calls in mdlaunch_kernels.hip and mdctl_kernels.hip (not part of the C-ABI).  Each of them
  * queues on the context's stream and returns: no copy from or to host memory, no wait. */
 #ifndef SVT_AMD_MDLAUNCH_H
 #define SVT_AMD_MDLAUNCH_H

@@ -1,5 +1,5 @@
 /*
- * mdlaunch_kernels.hip - what svt_amd_md_encode_picture_launch (md_kernels.hip; include/svt_hevc_amd.h "Device-resident mode decision") queues in
+ * mdlaunch_kernels.hip - what svt_amd_md_encode_picture_launch (md_picture.hip; include/svt_hevc_amd.h "Device-resident mode decision") queues in
  * front of the mode-decision kernel in place of the blocking call's host copies: every input reaches the picture object's device state by a LAUNCH, so the entry
  * neither copies from host memory nor waits, and a second launch queued on the same object before the first has run finds the first one's inputs untouched.
  *   k_md_source<T>  grid (rows / 4 capped, 3 planes), a wave per row: the caller's DEVICE source planes into the object's own planes at the object's pitch - 16 bytes

@@ -141,7 +141,7 @@ int svt_amd_ctx_scratch(SvtAmdContext *ctx, size_t bytes, uint8_t **out);
 /* context.hip: the device's view of a range inside a svt_amd_host_register'ed buffer, or nullptr */
 const void *svt_amd_registered_device_ptr(const void *h_ptr, size_t bytes);
 
-/* context.hip: what a consumer of the records resident in a slot goes through, in this order.  The mode-decision call (md_kernels.hip) calls all three itself;
+/* context.hip: what a consumer of the records resident in a slot goes through, in this order.  The mode-decision call (md_picture.hip) calls all three itself;
  * the batched readers (source-based operations, mode-decision configuration, initial rate control) go through the first two by way of
  * svt_amd_batch_slot_records and svt_amd_batch_bind_records (pa_batch.h) and leave no read mark.
  * svt_amd_slot_records: the device pointer of the slot's ME (which == 0) / OIS (which == 1) records, or nullptr unless the slot is in range, holds a picture of

@@ -1,5 +1,5 @@
 """GPU: the mode-decision picture call as a stream-ordered launch on device inputs (include/svt_hevc_amd.h: svt_amd_md_encode_picture_launch,
-svt_amd_encdec_picture_md_records; svt-hevc_amd/csrc/mdlaunch_kernels.hip and the entry in md_kernels.hip) - against the blocking call on the same picture object,
+svt_amd_encdec_picture_md_records; svt-hevc_amd/csrc/mdlaunch_kernels.hip and the entry in md_picture.hip) - against the blocking call on the same picture object,
 byte for byte, and against the decisions the REFERENCE recorded (tests/golden/md_*.npz); source planes at awkward pitches; launches in flight on one lane; the chain
 controls -> decision -> tail -> motion field -> next decision without a wait; a controls array refused on the device; the host time of the call."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""GPU: the motion-vector candidate lists the P / B unit loop executes (svt-hevc_amd/csrc/md_kernels.hip: md_list_consts, md_tmvp_position, md_amvp_one_list,
+"""GPU: the motion-vector candidate lists the P / B unit loop executes (svt-hevc_amd/csrc/md_lists.h: md_list_consts, md_tmvp_position, md_amvp_one_list,
 md_temporal_mvp_dev, md_merge_list_regs, md_choose_mvp_one - the REGISTER form of the lists, a second text beside md_logic.h's) against what the reference's own
 GenerateL0L1AmvpMergeLists and ChooseMVPIdx_V2 answered on the seeded jobs of tests/golden/mvlists_seeded.npz: POC distances beyond the +-128 clips, scale factors
 and scaled components at their clips, co-located list 1, no motion field, ClipMV at the far corner of 4096 x 2304 pictures.  svt_amd_debug_md_lists_batch runs those

@@ -1,5 +1,5 @@
 """CPU-only: the mode-decision checker (oracle/svt_oracle_md.c = the scalar decisions of svt-hevc_amd/csrc/md_logic.h, the text the HIP kernel
-executes - except the motion-vector candidate lists of P / B units, which the kernel derives from a register form of its own in md_kernels.hip:
+executes - except the motion-vector candidate lists of P / B units, which the kernel derives from a register form of its own in md_lists.h:
 tests/test_oracle_mvlists.py and tests/test_gpu_md_lists.py pin both forms - composed with the pinned oracle leaves) against whole pictures of
 ModeDecisionLcu calls recorded inside the reference encoder
 (tests/golden/md_*.npz, oracle/ref_harness_md_dump.c): for every leaf the reference tested - split flag, prediction mode, intra luma mode,

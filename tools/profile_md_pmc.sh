@@ -25,9 +25,9 @@ meta = {}
 for f in glob.glob(O + "/p*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
-        if "k_md_encode_picture" not in k:
+        if "k_md_picture" not in k:
             continue
-        k = "k_md_encode_picture<inter>" if "Lb1" in k or "<true" in k else "k_md_encode_picture<intra>"
+        k = "k_md_picture<inter>" if "Lb1" in k or "<true" in k else "k_md_picture<intra>"
         acc[k][r["Counter_Name"]] += float(r["Counter_Value"])
         meta[k] = (r["VGPR_Count"], r.get("Accum_VGPR_Count"), r["SGPR_Count"], r["LDS_Block_Size"], r["Scratch_Size"])
 with open(O + "/md_pmc.txt", "w") as out:

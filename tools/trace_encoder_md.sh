@@ -23,7 +23,7 @@ for f in glob.glob(O + "/tr/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         n = r["Kernel_Name"]
         rec = (int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Queue_Id", "?"), n[:40])
-        (md if "k_md_encode_picture" in n else other).append(rec)
+        (md if "k_md_picture" in n else other).append(rec)
 md.sort()
 with open(O + "/events.txt", "w") as ev:   # every kernel of the run: start end (us since the first) queue name - for offline questions
     allk = sorted(md + other)
@@ -33,7 +33,7 @@ if not md:
     print("no mode-decision kernel in the trace"); sys.exit(0)
 t0 = md[0][0]
 with open(O + "/md_timeline.txt", "w") as out:
-    print("k_md_encode_picture launches: %d; queues used: %s" % (len(md), sorted(set(m[2] for m in md))), file=out)
+    print("k_md_picture launches: %d; queues used: %s" % (len(md), sorted(set(m[2] for m in md))), file=out)
     for s, e, q, n in md:
         conc = sum(1 for s2, e2, _, _ in md if s2 < e and e2 > s)
         print("%9.2f -> %9.2f ms (%7.2f)  queue %s  overlapping launches %d" % ((s - t0) / 1e6, (e - t0) / 1e6, (e - s) / 1e6, q, conc), file=out)
