@@ -37,6 +37,18 @@ CASES = {
     # temporal layers 0 / 1 / 2; three LCU rows kept (top, interior, the partial bottom row) to bound the fixture size
     "ib_3840x2160_m7": ("motion", 3840, 2160, 5, 7,
                         ["-encMode", "7", "-pred-struct", "2", "-hierarchical-levels", "2", "-sao", "1", "-fps", "60"], 5),
+    # x_islands: 32x32 CUs whose every tested mode has SAD 32 * 32 * 255, so the reference keeps bestMode / stage1SadArray of the CU before (the
+    # carried state); threshold set 1 (encMode 9: three stage-1 modes at an island) and threshold set 2 (encMode 6: seven); the intra period
+    # makes picture 7, with islands, an I picture (32x32: planar only, nothing carried) and leaves the odd P pictures before it on the highest temporal
+    # layer, whose one reference picture is the flat picture before them
+    "x_islands_320x256_m9": ("x_islands", 320, 256, 8, 3, ["-encMode", "9", "-pred-struct", "0", "-intra-period", "6", "-scd", "0"], 8),
+    "x_islands_320x256_m6": ("x_islands", 320, 256, 8, 3, ["-encMode", "6", "-pred-struct", "2", "-hierarchical-levels", "2", "-scd", "0"], 8),
+    # saturated samples: SADs at the top of the 20-bit field, many equal maxima in the 35-mode ranking (encMode 4), both clips of the edge filters
+    "x_binary_192x128_m4": ("x_binary", 192, 128, 5, 3, ["-encMode", "4", "-pred-struct", "2", "-hierarchical-levels", "2"], 5),
+    "x_stripes_192x128_m7": ("x_stripes", 192, 128, 4, 3, ["-encMode", "7", "-pred-struct", "1"], 4),
+    "xc_blocks_192x128_m9": ("xc_blocks", 192, 128, 4, 3, ["-encMode", "9", "-pred-struct", "0"], 4),
+    # the smallest pictures: one LCU and a last LCU 8 samples wide (an I and two P pictures)
+    "ip_72x64_m9": ("x_binary", 72, 64, 3, 3, ["-encMode", "9", "-pred-struct", "0"], 3),
 }
 ROWS_KEPT = {"ib_3840x2160_m7": [0, 16, 33]}
 

@@ -283,8 +283,124 @@ def load_product():
 # synthetic clips
 # ----------------------------------------------------------------------------
 
+def islands_ground(t):
+    """Ground colour of frame t of x_islands: 255, 255, 0, 0, 255, ..."""
+    return 255 if (t // 2) % 2 == 0 else 0
+
+
+# texture directions of x_islands: the nine stage-1 modes of the open-loop intra search; u(x, y) is constant along the mode's prediction direction
+# (tan = 13 / 32 for modes 6 / 14 / 22 / 30, the reference's intraModeAngularTable)
+_ISLAND_DIRS = {10: (0, 32), 26: (32, 0), 2: (32, 32), 34: (32, 32), 18: (32, -32), 6: (13, 32), 14: (-13, 32), 22: (32, -13), 30: (32, 13)}
+_ISLAND_DIR_LIST = (10, 26, 2, 18, 34, 6, 14, 22, 30)
+
+
+def islands_layout(w, h, t, seed):
+    """Where frame t (odd) of x_islands has its 32x32 blocks, on the 32-grid, as pixel origins:
+      islands  blocks of the colour opposite to the ground; every one of the 4N + 1 samples an intra prediction of the block reads is ground
+      chained  the islands (a subset) at CU 2 of an LCU whose CU 1, and the CU above it, are textured along mode 30
+      twins    blocks of GROUND colour at CU 4 of an LCU whose CU 1 is an island, ringed by a one-sample line of the island colour: within one LCU only
+               CU 1 and CU 4 can both have every reference sample at the opposite colour (any other pair shares ring samples that would need both colours)
+      texture  {(x, y): (mode, period)} of the other 32x32 cells that carry stripes
+    No two blocks touch, not even diagonally; every block has x, y >= 32 and x + 64 <= w, y + 64 <= h."""
+    rng = np.random.default_rng([seed, t, 77])
+    cw, ch = w // 32, h // 32
+    occ = np.zeros((ch + 2, cw + 2), bool)  # cell (cx, cy) at occ[cy + 1, cx + 1]
+    need = np.full((h, w), -1, np.int16)    # the samples the blocks placed so far fix: 1 island colour, 0 ground
+
+    def views(cx, cy):  # a block's samples, the row above it and the column left of it (2N + 1 samples each)
+        ox, oy = 32 * cx, 32 * cy
+        return need[oy:oy + 32, ox:ox + 32], need[oy - 1, ox - 1:ox + 64], need[oy - 1:oy + 64, ox - 1]
+
+    def free(cx, cy, inner=1):
+        if not (1 <= cx and 1 <= cy and cx + 2 <= cw and cy + 2 <= ch) or occ[cy:cy + 3, cx:cx + 3].any():
+            return False
+        body, row, col = views(cx, cy)
+        return not ((body == 1 - inner).any() or (row == inner).any() or (col == inner).any())
+
+    def place(cx, cy, inner=1):
+        occ[cy + 1, cx + 1] = True
+        body, row, col = views(cx, cy)
+        body[...], row[...], col[...] = inner, 1 - inner, 1 - inner
+
+    islands, chained, twins, forced = [], [], [], {}
+    # A lattice packs the islands tightly: rows of cells 2 or 3 apart, an island every other cell.  A row holds one CU index (1 + (cx & 1) + 2 * (cy & 1));
+    # the rows and their first columns change from one odd frame to the next, so that a few frames hold every index often.
+    rows, firsts = (((2, 5), (2, 1)), ((1, 4, 6), (1, 1, 2)), ((1, 3, 6), (2, 1, 2)), ((1, 4, 6), (1, 1, 2)))[(t // 2) % 4]
+    lattice = [(cx, cy) for cy, first in zip(rows, firsts) for cx in range(first, cw - 1, 2)]
+    # one twin LCU where the row below the island's is free: its ground block stands in place of the next island of the row
+    fit = [(cx, cy) for cx, cy in lattice if not (cx & 1 or cy & 1) and cy + 1 not in rows and cy + 2 not in rows and cx + 3 <= cw and cy + 3 <= ch]
+    if fit:
+        cx, cy = fit[int(rng.integers(0, len(fit)))]
+        if free(cx, cy):
+            place(cx, cy)
+            place(cx + 1, cy + 1, 0)
+            islands.append((32 * cx, 32 * cy))
+            twins.append((32 * cx + 32, 32 * cy + 32))
+    for cx, cy in lattice:
+        if free(cx, cy):
+            place(cx, cy)
+            islands.append((32 * cx, 32 * cy))
+    # up to two chained LCUs: an island at CU 2 whose CU 1, and the CU above that, are free to be textured along mode 30; no island left of that CU 1
+    # either, whose ring would flatten the row of samples above it
+    for k in rng.permutation(len(islands)):
+        cx, cy = islands[k][0] // 32, islands[k][1] // 32
+        if len(chained) < 2 and cx & 1 and not cy & 1 and not occ[cy:cy + 2, cx].any() and not occ[cy + 1, cx - 1]:
+            chained.append(islands[k])
+            forced[(32 * cx - 32, 32 * cy)] = forced[(32 * cx - 32, 32 * cy - 32)] = (30, 6)
+    # ... and whatever else fits, always at the CU index that has the fewest so far
+    cells = [(cx, cy) for cy in range(1, ch) for cx in range(1, cw)]
+    cells = [cells[k] for k in rng.permutation(len(cells))]
+    count = [0, 0, 0, 0]
+    for ox, oy in islands:
+        count[(ox // 32 & 1) + 2 * (oy // 32 & 1)] += 1
+    while True:
+        for c in sorted(range(4), key=lambda c: count[c]):
+            fit = [(cx, cy) for cx, cy in cells if (cx & 1) + 2 * (cy & 1) == c and free(cx, cy) and (32 * cx, 32 * cy) not in forced]
+            if fit:
+                cx, cy = fit[0]
+                islands.append((32 * cx, 32 * cy))
+                place(cx, cy)
+                count[c] += 1
+                break
+        else:
+            break
+    texture = dict(forced)
+    for cy in range(ch):
+        for cx in range(cw):
+            mode, period, draw = _ISLAND_DIR_LIST[int(rng.integers(0, 9))], int(rng.integers(3, 10)), rng.integers(0, 4) > 0
+            if draw and not occ[cy + 1, cx + 1] and (32 * cx, 32 * cy) not in forced:
+                texture[(32 * cx, 32 * cy)] = (mode, period)
+    return dict(islands=islands, chained=chained, twins=twins, texture=texture)
+
+
+def _islands_frame(w, h, t, seed):
+    g = islands_ground(t)
+    luma = np.full((h, w), g, np.uint8)
+    if t % 2 == 0:
+        return luma
+    lay = islands_layout(w, h, t, seed)
+    y, x = np.mgrid[0:h, 0:w]
+    for (ox, oy), (mode, period) in lay["texture"].items():
+        a, b = _ISLAND_DIRS[mode]
+        sl = (slice(oy, oy + 32), slice(ox, ox + 32))
+        bits = ((a * x[sl] + b * y[sl]) // (32 * period)) & 1
+        luma[sl] = np.where(bits, 255 - g, g)
+    for blocks, inner in ((lay["islands"], 255 - g), (lay["twins"], g)):
+        for ox, oy in blocks:  # the ring: row oy - 1 and column ox - 1, 2N + 1 samples each
+            luma[oy - 1, ox - 1:ox + 64] = 255 - inner
+            luma[oy - 1:oy + 64, ox - 1] = 255 - inner
+    for blocks, inner in ((lay["islands"], 255 - g), (lay["twins"], g)):
+        for ox, oy in blocks:
+            luma[oy:oy + 32, ox:ox + 32] = inner
+    return luma
+
+
 def gen_luma(kind, w, h, t, seed):
     """One 8-bit luma frame of clip `kind` at time t."""
+    if kind == "x_islands":
+        # even frames flat, odd frames 32x32 islands of the opposite colour whose every intra reference sample is ground: all 35 predictions of an island are
+        # flat ground, every SAD is 32 * 32 * 255, no mode beats the reference's initial best and the open-loop intra search keeps the state the CU before left
+        return _islands_frame(w, h, t, seed)
     if kind == "xc_blocks":
         # 16x16 blocks of 0 and 255, new ones every frame: a white unit among black ones is predicted black by every intra mode, so whole units carry a
         # flat residual of 255 - the largest DC coefficient there is (32640), which at a high QP de-quantises past the top of 16 bits

@@ -54,8 +54,10 @@ def test_ois_oracle_matches_reference(oracle, name):
         want = g["after"][i]
         bad = np.nonzero((got["candidate"] != want["candidate"]).any(axis=(1, 2)) | (got["total"] != want["total"]).any(axis=1))[0]
         assert len(bad) == 0, (name, int(pn), bad[:5])
-        # the call really wrote something everywhere (guards against a vacuous mask)
-        assert (out["candidate"][:, 1:21, 0] & (S.OIS_W_DIST | S.OIS_W_VALID)).any(axis=1).all()
+        # the call really wrote something everywhere (guards against a vacuous mask); an LCU less than 16 samples wide or high holds 8x8 CUs only
+        wl = (w + 63) // 64
+        whole = (w - (kept % wl) * 64 >= 16) & (h - (kept // wl) * 64 >= 16)
+        assert (out["candidate"][:, 1:21, 0] & (S.OIS_W_DIST | S.OIS_W_VALID)).any(axis=1)[whole].all() and whole.any()
         seen.add((int(slice_type), int(params.ois_kernel_level), int(params.limit_ois_to_dc_mode)))
     assert len(seen) >= 1
 
