@@ -7,6 +7,7 @@ call pairs of the real encode pass: neighbour-array slices and flags in, the thr
 Stored as tests/golden/intra_<name>.npz.  Needs /root/reference (this container only).
 With SVT_REF_INTRA_MD_DUMP the same harness records the mode decision's closed-loop IntraPredictionCl calls (one record per
 luma block, one per chroma pair; component_mask says which planes are valid) -> tests/golden/intramd_<name>.npz.
+Names starting with "thr_" (THR_CASES) are encodes of a clip the script designs itself so that 32x32 units land on the strong-smoothing decision.
 Usage: python tests/golden/make_intra_golden.py [name ...]      (names of either family)
 """
 import os
@@ -56,6 +57,15 @@ I4_CASES = {
     # the mode decision's 4x4 search (Intra4x4IntraPredictionCl): names starting with "md_"
     "md_i_noise_200x136_m1": ("noise", 200, 136, 1, 11, 8, ["-encMode", "1", "-intra-period", "0", "-q", "24"], 97, 300),
 }
+# strong-smoothing thresholds (names starting with "thr_"): the script writes the clip itself - a curved luma surface whose second difference over +-32
+# samples IS the threshold (8 for 8-bit, 32 for 10-bit), +-1 dither, shifted per frame, flat chroma - and keeps only 32x32 records on or next to the decision
+# name -> (width, height, frames, seed, bit depth, encoder args)
+THR_CASES = {
+    "thr_i_448x256_m9": (448, 256, 16, 1, 8, ["-encMode", "9", "-intra-period", "0", "-q", "20"]),
+    "thr_i_448x256_m5": (448, 256, 16, 1, 8, ["-encMode", "5", "-intra-period", "0", "-q", "14"]),
+    "thr_i10_448x256_m5": (448, 256, 16, 1, 10, ["-encMode", "5", "-intra-period", "0", "-q", "14", "-bit-depth", "10"]),
+}
+THR_FIRED_CAP = 40      # records where the bilinear filter fires, per fixture
 KEEP = ("size", "bytes_per_sample", "constrained_intra", "strong_smoothing", "pic_left", "pic_top", "pic_right", "bottom_left_ok",
         "top_right_ok", "luma_mode", "chroma_mode", "mode_left", "mode_top", "mode_tl", "left", "top", "tl")
 
@@ -86,6 +96,49 @@ def run_case(name):
            len(np.unique(recs["luma_mode"])), int(recs["pic_left"].sum()), int(recs["pic_top"].sum()), int(recs["pic_right"].sum()),
            int(recs["bottom_left_ok"].sum()), int(recs["top_right_ok"].sum()),
            int(((recs["mode_left"] == 1).any(axis=1) | (recs["mode_top"] == 1).any(axis=1)).sum()), int(recs["constrained_intra"].sum())))
+
+
+def write_threshold_clip(path, w, h, n, seed, depth):
+    """luma base + c ((x % 128) / 32)^2 + c ((y % 128) / 32)^2 with c = 4 (8-bit) / 16 (10-bit): s(x - 32) + s(x + 32) - 2 s(x) = 2 c inside a period, the
+    threshold itself, so that the reconstruction's second differences scatter around it; +-1 dither; the surface moves by (5, 3) samples a frame; flat chroma"""
+    rng = np.random.default_rng(seed)
+    c, base, mid, dt = (4, 60, 128, np.uint8) if depth == 8 else (16, 240, 512, "<u2")
+    yy, xx = np.mgrid[0:h, 0:w]
+    with open(path, "wb") as f:
+        for t in range(n):
+            s = base + c * (((xx + 5 * t) % 128) / 32.0) ** 2 + c * (((yy + 3 * t) % 128) / 32.0) ** 2
+            f.write((np.rint(s).astype(np.int64) + rng.integers(-1, 2, (h, w))).astype(dt).tobytes())
+            f.write(np.full((h // 2, w // 2), mid, dt).tobytes() * 2)
+
+
+def run_thr_case(name):
+    import intra_ref_extremes as X
+    w, h, n, seed, depth, args = THR_CASES[name]
+    with tempfile.TemporaryDirectory() as td:
+        yuv, dump = os.path.join(td, "clip.yuv"), os.path.join(td, "intra.dump")
+        write_threshold_clip(yuv, w, h, n, seed, depth)
+        cmd = [S.REF_APP, "-i", yuv, "-w", str(w), "-h", str(h), "-n", str(n), "-asm", "0", "-b", os.path.join(td, "out.265")] + args
+        subprocess.run(cmd, env=dict(os.environ, SVT_REF_INTRA_DUMP=dump, SVT_REF_INTRA_STRIDE="1"), check=True, stdout=subprocess.DEVNULL)
+        recs = np.fromfile(dump, dtype=REC)
+    assert len(recs) and (recs["record_size"] == REC.itemsize).all(), (len(recs), REC.itemsize)
+    recs = recs[(recs["size"] == 32) & (recs["pic_left"] == 0) & (recs["pic_top"] == 0)]
+    recs = recs[sorted(range(len(recs)), key=lambda i: recs[i].tobytes())]      # the encoder's threads leave the records in the order they finish
+    cls = X.smoothing_classes(recs)
+    fired = np.flatnonzero(cls["fired"])
+    fired = fired[np.linspace(0, len(fired) - 1, min(THR_FIRED_CAP, len(fired))).astype(int)] if len(fired) else fired
+    sel = np.unique(np.concatenate([fired] + [np.flatnonzero(cls[k]) for k in "ABC"]))
+    total, avail = len(recs), int(cls["available"].sum())
+    recs = recs[sel]
+    out = {k: recs[k] for k in KEEP}
+    out["pred_y"] = np.concatenate([r["pred_y"][: int(r["size"]) ** 2] for r in recs])
+    out["pred_cb"] = np.concatenate([r["pred_cb"][: (int(r["size"]) // 2) ** 2] for r in recs])
+    out["pred_cr"] = np.concatenate([r["pred_cr"][: (int(r["size"]) // 2) ** 2] for r in recs])
+    path = os.path.join(S.GOLDEN_DIR, "intra_%s.npz" % name)
+    np.savez_compressed(path, **out)
+    kept = X.smoothing_classes(recs)
+    print("%-26s %d of %d records (%d all-available 32x32) -> %s (%.0f KiB); fired %d, A %d, B %d, C %d, %d luma modes" %
+          (name, len(recs), total, avail, os.path.basename(path), os.path.getsize(path) / 1024, int(kept["fired"].sum()), int(kept["A"].sum()),
+           int(kept["B"].sum()), int(kept["C"].sum()), len(np.unique(recs["luma_mode"]))))
 
 
 def run_i4_case(name):
@@ -156,7 +209,7 @@ def run_md_case(name, ol=False):
 if __name__ == "__main__":
     if not os.path.exists(S.REF_APP):
         sys.exit("oracle/_ref/SvtHevcEncApp_ref missing: run `make -C oracle ref` (needs /root/reference)")
-    names = sys.argv[1:] or (list(CASES) + ["md:" + k for k in MD_CASES] + ["ol:" + k for k in OL_CASES] + ["i4:" + k for k in I4_CASES])
+    names = sys.argv[1:] or (list(CASES) + list(THR_CASES) + ["md:" + k for k in MD_CASES] + ["ol:" + k for k in OL_CASES] + ["i4:" + k for k in I4_CASES])
     for nm in names:
         if nm.startswith("md:"):
             run_md_case(nm[3:])
@@ -164,5 +217,7 @@ if __name__ == "__main__":
             run_md_case(nm[3:], ol=True)
         elif nm.startswith("i4:"):
             run_i4_case(nm[3:])
+        elif nm in THR_CASES:
+            run_thr_case(nm)
         else:
             run_case(nm)

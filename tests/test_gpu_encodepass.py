@@ -144,8 +144,9 @@ def z_available(x, y, s):
     return int(bl), int(tr)
 
 
-def random_picture(oracle, w, h, qp, seed, tile_cols=1, tile_rows=1, constrained=0):
-    """seeded works of a whole picture (random unit trees, modes, QPs, dead zones) and what the CPU oracle makes of them in raster order"""
+def random_picture(oracle, w, h, qp, seed, tile_cols=1, tile_rows=1, constrained=0, strong=1):
+    """seeded works of a whole picture (random unit trees, modes, QPs, dead zones) and what the CPU oracle makes of them in raster order.
+    constrained / strong: constrained_intra / strong_smoothing of every LCU"""
     oracle.svt_oracle_encode_lcu.restype = None
     oracle.svt_oracle_encode_lcu.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                              C.c_void_p, C.c_void_p]
@@ -161,8 +162,8 @@ def random_picture(oracle, w, h, qp, seed, tile_cols=1, tile_rows=1, constrained
         for lx in range(wl):
             wk = works[ly * wl + lx]
             lw, lh = min(64, w - 64 * lx), min(64, h - 64 * ly)
-            wk["lcu_x"], wk["lcu_y"], wk["slice_type"], wk["strong_smoothing"] = 64 * lx, 64 * ly, 2, 1
-            wk["constrained_intra"] = 0
+            wk["lcu_x"], wk["lcu_y"], wk["slice_type"], wk["strong_smoothing"] = 64 * lx, 64 * ly, 2, strong
+            wk["constrained_intra"] = constrained
             wk["tile_left"], wk["tile_top"], wk["tile_right"] = lx in col0, ly in row0, (lx + 1) in col0
             tree = random_tree(rng, lw, lh)
             wk["num_cus"] = len(tree)
@@ -192,7 +193,7 @@ def random_picture(oracle, w, h, qp, seed, tile_cols=1, tile_rows=1, constrained
     return works, want
 
 
-def random_inter_picture(oracle, w, h, qp, seed, pad=80, intra_lcus=1.0, tile_cols=1, matched=False, wide=False):    # pad > 75: a window at a clamped position stays inside the plane
+def random_inter_picture(oracle, w, h, qp, seed, pad=80, intra_lcus=1.0, tile_cols=1, matched=False, wide=False, constrained=0, strong=1):    # pad > 75: a window at a clamped position stays inside the plane
     """a seeded B picture: random unit trees with ~80 % inter units (L0 / L1 / bi, AMVP / merge / skip, whole-LCU 64x64 units, motion vectors
     that reach far outside the picture now and then), two reference pictures, rate tables and per-LCU lambdas spread over three decades -
     and what the CPU oracle makes of it in raster order.  Returns works, want, (reference planes, geometry), cost.
@@ -203,7 +204,7 @@ def random_inter_picture(oracle, w, h, qp, seed, pad=80, intra_lcus=1.0, tile_co
     assert matched or not wide
     fn = inter_oracle_fn(oracle, wide)
     rng = np.random.default_rng(seed)
-    works, _ = random_picture(oracle, w, h, qp, seed, tile_cols)           # trees, intra modes, QPs, source, tile edges
+    works, _ = random_picture(oracle, w, h, qp, seed, tile_cols, constrained=constrained, strong=strong)           # trees, intra modes, QPs, source, tile edges
     yy, xx = np.mgrid[0:h + 2 * pad, 0:w + 2 * pad]
     refs = []
     for r in range(2):
@@ -307,6 +308,74 @@ def test_encode_picture_random_b_pictures_match_oracle(product, oracle, w, h, qp
     finally:
         lib.svt_amd_encdec_picture_destroy(ctx, pic)
         lib.svt_amd_context_destroy(ctx)
+
+
+def constrained_neighbourhoods(works, w, h):
+    """the intra units of a constrained-intra picture by what their neighbour groups hold, from the work records alone (the mode map as the oracle keeps it:
+    the prediction mode of every unit coded so far, raster order of LCUs): (units whose groups - the ones coded, inside the picture and the tile, and allowed
+    by the Z order - are partly inter and partly intra, units whose groups are inter ones only: no group is available, intra units)"""
+    mp = np.full(((h + 3) // 4, (w + 3) // 4), 0xFF, np.uint8)
+    at = lambda px, py: 0xFE if px < 0 or py < 0 or px >= w or py >= h else int(mp[py >> 2, px >> 2])
+    mixed = empty = intra = 0
+    for wk in works:
+        for cu in wk["cu"][:int(wk["num_cus"])]:
+            x, y, n = int(cu["x"]), int(cu["y"]), int(cu["size"])
+            x0, y0, nb = int(wk["lcu_x"]) + x, int(wk["lcu_y"]) + y, n // 4
+            if int(cu["pred_mode"]) == 2:
+                pl, pt, pr = wk["tile_left"] and x == 0, wk["tile_top"] and y == 0, wk["tile_right"] and (x + n) & 63 == 0
+                kinds = [at(x0 - 1, y0 + 4 * k) for k in range(2 * nb) if not pl and (k < nb or cu["bottom_left_ok"])]
+                kinds += [at(x0 + 4 * k, y0 - 1) for k in range(2 * nb) if not pt and (k < nb or (cu["top_right_ok"] and not pr))]
+                kinds += [at(x0 - 1, y0 - 1)] if not pl and not pt else []
+                intra, mixed, empty = intra + 1, mixed + (1 in kinds and 2 in kinds), empty + (1 in kinds and 2 not in kinds)
+            mp[y0 >> 2:(y0 + n) >> 2, x0 >> 2:(x0 + n) >> 2] = cu["pred_mode"]
+    return mixed, empty, intra
+
+
+# w, h, qp, seed, arguments of random_inter_picture: B pictures of a ragged size encoded with constrained intra (tests/test_intra_ref_extremes_cpu.py counts them too)
+CONSTRAINED_PICTURES = [(264, 200, 30, 22, {}), (264, 200, 30, 23, dict(matched=True, wide=True))]      # 33 / 31 units with mixed groups, 29 / 21 with none
+
+
+@pytest.mark.parametrize("w,h,qp,seed,kw", CONSTRAINED_PICTURES)
+def test_encode_picture_constrained_intra_matches_oracle(product, oracle, gpu_ctx, w, h, qp, seed, kw):
+    """constrained intra in random B pictures: about four in five units are inter ones, so the intra units between them find neighbour groups that are partly
+    inter (unavailable, substituted) and partly intra, and some find none (mid-grey prediction) - an 8-bit sinusoid picture and a 10-bit one on matched planes"""
+    lib = product
+    sig_picture(lib)
+    wide = bool(kw.get("wide"))
+    works, want, refs_geom, cost = random_inter_picture(oracle, w, h, qp, seed, constrained=1, **kw)
+    assert (works["constrained_intra"] == 1).all()
+    mixed, empty, intra = constrained_neighbourhoods(works, w, h)
+    assert mixed >= 20 and empty >= 1, (mixed, empty, intra)
+    pic = C.c_void_p()
+    assert lib.svt_amd_encdec_picture_create(gpu_ctx, w, h, 2 if wide else 1, C.byref(pic)) == 0, lib.svt_amd_last_error()
+    try:
+        keep = set_inter_random(lib, gpu_ctx, pic, refs_geom, cost)
+        got = np.zeros(len(works), S.LCU_RESULT16_DTYPE if wide else S.LCU_RESULT_DTYPE)
+        fn = lib.svt_amd_encode_picture16 if wide else lib.svt_amd_encode_picture
+        assert fn(gpu_ctx, pic, works.ctypes.data, got.ctypes.data) == 0, lib.svt_amd_last_error()
+        for k in range(len(works)):
+            compare_lcu(works[k], want[k], got[k], w, h, ("constrained B picture", wide, k))
+        del keep
+    finally:
+        lib.svt_amd_encdec_picture_destroy(gpu_ctx, pic)
+
+
+def test_encode_picture_without_strong_smoothing_matches_oracle(product, oracle, gpu_ctx):
+    """an I picture with strong_smoothing 0 in every LCU: its 32x32 units keep the [1 2 1] filter however flat their neighbours are"""
+    lib = product
+    sig_picture(lib)
+    w, h = 200, 136
+    works, want = random_picture(oracle, w, h, 30, 23, strong=0)
+    assert (works["strong_smoothing"] == 0).all() and sum(int((wk["cu"]["size"][:int(wk["num_cus"])] == 32).sum()) for wk in works) >= 4
+    pic = C.c_void_p()
+    assert lib.svt_amd_encdec_picture_create(gpu_ctx, w, h, 1, C.byref(pic)) == 0, lib.svt_amd_last_error()
+    try:
+        got = np.zeros(len(works), S.LCU_RESULT_DTYPE)
+        assert lib.svt_amd_encode_picture(gpu_ctx, pic, works.ctypes.data, got.ctypes.data) == 0, lib.svt_amd_last_error()
+        for k in range(len(works)):
+            compare_lcu(works[k], want[k], got[k], w, h, ("I picture, no strong smoothing", k))
+    finally:
+        lib.svt_amd_encdec_picture_destroy(gpu_ctx, pic)
 
 
 @pytest.mark.parametrize("w,h,qp,seed", [(832, 480, 27, 1), (456, 264, 38, 2)])

@@ -182,3 +182,34 @@ def test_intra_pu_host_pointer_form(product, gpu_ctx, oracle):
         assert rc == 0, product.svt_amd_last_error()
         for p in range(3):
             assert np.array_equal(got[p], want[p]), (k, p)
+
+
+@pytest.mark.parametrize("bps", [1, 2])
+def test_intra_pu_on_the_smoothing_thresholds_matches_oracle(product, gpu_ctx, oracle, bps):
+    """the threshold grid and the size gate of tests/intra_ref_extremes.py as jobs (left, top and tl given directly), 32x32 and 16x16 in ONE launch per depth:
+    second differences of -thr, -(thr-1), thr-1 and thr on either side in all 16 pairs - thr 8 at 8 bits, 32 at 10 - filtered and unfiltered modes,
+    strong_smoothing set and clear, each with no_smoothing 0 and 1.  That the flag matters in exactly the cells inside both thresholds:
+    tests/test_intra_ref_extremes_cpu.py"""
+    import torch
+    import intra_ref_extremes as X
+    cases = X.grid_cases(bps) + X.gate_cases(bps)
+    jobs = np.concatenate([X.job_of(c, ns) for c in cases for ns in (0, 1)])
+    n = len(jobs)
+    assert set(jobs["size"].tolist()) == {16, 32} and set(jobs["strong_smoothing"].tolist()) == {0, 1}
+    jobs["dst_off_y"], jobs["dst_off_c"] = np.arange(n) * 1024, np.arange(n) * 256      # rows of 32 / 16 samples for every size: a block stays inside its slot
+    tdt = torch.uint8 if bps == 1 else torch.int16
+    d_j = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+    d_y, d_cb, d_cr = (torch.zeros(n * s, dtype=tdt, device="cuda") for s in (1024, 256, 256))
+    torch.cuda.synchronize()
+    product.svt_amd_intra_pu_batch.argtypes = [vp, C.c_int, vp, u32, vp, u32, vp, vp, u32]
+    assert product.svt_amd_intra_pu_batch(gpu_ctx, bps, d_j.data_ptr(), n, d_y.data_ptr(), 32, d_cb.data_ptr(), d_cr.data_ptr(), 16) == 0, \
+        product.svt_amd_last_error()
+    product.svt_amd_synchronize(gpu_ctx)
+    dt = np.uint8 if bps == 1 else np.uint16
+    hy, hcb, hcr = (a.cpu().numpy().view(dt) for a in (d_y, d_cb, d_cr))
+    for k in range(n):
+        s = int(jobs["size"][k])
+        got = [hy[k * 1024:(k + 1) * 1024].reshape(32, 32)[:s, :s]] + [a[k * 256:(k + 1) * 256].reshape(16, 16)[:s // 2, :s // 2] for a in (hcb, hcr)]
+        want = X.oracle_pu(oracle, bps, jobs[k:k + 1])
+        for p in range(3):
+            assert np.array_equal(got[p], want[p]), (cases[k // 2]["tag"], k & 1, p, np.argwhere(got[p] != want[p])[:4].tolist())
