@@ -1,6 +1,6 @@
 /* inter_position.h - where a list's motion-compensated block starts in its reference picture: the position clamp of EncodePassInterPrediction
  * (Codec/EbInterPrediction.c:802-812) and the split of the clamped position into integer sample and fraction.  One text for every kernel that addresses a reference
- * window - ep_inter_predict_core, ep_ref_windows_fill, ep_ref_windows_fill_chroma (encdec_device.h), md_predict_tile (md_kernels.hip) - for the host half of
+ * window - ep_inter_predict_core, ep_ref_windows_fill, ep_ref_windows_fill_chroma (encdec_device.h), md_predict_tile (md_inter.h) - for the host half of
  * svt_amd_inter_pu_batch (mcp_kernels.hip), and for tools/inter_position_check.c (a plain C program, tests/test_inter_position_cpu.py pins the values).
  * Plain C (with the statement expression gcc and clang both have); the accessors are __host__ __device__ under hipcc. */
 #ifndef SVT_AMD_INTER_POSITION_H

@@ -1,5 +1,5 @@
 /* md_lists.h - the AMVP and merge lists of a unit on registers (GenerateL0L1AmvpMergeLists, Codec/EbAdaptiveMotionVectorPrediction.c:2117-3005; ChooseMVPIdx_V2):
- * what the P / B unit loop md_units_inter and the test kernel k_md_lists_batch (both md_kernels.hip) are built on.  Device code: the including unit sets MD_FN for
+ * what the P / B unit loop md_units_inter (md_units_inter.h) and the test kernel k_md_lists_batch (md_kernels.hip) are built on.  Device code: the including unit sets MD_FN for
  * md_logic.h; MD_NB_ARGS expands to md_rl, which the unit loop defines where it uses the macro. */
 #ifndef SVT_AMD_MD_LISTS_H
 #define SVT_AMD_MD_LISTS_H

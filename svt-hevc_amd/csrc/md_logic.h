@@ -1,7 +1,7 @@
 /*
  * md_logic.h - the SCALAR decisions of the mode decision of one LCU (Codec/EbProductCodingLoop.c:4691 ModeDecisionLcu and what it calls),
  * restated once in the common subset of C99 and C++ so that the same text is
- *   - the per-coding-unit control code of the HIP kernel (md_kernels.hip; executed by one lane between the data-parallel stages), and
+ *   - the per-coding-unit control code of the HIP kernel (md_kernels.hip, md_units_inter.h; executed by one lane between the data-parallel stages), and
  *   - compiled by gcc into the CPU checker (oracle/svt_oracle_md.c), which runs it against the fixtures recorded from the reference
  *     (tests/golden/md_*.npz) without a GPU.
  * Nothing here touches samples: prediction, SAD, transform, quantiser, rate estimation and reconstruction are the callers' business

@@ -1,4 +1,4 @@
-/* md_picture.h - where the two translation units of the device-resident mode decision meet (not part of the C-ABI): md_kernels.hip holds every kernel and __device__
+/* md_picture.h - where the two translation units of the device-resident mode decision meet (not part of the C-ABI): md_kernels.hip (with the five headers of its device code, md_state.h .. md_units_inter.h) holds every kernel and __device__
  * function, md_picture.hip the picture state, the launch budget and the entries.  The picture's descriptor as the kernel reads it, and what the kernel unit offers the
  * host unit; nothing else crosses. */
 #ifndef SVT_AMD_MD_PICTURE_H
