@@ -975,6 +975,94 @@ SVT_AMD_API int svt_amd_initial_rc_batch_launch(SvtAmdContext *ctx, const SvtAmd
 SVT_AMD_API size_t svt_amd_initial_rc_bytes(uint16_t luma_width, uint16_t luma_height, int which);
 
 /*
+ * Batched scene-transition detection: SceneTransitionDetector of the picture decision (Codec/EbPictureDecisionProcess.c:73-258) - the one function of that
+ * process that reads data, and the one reader of the histograms svt_amd_side_stats_batch_launch and svt_amd_chroma_stats_batch_launch leave in HBM - for up to
+ * 256 CONSECUTIVE CALLS of the detector per call of this entry, stream-ordered on the context's lane like svt_amd_initial_rc_batch_launch: the call never blocks
+ * and never copies to the host, and it allocates at its first call only.  The host reads sizeof(SvtAmdScdPic) bytes a picture instead of 48 KB of histograms.
+ * Job i is the detector's call for one picture: ParentPcsWindow[0] the past, [1] the current, [2] the future picture.  Job i starts from the state job i - 1
+ * left (the running averages and resetRunningAvg of PictureDecisionContext_t); job 0 starts from *d_state_in (DEVICE), or from the constructor's state - all
+ * averages 0, the flag 1 (:63-68) - when d_state_in is NULL.  state[n - 1] of one batch is the d_state_in of the next.  WHICH pictures get a call is the
+ * caller's business, as the window lists of SvtAmdIrcJob are (PictureDecisionKernel :648-697): not picture 0, a past entry present, and four future entries
+ * present with none of them at end of sequence.
+ * Job (all pointers DEVICE memory, all required, read in place; they may be arrays an earlier launch on the same lane wrote):
+ *   past_histogram, cur_histogram                 uint32_t[regions_w][regions_h][256]      SvtAmdSideArrays.histogram of the picture
+ *   past_chroma_histogram, cur_chroma_histogram   uint32_t[regions_w][regions_h][2][256]   SvtAmdChromaArrays.histogram of the picture
+ *   past_region_average, cur_region_average, future_region_average   the picture's 64-byte row of SvtAmdSideArrays.region_average; bytes 0 .. regions - 1 are read
+ *   past_detect, cur_detect                       the SvtAmdPaPicDetect record, read for pic_avg_variance
+ * Region (wi, hi) - wi the width index, the OUTER loop - is region wi * regions_h + hi of every [16] below.  The rules, restated as the reference has them
+ * (nothing is repaired; tests/scd_numpy.py spells every width out, svt-hevc_amd/csrc/scd_logic.h is the one text the kernels compile), W x H the luma size:
+ *   vote threshold  (EB_U32)((float)(regions * P) / 100 + 0.5), P 75 for scd_mode 2 and 50 otherwise (:126-128) = (regions * P + 50) / 100 in integers
+ *   region size     regionWidth = W / regions_w and regionHeight = H / regions_h are set ONCE in front of the loops; inside them `regionWidth += W - regions_w *
+ *                   regionWidth` runs in the last column and `regionHeight += H - regions_h * regionHeight` in the last row (:147-156), on the values the
+ *                   iterations before left, in 32-bit unsigned arithmetic.  After k such steps a size is q + rem * (1 + (1 - regions) + .. + (1 - regions)^(k - 1))
+ *                   with q the quotient and rem the remainder; the width has taken hi + 1 steps in the last column and none before it, the height wi + (hi ==
+ *                   regions_h - 1).  With remainders of 0 (4 x 4 regions, sizes that are multiples of 8) every region is W / 4 x H / 4
+ *   thresholds      T * ((regionWidth * regionHeight) >> 12) in 32 bits; T 4500 when |cur - past| of pic_avg_variance > 390 and either exceeds 1500, else 3000
+ *                   (:158-163); for chroma a quarter of it
+ *   ahd             per plane the sum over the 256 bins of |cur - past| (:167-172)
+ *   running averages   with the reset flag all three take the three sums (:174-178); error = |average - ahd| per plane.  Only the luma average is updated
+ *                   afterwards: the chroma averages change at a reset alone
+ *   region class    abrupt: (error > th && ahd >= error) for luma, or the same with the chroma threshold for Cb or Cr; else gradual: error > th / 2 && ahd >=
+ *                   error for luma (:185-194).  An abrupt region is a flash (class 2) when |future - past| < 5 && |future - cur| >= 5 && |cur - past| >= 5 of the
+ *                   luma region averages, else a fade (3) when |future - cur| < 3 && |cur - past| < 3, else a scene change (4); its luma average is NOT
+ *                   updated (:196-214).  A gradual region (1) and a region of neither class (0) set average = (3 * average + ahd) / 4 in 32 bits (:215-232)
+ *   after the loops reset_running_avg = abrupt regions >= vote threshold; scene_change, the return value, = scene-change regions >= vote threshold (:243-256)
+ * Two stages in stream order - a workgroup per region and job (a thread per bin, the three sums reduced by wave shuffles and four words of LDS, stored - not
+ * added), then ONE wave with a lane per region that walks the jobs in order, its running averages in registers, the two counts population counts of wave
+ * ballots.  No atomics, nothing to zero; every array is written by one kernel only.  The arrays are DEVICE memory, all required, job i at index i; every byte
+ * of a job's part is written, pads and the entries of regions beyond regions_w * regions_h as 0.
+ * regions_w, regions_h 1..4 each (MAX_NUMBER_OF_REGIONS_IN_WIDTH / _HEIGHT); scd_mode 1 or 2; luma_width, luma_height from 8 x 8 up to 16,384 LCUs - no picture
+ * slot is read, so the picture need not fit the context.  Everything is checked before anything is queued: a NULL context, jobs or out, a job count outside
+ * 1..256, regions outside 1..4, scd_mode outside 1..2, a size below 8 or above the bound, a NULL array or a NULL pointer in a job return SVT_AMD_ERR_BAD_PARAM
+ * (svt_amd_last_error names the entry, and the job where one is at fault; a size above the bound is refused in the words all batched entries share, which say
+ * "job 0" for the batch's size), queue nothing and wait for nothing.
+ */
+#define SVT_AMD_SCD_MAX_LCUS    16384
+#define SVT_AMD_SCD_MAX_REGIONS 16
+#define SVT_AMD_SCD_CLASS_NONE    0
+#define SVT_AMD_SCD_CLASS_GRADUAL 1
+#define SVT_AMD_SCD_CLASS_FLASH   2
+#define SVT_AMD_SCD_CLASS_FADE    3
+#define SVT_AMD_SCD_CLASS_SCENE   4
+typedef struct SvtAmdScdJob {
+    const uint32_t *past_histogram, *cur_histogram;
+    const uint32_t *past_chroma_histogram, *cur_chroma_histogram;
+    const uint8_t  *past_region_average, *cur_region_average, *future_region_average;
+    const SvtAmdPaPicDetect *past_detect, *cur_detect;
+} SvtAmdScdJob;                             /* 72 bytes */
+typedef struct SvtAmdScdPic {
+    uint8_t scene_change;                   /* the detector's return value: sceneChangeFlag (:697)                  */
+    uint8_t reset_running_avg;              /* contextPtr->resetRunningAvg after the call (:243-248)                */
+    uint8_t abrupt_regions;                 /* isAbruptChangeCount                                                  */
+    uint8_t scene_regions;                  /* isSceneChangeCount                                                   */
+    uint8_t region_count_threshold;         /* regionCountThreshold (:126-128)                                      */
+    uint8_t pad[3];                         /* 0 */
+    uint8_t region_class[16];               /* SVT_AMD_SCD_CLASS_*: the branch the region took; 0 beyond the regions */
+} SvtAmdScdPic;                             /* 24 bytes */
+typedef struct SvtAmdScdState {             /* PictureDecisionContext_t as the detector reads and leaves it */
+    uint32_t ahd_running_avg[16];           /* ahdRunningAvg[wi][hi] at wi * regions_h + hi; written as 0 beyond the regions */
+    uint32_t ahd_running_avg_cb[16];        /* ahdRunningAvgCb */
+    uint32_t ahd_running_avg_cr[16];        /* ahdRunningAvgCr */
+    uint8_t  reset_running_avg;             /* resetRunningAvg: any non-zero byte is a set flag; written as 0 / 1   */
+    uint8_t  pad[3];                        /* 0 */
+} SvtAmdScdState;                           /* 196 bytes */
+typedef struct SvtAmdScdArrays {            /* DEVICE pointers, job i of the batch at index i; all required */
+    SvtAmdScdPic   *picture;                /* [n]        */
+    uint32_t       *ahd;                    /* [n][16][3]: the sums of luma, Cb, Cr per region */
+    SvtAmdScdState *state;                  /* [n]: the context AFTER job i */
+} SvtAmdScdArrays;
+SVT_AMD_API int svt_amd_scene_detect_batch_launch(SvtAmdContext *ctx, const SvtAmdScdJob *jobs, int num_jobs, uint16_t luma_width, uint16_t luma_height,
+                                                  int regions_w, int regions_h, int scd_mode, const SvtAmdScdState *d_state_in, const SvtAmdScdArrays *out);
+#define SVT_AMD_SCD_PICTURE 0
+#define SVT_AMD_SCD_AHD     1
+#define SVT_AMD_SCD_STATE   2
+/* bytes ONE job takes in array `which`; 0 for an unknown `which` or regions outside 1..4.  Host arithmetic: no context, no device. */
+SVT_AMD_API size_t svt_amd_scene_detect_bytes(int which, int regions_w, int regions_h);
+/* Development aid (tools/scd_time.py): the stages the launches of this process run from now on - bit 0 k_scd_ahd, bit 1 k_scd_decide; 3 is the start value and
+ * the only one that gives complete results on arrays that hold none yet. */
+SVT_AMD_API void svt_amd_debug_scene_detect_stages(int mask);
+
+/*
  * Batched mode-decision LCU controls: the SvtAmdMdLcu records (below, "Device-resident mode decision") svt_amd_md_encode_picture* reads, assembled on the device from
  * the records of the batches above - what integration/svt_md_fill.h:svt_md_fill_lcu reads out of the reference's control sets on the host - for up to 256 pictures
  * of ONE geometry per call, stream-ordered on the context's lane like svt_amd_initial_rc_batch_launch: the call never blocks and never copies to the host, and it

@@ -81,8 +81,8 @@ struct PackSrc {
 
 /* the batched, stream-ordered entries of pa_batch.h: each owns one device allocation of the context (SvtAmdContext.d_batch), what follows the descriptor table
  * in it is the entry's own.  side / chroma: per-region sums; detect / noise: a per-picture reduction; sbo: per-workgroup partials and per-LCU flags; mdc: per-LCU
- * scores and flags; irc: per-workgroup vote totals, per-LCU votes and flags; mdctl: the check record of a bound controls array */
-enum SvtAmdBatchEntry { BATCH_SIDE, BATCH_CHROMA, BATCH_DETECT, BATCH_NOISE, BATCH_SBO, BATCH_MDC, BATCH_IRC, BATCH_MDCTL, BATCH_ENTRIES };
+ * scores and flags; irc: per-workgroup vote totals, per-LCU votes and flags; mdctl: the check record of a bound controls array; scd: nothing */
+enum SvtAmdBatchEntry { BATCH_SIDE, BATCH_CHROMA, BATCH_DETECT, BATCH_NOISE, BATCH_SBO, BATCH_MDC, BATCH_IRC, BATCH_MDCTL, BATCH_SCD, BATCH_ENTRIES };
 
 struct SvtAmdContext {
     int device;
